@@ -7,14 +7,20 @@ Jasper 10x5 Dense-Residual (BASELINE.json configs[1]) on synthetic 16 kHz-shaped
 feature batches already resident in HBM, one process per GPU (RCCL through
 torch.distributed under torchrun), and prints ONE JSON line on rank 0.
 
+A plain run does only that: set up, warm up, time the K steps, print the line.
+`--full` adds everything else the bench measures (the blocks marked [full]
+below, the Transformer-big secondary, the other BASELINE configs, the front end
+alone, the all-reduce timing of a multi-rank run). `--dump-outputs DIR` writes
+what the last timed step computed as DIR/<name>.npy (see dump_outputs).
+
 metric  = what `run.py --benchmark` prints as "Avg objects per second"
           (open_seq2seq/utils/funcs.py:192-218): sum over ranks of INPUT feature
           frames (sum of src_length, models/speech2text.py:356-360) / wall time.
-roofline = the dominant kernel (implicit-GEMM conv1d on the matrix cores, used by
+roofline = [full] the dominant kernel (implicit-GEMM conv1d on the matrix cores, used by
           forward and data-gradient): algorithmic FLOPs of its launches / their
           measured durations (HIP events on the launch stream, live in the timed
           region) vs the dense bf16 MFMA peak.
-cpu_baseline = the CPU oracle (fp32 restatement of the reference's path, torch-CPU
+cpu_baseline = [full] the CPU oracle (fp32 restatement of the reference's path, torch-CPU
           + NumPy NovoGrad) timed on the host cores on a bounded sample.
 """
 import argparse
@@ -41,6 +47,12 @@ def parse():
   ap.add_argument("--gpus", type=int, default=1)
   ap.add_argument("--steps", type=int, default=20)
   ap.add_argument("--warmup", type=int, default=5)
+  ap.add_argument("--full", action="store_true",
+                  help="besides the headline: roofline / per-kernel timing and shader clock, the Transformer-big "
+                       "secondary, the other BASELINE configs, the front end alone, the CPU baselines, the all-reduce "
+                       "timing of a multi-rank run (the --no-* flags below switch parts of it off)")
+  ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                  help="write what the last timed step of the headline run computed as DIR/<name>.npy")
   ap.add_argument("--batch", type=int, default=32, help="batch_size_per_gpu (reference: 32)")
   ap.add_argument("--fixed-frames", type=int, default=0,
                   help="0: durations U[2,16.7]s (default workload); >0: every utterance has "
@@ -1082,8 +1094,53 @@ def launcher_dry_run(args, hvd, rank, world):
                                  "units_sum_over_ranks": float(units.item())}})
 
 
+DUMP_SAMPLE = 1 << 21       # positions of the sampled weight / moment buffers (8 MB of float32 each)
+
+
+def dump_outputs(out_dir, model, loss):
+  """--dump-outputs: what the last timed step hands its caller, as out_dir/<name>.npy in float32 — the loss, and
+  the state the update wrote: the fp32 master weights and NovoGrad first moments at DUMP_SAMPLE fixed, seeded
+  positions of the variables laid end to end in creation order (padding of the flat buffers excluded), the
+  per-variable second moments, the BatchNorm moving statistics and the loss scale. The weights, the batch and the
+  dropout seeds all derive from fixed seeds, and the reductions of the Jasper step sum in a fixed order (its
+  lockstep weight gradients sum their splits in split order with the stream's workspace), so two runs with the
+  same arguments write the same bits (tests/test_bench_contract.py::test_dump_outputs_same_bits_on_every_run) and
+  two builds compare entry for entry."""
+  import numpy as np
+  store = model.store
+  st = model.train_op.read_state()              # waits for the asynchronous update of the last step
+  torch.cuda.synchronize()
+  sizes = np.array([p.numel for p in store.params], np.int64)
+  starts = np.concatenate([[0], np.cumsum(sizes)])
+  pos = np.sort(np.random.RandomState(20241015).randint(0, int(starts[-1]), size=min(DUMP_SAMPLE, int(starts[-1]))))
+  var = np.searchsorted(starts, pos, side="right") - 1
+  offsets = np.array([p.offset for p in store.params], np.int64)
+  flat = torch.from_numpy(offsets[var] + (pos - starts[var])).to(store.master.device)
+  arrays = {
+      "loss": loss.float(),
+      "weights_sample": store.master[flat],
+      "first_moments_sample": store.m1[flat],
+      "second_moments": store.t_v,
+      "batchnorm_statistics": torch.cat([t.float().flatten() for t in store.state.values()]) if store.state
+                              else torch.zeros(0),
+      "loss_scale": torch.tensor([float(st["loss_scale"])]),
+  }
+  os.makedirs(out_dir, exist_ok=True)
+  for name, t in arrays.items():
+    np.save(os.path.join(out_dir, name + ".npy"), t.detach().float().cpu().numpy())
+
+
 def main():
   args = parse()
+  if args.steps < 1:
+    raise SystemExit("bench.py: --steps must be at least 1 (the line reports the time of one timed step)")
+  if not args.full:       # a plain run times the headline only
+    args.no_kernel_timing = args.no_transformer = args.no_other_configs = args.no_cpu_baseline = True
+  only = [k for k in ("only_quartznet", "only_tacotron", "only_ds2", "only_nmt", "only_transformer_infer",
+                      "only_frontend", "only_tacotron_decode", "only_transformer") if getattr(args, k)]
+  if args.dump_outputs and only:
+    raise SystemExit("bench.py: --dump-outputs writes the headline run's outputs; it does not go with --%s"
+                     % only[0].replace("_", "-"))
   if args.cpu_nmt_leg:
     emit(cpu_baseline_nmt(torch.load(args.cpu_nmt_leg)))
     return
@@ -1241,7 +1298,7 @@ def main():
     except Exception as e:
       print("bench.py: no shader-clock probe (%r)" % (e,), file=sys.stderr)
   timer.enabled = not args.no_kernel_timing and rank == 0
-  reducer = getattr(model, "_reducer", None)
+  reducer = getattr(model, "_reducer", None) if args.full else None
   if reducer is not None:
     reducer.timing = True           # a few event records per step (one pair per 128 MB bucket)
   t0 = time.perf_counter()
@@ -1250,6 +1307,8 @@ def main():
   barrier()
   dt = time.perf_counter() - t0
   timer.enabled = False
+  if args.dump_outputs and rank == 0:
+    dump_outputs(args.dump_outputs, model, loss)
   shader_mhz = None
   if clock_probe is not None:
     try:
@@ -1442,7 +1501,7 @@ def main():
     except Exception as e:
       others["tacotron_decode"] = {"error": repr(e)}
     out["other_configs"] = others
-  if world == 1:
+  if world == 1 and args.full:
     try:
       out["frontend"] = bench_frontend(dev, args.batch)
     except Exception as e:

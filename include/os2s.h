@@ -342,7 +342,9 @@ int os2s_conv1d_wgrad_ex(os2s_stream_t stream, const uint16_t* x, long long x_ro
  * cuts the reduction over the live (sample, 64-row) chunks when a layer has too few
  * (co, ci, tap) tiles to fill the chip; partial tiles are reduced in a fixed order by one
  * owner per tile, which also adds the previous dW when accumulate = 1: no fp32 atomics, results
- * are run-to-run identical. */
+ * are run-to-run identical. Other shapes (stride > 1, K = 1, narrow layers) with accumulate = 1 may
+ * split the batch as well: each split stores its partial dW in the workspace's slab area and one
+ * more launch adds them to dW in split order (as many splits as that area holds). */
 int os2s_conv1d_wgrad_ws(os2s_stream_t stream, const uint16_t* x, long long x_row_stride,
                          const uint16_t* dy, float* dw, const int32_t* in_len, int B, int Tin,
                          int Cin, int Cout, int K, int stride, int dil, int padL, int Tout,

@@ -21,8 +21,9 @@
 //     (64 + dil)-row X window: halves L2->LDS bytes per FLOP;
 //   * grid = (co tile, ci tile, batch split) x tap pairs; tap pairs of one tile
 //     are adjacent on one XCD so dY/X tiles are L2 hits for all but the first;
-//   * batch splits are combined with fp32 atomics only when a layer is too
-//     small to fill the chip otherwise.
+//   * batch splits, only when a layer is too small to fill the chip otherwise,
+//     store partial dW tiles that one more launch sums in split order (with a
+//     workspace), or are combined with fp32 atomics (without one).
 #include <stdlib.h>
 
 #include <cstdlib>
@@ -39,6 +40,9 @@ struct WgradArgs {
   const int32_t* in_len;
   int B, Tin, Tout, Cin, Cout, K, stride, dil, padL;
   int NCO, NCI, NTP, NSPLIT, steps_per_split, use_atomic;
+  // lockstep kernel with a split reduction: split s stores its partial dW at part + s * K * Cout * Cin (a slab area of
+  // the stream's workspace) and wgrad_split_sum_kernel adds the partials to dw in split order; nullptr: into dw
+  float* part;
   int xrows, xrows_pad;  // X window rows per 64-step (and padded to x4)
   int xbuf_bytes, steptab_bytes;   // ping-pong kernel: X ring slot size, step table size
   long long x_ld;        // x row stride in elements (>= Cin; channel slice of a wider tensor)
@@ -247,7 +251,8 @@ __device__ __forceinline__ void wgrad_lockstep_unit(const WgradArgs& p, const in
 #pragma unroll
   for (int a = 0; a < TAPS; ++a) {
     if (a < ntaps) {
-      float* const dwk = p.dw + (long long)(k0 + a) * p.Cout * p.Cin;
+      float* const dw0 = p.part ? p.part + (long long)split * p.K * p.Cout * p.Cin : p.dw;
+      float* const dwk = dw0 + (long long)(k0 + a) * p.Cout * p.Cin;
 #pragma unroll
       for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -267,6 +272,18 @@ __device__ __forceinline__ void wgrad_lockstep_unit(const WgradArgs& p, const in
           }
         }
     }
+  }
+}
+
+// dw[e] += part[0][e] + part[1][e] + ... + part[nsplit - 1][e], in split order: the lockstep kernel's split reduction
+// with the same bits on every run (part: [nsplit][n] fp32, every element written by its split).
+__global__ __launch_bounds__(256) void wgrad_split_sum_kernel(const float* __restrict__ part, float* __restrict__ dw,
+                                                              long long n, int nsplit) {
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
+    float s = 0.f;
+#pragma unroll 8
+    for (int k = 0; k < nsplit; ++k) s += part[(long long)k * n + i];   // loads issued together, added in order
+    dw[i] += s;
   }
 }
 
@@ -1118,8 +1135,10 @@ __global__ __launch_bounds__(512, 2) void conv1d_wgrad1x1_pp_kernel(WgradArgs p,
 // With a workspace (os2s_conv1d_workspace_bytes(), zero tickets, one per stream — the same
 // contract as os2s_conv1d_fwd_ws) the ping-pong kernel spreads small layers over the chip by
 // cutting the reduction; its result is deterministic and written by one owner per element.
-// The lockstep kernel (stride > 1, K = 1, narrow layers) splits the batch with fp32 atomics when
-// accumulate = 1 and the layer is too small to fill the chip otherwise.
+// The lockstep kernel (stride > 1, K = 1, narrow layers) splits the batch when accumulate = 1 and
+// the layer is too small to fill the chip otherwise: with a workspace the splits' partial dW go to
+// its slab area and are summed in split order (deterministic), without one they add into dW with
+// fp32 atomics.
 static int conv1d_wgrad_impl(os2s_stream_t stream, const uint16_t* x, long long x_row_stride,
                              const uint16_t* dy, float* dw, const int32_t* in_len, int B,
                              int Tin, int Cin, int Cout, int K, int stride, int dil,
@@ -1247,7 +1266,7 @@ static int conv1d_wgrad_impl_g(os2s_stream_t stream, const uint16_t* x, long lon
   a.B = B; a.Tin = Tin; a.Tout = Tout; a.Cin = Cin; a.Cout = Cout; a.K = K;
   a.stride = stride; a.dil = dil; a.padL = padL; a.x_ld = x_row_stride;
   a.accumulate = accumulate ? 1 : 0;
-  a.ws_slabs = nullptr; a.ws_cnt = nullptr; a.ws_nslabs = 0; a.ncu = 256; a.force_split = g_wgrad_split;
+  a.part = nullptr; a.ws_slabs = nullptr; a.ws_cnt = nullptr; a.ws_nslabs = 0; a.ncu = 256; a.force_split = g_wgrad_split;
   a.dbg = g_wgrad_dbg; a.dbg_mode = g_wgrad_dbg_mode; a.xcd_order = g_wgrad_xcd; a.NG = 1;
   for (int i = 0; i < 8; ++i) { a.gx[i] = nullptr; a.gdy[i] = nullptr; a.gdw[i] = nullptr; }
   if (groups) {
@@ -1442,9 +1461,21 @@ static int conv1d_wgrad_impl_g(os2s_stream_t stream, const uint16_t* x, long lon
     if (nsplit < 1) nsplit = 1;
     if (os2s_deterministic()) nsplit = 1;     // one add per dW element
   }
+  // With a workspace the splits' partials are summed in a fixed order, not with fp32 atomics into dW (whose order
+  // changes from run to run): they go to the slab area of the workspace, as many splits as it holds. Without one
+  // (os2s_conv1d_wgrad / _ex) the splits add into dW with fp32 atomics.
+  const long long dw_elems = (long long)K * Cout * Cin;
+  if (workspace) {
+    const long long part_room = workspace_bytes > kSplitTicketBytes
+                                    ? (long long)((workspace_bytes - kSplitTicketBytes) / ((size_t)dw_elems * 4)) : 0;
+    if (nsplit > part_room) nsplit = (int)part_room;
+    if (nsplit < 1) nsplit = 1;
+  }
   a.steps_per_split = ceil_div(total_steps, nsplit);
   a.NSPLIT = ceil_div(total_steps, a.steps_per_split);
-  a.use_atomic = accumulate ? 1 : 0;
+  if (workspace && a.NSPLIT > 1)
+    a.part = reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) + kSplitTicketBytes);
+  a.use_atomic = (accumulate && !a.part) ? 1 : 0;
   a.xrows = 63 * stride + (TAPS - 1) * dil + 1;
   a.xrows_pad = ceil_div(a.xrows, 4) * 4;
   const size_t smem = (size_t)2 * 64 * 2 * COT + (size_t)2 * a.xrows_pad * 256;
@@ -1475,6 +1506,11 @@ static int conv1d_wgrad_impl_g(os2s_stream_t stream, const uint16_t* x, long lon
       OS2S_LAUNCH((conv1d_wgrad_kernel<1, 128>), dim3(grid), dim3(256), smem, (hipStream_t)stream, a);
     else
       OS2S_LAUNCH((conv1d_wgrad_kernel<2, 128>), dim3(grid), dim3(256), smem, (hipStream_t)stream, a);
+  }
+  if (a.part) {
+    const int blocks = ceil_div(dw_elems, 256) < 2048 ? ceil_div(dw_elems, 256) : 2048;
+    OS2S_LAUNCH(wgrad_split_sum_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream,
+                (const float*)a.part, dw, dw_elems, a.NSPLIT);
   }
   return OS2S_OK;
 }
@@ -1508,7 +1544,7 @@ extern "C" int os2s_conv1x1_wgrad_grouped(os2s_stream_t stream, const os2s_wgrad
   a.x = nullptr; a.dy = nullptr; a.dw = nullptr; a.in_len = in_len;
   a.B = B; a.Tin = T; a.Tout = T; a.Cin = 0; a.Cout = 0; a.K = 1;
   a.stride = 1; a.dil = 1; a.padL = 0; a.x_ld = 0; a.accumulate = 1;
-  a.ws_slabs = nullptr; a.ws_cnt = nullptr; a.ws_nslabs = 0; a.ncu = 256; a.force_split = -1;
+  a.part = nullptr; a.ws_slabs = nullptr; a.ws_cnt = nullptr; a.ws_nslabs = 0; a.ncu = 256; a.force_split = -1;
   a.dbg = nullptr; a.dbg_mode = 0; a.xcd_order = g_wgrad_xcd; a.NG = 1;
   a.NCO = 0; a.NCI = 0; a.NTP = 1;
   a.steps_per_split = ceil_div(total_steps, nsplit);
@@ -1576,7 +1612,7 @@ extern "C" int os2s_conv1x1_wgrad_grouped_ws(os2s_stream_t stream, const os2s_wg
   a.B = B; a.Tin = T; a.Tout = T; a.Cin = gt.g[0].Cin; a.Cout = gt.g[0].Cout; a.K = 1;
   a.stride = 1; a.dil = 1; a.padL = 0; a.x_ld = gt.g[0].x_ld;
   a.accumulate = 1;
-  a.ws_slabs = nullptr; a.ws_cnt = nullptr; a.ws_nslabs = 0; a.ncu = 256; a.force_split = g_wgrad_split;
+  a.part = nullptr; a.ws_slabs = nullptr; a.ws_cnt = nullptr; a.ws_nslabs = 0; a.ncu = 256; a.force_split = g_wgrad_split;
   a.dbg = nullptr; a.dbg_mode = 0; a.xcd_order = g_wgrad_xcd; a.NG = 1;
   a.NCO = units; a.NCI = 1; a.NTP = 1;                   // U = NCO * NCI = all units of all groups
   a.NSPLIT = 1; a.steps_per_split = 0; a.use_atomic = 0;
@@ -1638,7 +1674,7 @@ extern "C" int os2s_gemm_wgrad_grouped(os2s_stream_t stream, const os2s_wgrad_gr
   a.B = 1; a.Tin = (int)M; a.Tout = (int)M; a.Cin = gt.g[0].Cin; a.Cout = gt.g[0].Cout; a.K = 1;
   a.stride = 1; a.dil = 1; a.padL = 0; a.x_ld = gt.g[0].x_ld;
   a.accumulate = accumulate ? 1 : 0;
-  a.ws_slabs = nullptr; a.ws_cnt = nullptr; a.ws_nslabs = 0; a.ncu = 256; a.force_split = g_wgrad_split;
+  a.part = nullptr; a.ws_slabs = nullptr; a.ws_cnt = nullptr; a.ws_nslabs = 0; a.ncu = 256; a.force_split = g_wgrad_split;
   a.dbg = nullptr; a.dbg_mode = 0; a.xcd_order = g_wgrad_xcd; a.NG = 1;
   a.NCO = units; a.NCI = 1; a.NTP = 1;                   // U = NCO * NCI = all units of all groups
   a.NSPLIT = 1; a.steps_per_split = 0; a.use_atomic = 0;

@@ -15,6 +15,9 @@ reference checkout (only runnable where /root/reference exists).
                           Kept at the path the reference's configs name, relative to the repository root, so
                           that `python run.py --config_file=open_seq2seq/test_utils/test_speech_configs/...`
                           runs as in the reference (tests/test_speech_acceptance_gpu.py).
+  ctc_greedy_ref_ids.npz <- what the reference's decoders/ctc_greedy_decoder.cpp (compiled into oracle/_ref/
+                          by build()) decodes from ctc_greedy_cases(): the golden utterance and 20 seeded
+                          random ones (tests/test_ctc_greedy_oracle.py; `python make_golden.py ctc_greedy`)
 """
 import json
 import os
@@ -71,5 +74,40 @@ def main():
   print("wrote", OUT)
 
 
+def softmax(x):
+  e = np.exp(x - x.max(-1, keepdims=True))
+  return e / e.sum(-1, keepdims=True)
+
+
+def ctc_greedy_cases(seq):
+  """[(name, logits [T, 1, V] float32)]: the golden utterance, then 20 seeded ragged ones with peaky logits so that
+  repeats and blanks are frequent (NumPy only: the test builds the same cases)."""
+  cases = [("golden", seq)]
+  rng = np.random.RandomState(1)
+  for trial in range(20):
+    T, V = int(rng.randint(1, 200)), int(rng.randint(2, 40))
+    lg = (rng.randn(T, 1, V) * 3).astype(np.float32)
+    lg[:, 0, V - 1] += 2.0
+    lg = np.repeat(lg, rng.randint(1, 4), axis=0)[:T]
+    cases.append(("trial%02d" % trial, lg))
+  return cases
+
+
+def ctc_greedy_ref_ids():
+  import sys
+  sys.path.insert(0, os.path.dirname(os.path.dirname(OUT)))
+  from oracle import ctc_greedy as og
+  assert og.reference_cpp_available(), "build() first: oracle/_ref/libref_ctc_greedy.so"
+  seq = np.load(os.path.join(OUT, "ctc_test_logits.npy"))
+  ids = {name: og.greedy_reference_cpp(softmax(lg[:, 0, :].astype(np.float64))).astype(np.int32)
+         for name, lg in ctc_greedy_cases(seq)}
+  np.savez(os.path.join(OUT, "ctc_greedy_ref_ids.npz"), **ids)
+  print("wrote", os.path.join(OUT, "ctc_greedy_ref_ids.npz"))
+
+
 if __name__ == "__main__":
-  main()
+  import sys
+  if sys.argv[1:] == ["ctc_greedy"]:
+    ctc_greedy_ref_ids()
+  else:
+    main()

@@ -1,8 +1,10 @@
-"""The committed bench line (profiles/*_bench_default.json = stdout of `python bench.py` on an
+"""The committed bench line (profiles/*_bench_default.json = stdout of `python bench.py --full` on an
 MI355X) carries every field of the measurement contract, with consistent arithmetic."""
 import glob
 import json
 import os
+
+import pytest
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -199,3 +201,39 @@ def test_with_headline_puts_both_metrics_in_the_tail():
   c = json.loads(line)["config"]
   assert c["secondary_value"] == 9.0 and c["secondary_ms_per_step"] == 4.0 and c["secondary_roofline_frac"] == 0.25
   assert c["tacotron_decode_us_per_step"] == 30.0 and c["ds2_ms_per_step"] == 50.0
+
+
+@pytest.mark.gpu
+def test_dump_outputs_same_bits_on_every_run(cuda, tmp_path):
+  """`--dump-outputs`: two plain runs with the same arguments (fresh processes) write the same files, bit for bit —
+  seeded inputs and a step whose reductions sum in a fixed order; --steps is the number of timed steps."""
+  import subprocess
+  import sys
+  import numpy as np
+  outs = []
+  for i in range(2):
+    d = tmp_path / ("run%d" % i)
+    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                        "--batch", "8", "--dump-outputs", str(d)],
+                       stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
+    assert r.returncode == 0, r.stderr[-3000:]
+    line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    assert line["steps"] == 3 and line["ms_per_step"] > 0 and "roofline" not in line
+    outs.append(d)
+  names = sorted(os.listdir(outs[0]))
+  assert names == sorted(os.listdir(outs[1])) and "loss.npy" in names and "weights_sample.npy" in names
+  total = 0
+  for n in names:
+    a, b = np.load(outs[0] / n), np.load(outs[1] / n)
+    assert a.dtype in (np.float32, np.float64) and np.isfinite(a).all(), n
+    assert a.shape == b.shape and a.tobytes() == b.tobytes(), n
+    total += a.nbytes
+  assert total <= 64 << 20
+
+
+def test_bench_refuses_zero_steps():
+  import subprocess
+  import sys
+  r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--steps", "0", "--launcher-dry-run"],
+                     stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
+  assert r.returncode != 0 and "--steps" in r.stderr

@@ -6,9 +6,10 @@ import os
 import pytest
 
 REF = "/root/reference/example_configs"
-pytestmark = pytest.mark.skipif(not os.path.isdir(REF), reason="reference checkout not present")
+needs_ref = pytest.mark.skipif(not os.path.isdir(REF), reason="reference checkout not present")
 
 
+@needs_ref
 def test_jasper_config_loads_and_maps():
   from openseq2seq_amd.utils.utils import get_base_config
   cfg = os.path.join(REF, "speech2text", "jasper10x5_LibriSpeech_nvgrad_masks.py")
@@ -31,6 +32,7 @@ def test_jasper_config_loads_and_maps():
       getattr(__import__("sys").modules["tensorflow"], "__version__", "").endswith("shim") is False
 
 
+@needs_ref
 def test_transformer_big_config_loads_and_maps():
   from openseq2seq_amd.utils.utils import get_base_config
   cfg = os.path.join(REF, "text2text", "en-de", "transformer-big.py")
@@ -56,6 +58,7 @@ def test_unknown_param_is_rejected():
                  "bogus": 1}, None)
 
 
+@needs_ref
 def test_baseline_configs_load_unchanged():
   """The example configs BASELINE.json names (plus their infer / eval variants) load through the
   reference's own runpy path and resolve to classes of this package."""
@@ -83,6 +86,7 @@ def test_baseline_configs_load_unchanged():
   assert mod["infer_params"]["decoder_params"]["beam_width"] == 10
 
 
+@needs_ref
 def test_toy_speech_test_configs_equal_the_reference():
   """open_seq2seq/test_utils/test_speech_configs/*.py of THIS repository restate the reference's acceptance
   configurations (DS2 / W2L convergence tests, block-dropout runs): same dictionaries, value for value (the

@@ -51,6 +51,37 @@ def test_conv_weight_gradients_bit_identical(det, cuda):
     torch.testing.assert_close(a, c, rtol=2e-4, atol=2e-3)
 
 
+def test_conv_weight_gradient_split_is_bit_identical_by_default(det, cuda):
+  """Default mode, the lockstep kernel's reduction split with the stream's workspace (the shapes of Jasper's first
+  stride-2 layer, its last 1x1 layer and the FC decoder, ragged lengths): the per-split partials are summed in split
+  order, so two launches give the same bits; the sum agrees with the one-contributor geometry and with the split
+  that adds with fp32 atomics (no workspace) to fp32 summation-order accuracy."""
+  capi = det
+  capi.set_deterministic(False)
+  g = torch.Generator().manual_seed(1)
+  for (B, T, Cin, Cout, K, stride) in [(32, 640, 64, 256, 11, 2), (32, 320, 896, 1024, 1, 1),
+                                       (32, 320, 1024, 32, 1, 1)]:
+    x = torch.randn(B, T, Cin, generator=g).to(torch.bfloat16).to(cuda)
+    tout = (T + stride - 1) // stride
+    dy = torch.randn(B, tout, Cout, generator=g).to(torch.bfloat16).to(cuda)
+    lens = torch.randint(T // 4, T + 1, (B,), generator=g).to(torch.int32).to(cuda)
+    init = torch.randn(K, Cout, Cin, generator=g).to(cuda)
+
+    def run(use_workspace=True):
+      dw = init.clone()
+      capi.conv1d_wgrad(x, dy, K, stride=stride, in_len=lens, out=dw, accumulate=True, use_workspace=use_workspace)
+      return dw
+    a, b = _twice(run)
+    assert _bits_equal(a, b), (B, T, Cin, Cout, K, stride)
+    atomic = run(use_workspace=False)
+    capi.set_deterministic(True)
+    single = run()
+    capi.set_deterministic(False)
+    torch.cuda.synchronize()
+    torch.testing.assert_close(a, single, rtol=2e-4, atol=2e-3)
+    torch.testing.assert_close(a, atomic, rtol=2e-4, atol=2e-3)
+
+
 def test_depthwise_weight_gradients_bit_identical(det, cuda):
   capi = det
   g = torch.Generator().manual_seed(1)

@@ -59,7 +59,7 @@ def test_bench_gpus_2_end_to_end_on_one_device(cuda):
   for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "OS2S_BUCKET_MB", "OS2S_ALLREDUCE_DTYPE"):
     env.pop(k, None)
   r = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--gpus", "2", "--one-device", "--backend", "gloo",
-                      "--steps", "3", "--warmup", "2", "--batch", "8", "--transformer-batch", "32",
+                      "--full", "--steps", "3", "--warmup", "2", "--batch", "8", "--transformer-batch", "32",
                       "--no-cpu-baseline", "--bucket-mb", "64", "--allreduce-dtype", "bf16"],
                      stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, env=env, timeout=1800)
   assert r.returncode == 0, r.stderr[-4000:]

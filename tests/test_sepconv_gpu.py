@@ -81,7 +81,9 @@ def _check_depthwise(cuda, K, stride, dil, shape):
     dx = capi.depthwise_conv1d_fwd(dy.to(cuda), w.to(cuda), dil=dil, pad_left=(K - 1) * dil - pl, tout=T,
                                    out_len=lens.to(cuda), flip=True).float().cpu()
     m = (torch.arange(T)[None, :, None] < lens[:, None, None])
-    torch.testing.assert_close(dx * m, xr.grad * m, atol=5e-2, rtol=2e-2)
+    # rows at or past out_len are never stored (os2s.h: the consumer masks them): select the valid rows, do not
+    # multiply the unwritten ones (whatever the allocator left there, NaN included) by zero
+    torch.testing.assert_close(torch.where(m, dx, 0.0), xr.grad * m, atol=5e-2, rtol=2e-2)
 
 
 def test_quartznet_small_fwd_bwd(cuda):
@@ -258,7 +260,9 @@ def test_one_tap_separable_layer_math(cuda):
 
   def rel(a, b):
     return float((a.double() - b).norm() / b.norm())
-  errs = dict(y=rel(y * m, y_ref * m), dx=rel(dx * m, dx_ref * m), dw=rel(dw.cpu()[0], dw_ref), dd=rel(dd.cpu()[0], dd_ref))
+  # dx rows at or past out_len are never stored (os2s.h): selected away, not multiplied by zero (they may hold NaN)
+  errs = dict(y=rel(y * m, y_ref * m), dx=rel(torch.where(m > 0, dx, 0.0), dx_ref * m), dw=rel(dw.cpu()[0], dw_ref),
+              dd=rel(dd.cpu()[0], dd_ref))
   print("one-tap separable layer, folded form vs fp64:", {k: "%.2e" % v for k, v in errs.items()})
   # bf16 storage of W diag(d) (2^-9 per element, rms 2^-10.3) and of y / dx; dw and dd carry no rounding of their own
   assert errs["y"] <= 4e-3 and errs["dx"] <= 4e-3 and errs["dw"] <= 1e-4 and errs["dd"] <= 1e-4, errs

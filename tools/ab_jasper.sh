@@ -3,7 +3,7 @@
 VAR=$1; A=$2; B=$3; STEPS=${4:-12}
 for rep in 1 2; do
   for v in "$A" "$B"; do
-    env $VAR=$v python bench.py --no-other-configs --no-transformer --no-cpu-baseline --steps $STEPS --warmup 4 \
+    env $VAR=$v python bench.py --full --no-other-configs --no-transformer --no-cpu-baseline --steps $STEPS --warmup 4 \
       2>/dev/null | python -c "
 import json,sys
 d=json.loads([l for l in sys.stdin if l.startswith('{')][-1])

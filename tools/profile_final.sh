@@ -1,6 +1,6 @@
 #!/bin/bash
 # Final-tree evidence of a round in ONE short GPU call (tools/profile_round.sh is the long form with the PMC passes):
-#   <tag>_bench_final.json(.err)             python bench.py — the driver's command
+#   <tag>_bench_final.json(.err)             python bench.py --full (the line with every block)
 #   <tag>_jasper_kernel_stats_final.csv      rocprofv3 --kernel-trace --stats of the Jasper step, bench streams
 #   <tag>_jasper_kernel_stats_serial_final.csv   the same with OS2S_WGRAD_STREAM=0 (every kernel alone on the GPU)
 #   <tag>_transformer_kernel_stats_serial_final.csv
@@ -9,7 +9,7 @@ TAG=${1:-rXX}
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 OUT=gpurun_out/final_$TAG
 mkdir -p $OUT
-python bench.py > $OUT/${TAG}_bench_final.json 2> $OUT/${TAG}_bench_final.err
+python bench.py --full > $OUT/${TAG}_bench_final.json 2> $OUT/${TAG}_bench_final.err
 J="python bench.py --no-transformer --no-other-configs --no-cpu-baseline --no-kernel-timing"
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/ks -o jasper -- $J --steps 8 --warmup 3 > $OUT/ks.log 2>&1
 cp $OUT/ks/jasper_kernel_stats.csv $OUT/${TAG}_jasper_kernel_stats_final.csv

@@ -1,6 +1,6 @@
 #!/bin/bash
 # One call that produces every profile committed under profiles/ for a round:
-#   <tag>_bench_default.json(.err)        python bench.py (the driver's command)
+#   <tag>_bench_default.json(.err)        python bench.py --full (the line with every block)
 #   <tag>_jasper_kernel_stats.csv         rocprofv3 --kernel-trace --stats of the Jasper step (bench streams)
 #   <tag>_jasper_kernel_stats_serial.csv  the same with the weight-gradient stream folded into the main
 #                                         stream (OS2S_WGRAD_STREAM=0): every kernel alone on the GPU
@@ -164,6 +164,6 @@ cp $OUT/${TAG}_pmc_transformer_traffic.json $OUT/${TAG}_pmc_frontend_traffic.jso
 # ---- the driver's command, AFTER every PMC pass: bench.py reads roofline.traffic from the newest
 #      profiles/*_pmc_bench_traffic.json, which must be the one committed next to its line ----
 cp $OUT/${TAG}_pmc_bench_traffic.json profiles/${TAG}_pmc_bench_traffic.json
-timeout 900 python bench.py > $OUT/${TAG}_bench_default.json 2> $OUT/${TAG}_bench_default.err
+timeout 900 python bench.py --full > $OUT/${TAG}_bench_default.json 2> $OUT/${TAG}_bench_default.err
 tail -c 600 $OUT/${TAG}_bench_default.json; echo
 ls -la $OUT/*.json $OUT/*.csv $OUT/*.txt
