@@ -19,12 +19,6 @@ import numpy as np
 
 from . import _lib
 
-_c_pp = ctypes.POINTER(ctypes.c_char_p)
-
-
-def _fn(name, argtypes, restype=ctypes.c_int):
-  return _lib.bind(name, list(argtypes), restype)
-
 
 class Scorer(object):
   """External scorer: n-gram language model + word insertion bonus + dictionary.
@@ -32,14 +26,13 @@ class Scorer(object):
 
   def __init__(self, alpha, beta, model_path, vocabulary):
     self._h = ctypes.c_void_p(0)
-    self._destroy = _fn("os2s_ctc_dict_scorer_destroy", (ctypes.c_void_p,), None)
+    self._destroy = _lib.C.os2s_ctc_dict_scorer_destroy
     self.alpha, self.beta = float(alpha), float(beta)
     self.vocabulary = list(vocabulary)
     arr = (ctypes.c_char_p * len(self.vocabulary))(*[v.encode("utf-8") for v in self.vocabulary])
-    f = _fn("os2s_ctc_dict_scorer_create", (ctypes.c_char_p, _c_pp, ctypes.c_int, ctypes.c_double,
-                                            ctypes.c_double, ctypes.POINTER(ctypes.c_void_p)))
-    _lib.check(f(str(model_path).encode(), arr, len(self.vocabulary), self.alpha, self.beta,
-                 ctypes.byref(self._h)), "os2s_ctc_dict_scorer_create(%s)" % model_path)
+    _lib.check(_lib.C.os2s_ctc_dict_scorer_create(str(model_path).encode(), arr, len(self.vocabulary), self.alpha,
+                                                  self.beta, ctypes.byref(self._h)),
+               "os2s_ctc_dict_scorer_create(%s)" % model_path)
 
   @property
   def handle(self):
@@ -47,13 +40,13 @@ class Scorer(object):
 
   def reset_params(self, alpha, beta):
     self.alpha, self.beta = float(alpha), float(beta)
-    _lib.check(_fn("os2s_ctc_dict_scorer_set_weights", (ctypes.c_void_p, ctypes.c_double, ctypes.c_double))(
-        self._h, self.alpha, self.beta), "os2s_ctc_dict_scorer_set_weights")
+    _lib.check(_lib.C.os2s_ctc_dict_scorer_set_weights(self._h, self.alpha, self.beta),
+               "os2s_ctc_dict_scorer_set_weights")
 
   def _info(self):
     a, b, c = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0)
-    _lib.check(_fn("os2s_ctc_dict_scorer_info", (ctypes.c_void_p,) + (ctypes.POINTER(ctypes.c_int),) * 3)(
-        self._h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)), "os2s_ctc_dict_scorer_info")
+    _lib.check(_lib.C.os2s_ctc_dict_scorer_info(self._h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)),
+               "os2s_ctc_dict_scorer_info")
     return bool(a.value), b.value, c.value
 
   def is_character_based(self):
@@ -91,15 +84,13 @@ def _decode(probs, lens, vocabulary, beam_size, cutoff_prob, cutoff_top_n, score
   ids = np.empty((B, beam_size, T), dtype=np.int32)
   ln = np.empty((B, beam_size), dtype=np.int32)
   sc = np.empty((B, beam_size), dtype=np.float32)
-  f = _fn("os2s_ctc_dict_beam_search",
-          (ctypes.c_void_p, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_void_p) + (ctypes.c_int,) * 4
-          + (ctypes.c_double, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int) + (ctypes.c_void_p,) * 3)
   # fewer than beam_size prefixes can exist (short utterances): ask for what is there
   top = beam_size
   while True:
-    rc = f(probs.ctypes.data, B * C, C, lens.ctypes.data, T, B, C, int(beam_size), float(cutoff_prob),
-           int(cutoff_top_n), int(top), scorer.handle if scorer is not None else None, int(n_threads),
-           ids.ctypes.data, ln.ctypes.data, sc.ctypes.data)
+    rc = _lib.C.os2s_ctc_dict_beam_search(probs.ctypes.data, B * C, C, lens.ctypes.data, T, B, C, int(beam_size),
+                                          float(cutoff_prob), int(cutoff_top_n), int(top),
+                                          scorer.handle if scorer is not None else None, int(n_threads),
+                                          ids.ctypes.data, ln.ctypes.data, sc.ctypes.data)
     if rc == 0 or top == 1:
       break
     top = max(1, top // 2)

@@ -56,7 +56,7 @@ _ENUM_OF = {v: k for k, v in _DTYPES.items()}
 
 def crc32c(data, init=0):
   """CRC-32C of a bytes-like / contiguous ndarray (os2s_crc32c in libos2s_hip.so, host code)."""
-  f = _lib.bind("os2s_crc32c", [ctypes.c_uint32, ctypes.c_void_p, ctypes.c_size_t], ctypes.c_uint32)
+  f = _lib.C.os2s_crc32c
   if isinstance(data, np.ndarray):
     a = np.ascontiguousarray(data)
     return int(f(init, a.ctypes.data_as(ctypes.c_void_p), a.nbytes))

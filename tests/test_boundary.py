@@ -1,16 +1,33 @@
 """CPU tests of the drop-in boundary: the C-ABI library loads and exports every
-symbol include/os2s.h declares; the product package never imports the oracle."""
+symbol include/os2s.h declares, the binder reads every declaration and binds it
+with the header's signature; the product package never imports the oracle."""
 import ctypes
+import glob
 import os
 import re
+
+import pytest
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def _declared_symbols():
+  """The entry points the binder reads from include/os2s.h."""
+  from openseq2seq_amd import _lib
+  return sorted(_lib.declarations())
+
+
+def _python_sources():
+  return glob.glob(os.path.join(REPO, "openseq2seq_amd", "**", "*.py"), recursive=True) + \
+      glob.glob(os.path.join(REPO, "tests", "*.py")) + glob.glob(os.path.join(REPO, "tools", "*.py")) + \
+      [os.path.join(REPO, "bench.py")]
+
+
+def test_binder_parses_every_declaration():
+  """The parser skips no declaration: its names are every os2s_*( identifier of the header's code."""
   txt = open(os.path.join(REPO, "include", "os2s.h")).read()
   txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-  return sorted(set(re.findall(r"\b(os2s_[a-z0-9_]+)\s*\(", txt)))
+  assert _declared_symbols() == sorted(set(re.findall(r"\b(os2s_[a-z0-9_]+)\s*\(", txt)))
 
 
 def test_library_exports_every_declared_symbol():
@@ -22,6 +39,52 @@ def test_library_exports_every_declared_symbol():
   assert not missing, missing
   assert lib.os2s_abi_version() >= 1
   assert _lib.lib().os2s_strerror(-1).decode() == "invalid argument"
+
+
+def test_every_entry_point_binds_with_its_header_signature():
+  """_lib.C holds one private function object per declaration, typed from the header; only the launches (int
+  result, an os2s_stream_t argument) check their status themselves."""
+  from openseq2seq_amd import _lib
+  lib = _lib.lib()
+  decls = _lib.declarations()
+  for name, (restype, argtypes, is_launch) in decls.items():
+    f = getattr(_lib.C, name)
+    assert f is not getattr(lib, name), name
+    assert f.restype is restype and tuple(f.argtypes) == argtypes, name
+    assert (f.errcheck is not None) == is_launch, name
+  assert _lib.C.os2s_ctc_scorer_create.argtypes[:3] == (ctypes.c_char_p,) * 3
+  assert _lib.C.os2s_conv1d_fwd_ws.argtypes[17] is ctypes.c_longlong          # y_stride_b
+  with pytest.raises(ctypes.ArgumentError):
+    _lib.C.os2s_set_option("str, not bytes", 1.0)
+  with pytest.raises(_lib.Os2sError, match=r"^os2s_bn_stats failed: invalid argument( \[.*\])? \(code -1\)$"):
+    _lib.C.os2s_bn_stats(None, None, 0, 0, None)
+
+
+def test_status_rule_matches_the_header():
+  """The header documents the OS2S_OK / OS2S_ERR_* return of its entry points, describes none of the launches as
+  returning anything else, and the package wraps in _lib.check only calls that do not check themselves."""
+  from openseq2seq_amd import _lib
+  header = open(os.path.join(REPO, "include", "os2s.h")).read()
+  assert "returns OS2S_OK (0) or a negative OS2S_ERR_* code" in header
+  decls = _lib.declarations()
+  launches = set(n for n, d in decls.items() if d[2])
+  assert len(launches) >= 90
+  valued = set(re.findall(r"\b(os2s_[a-z0-9_]+)(?:\(\w*\))? returns\b", header))
+  assert valued and not (valued & launches), sorted(valued & launches)
+  checked = set()
+  for f in glob.glob(os.path.join(REPO, "openseq2seq_amd", "**", "*.py"), recursive=True):
+    checked |= set(re.findall(r"_lib\.check\(_lib\.C\.(os2s_[a-z0-9_]+)\(", open(f).read()))
+  assert checked and not (checked & launches), sorted(checked & launches)
+
+
+def test_python_code_calls_only_declared_entry_points():
+  """Every entry point the package, the tests, the tools and bench.py call through _lib.C is declared in the
+  header: read from the source, not found by a call."""
+  used = set()
+  for f in _python_sources():
+    used |= set(re.findall(r"\bC\.(os2s_[a-z0-9_]+)", open(f).read()))
+  assert len(used) >= 100
+  assert not (used - set(_declared_symbols())), sorted(used - set(_declared_symbols()))
 
 
 def test_no_torch_types_in_header():

@@ -17,8 +17,7 @@ def loop(fn, n=3000):
   t2 = time.perf_counter()
   return (t1 - t0) / n * 1e6, (t2 - t0) / n * 1e6
 print("bn_finalize via capi: host %.2f us/call, wall %.2f us/call" % loop(lambda: capi.bn_finalize(partial, 224 * 128, gamma, beta, 1e-3, 0.9, True, mm, mv, mean, rstd, sc, sh)))
-from ctypes import c_void_p, c_int, c_float, c_longlong as c_ll
-f = capi._fn("os2s_bn_finalize", None)
+f = _lib.C.os2s_bn_finalize
 st = capi._stream()
 args = (st, partial.data_ptr(), 224, C, 224 * 128, gamma.data_ptr(), beta.data_ptr(), 1e-3, 0.9, 1, mm.data_ptr(), mv.data_ptr(), mean.data_ptr(), rstd.data_ptr(), sc.data_ptr(), sh.data_ptr())
 print("bn_finalize prebuilt ctypes args: host %.2f us/call, wall %.2f" % loop(lambda: f(*args)))

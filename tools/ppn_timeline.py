@@ -8,7 +8,6 @@ import torch
 from openseq2seq_amd import capi, _lib
 dev = torch.device("cuda:0")
 L = _lib.lib()
-L.os2s_set_option.argtypes = [_lib.ctypes.c_char_p, _lib.ctypes.c_double]
 B, T, NS = 32, 840, 24
 # mode: 0 normal, 2 no DMA issue in the loop, 4 no fragment reads in the loop, 6 neither (barriers + MFMAs only)
 for cin, cout, K, v, prio, mode in [(384, 384, 13, 12, 0, 0), (384, 384, 13, 12, 1, 0), (384, 384, 13, 12, 0, 2),
