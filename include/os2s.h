@@ -611,6 +611,35 @@ int os2s_layernorm_bwd(os2s_stream_t stream, const uint16_t* dy, const uint16_t*
                        const float* gamma, const float* mean, const float* rstd,
                        const uint16_t* dres, long long N, int D, uint16_t* dx,
                        float* partial);
+/* LayerNormalization "layernorm_L1" (parts/transformer/common.py:69-80), D in {512, 1024}:
+ * y = c / (mean|c| + eps) * gamma + beta with c = x - mean(x); saves mean and rinv = 1 / (mean|c| + eps) per row */
+int os2s_layernorm_l1_fwd(os2s_stream_t stream, const uint16_t* x, const float* gamma,
+                          const float* beta, float eps, long long N, int D, uint16_t* y,
+                          float* mean, float* rinv);
+int os2s_layernorm_l1_bwd_num_parts(long long N);
+/* dx = dres + L1'(dy) (d|c|/dc = sign(c), 0 at 0); partial [num_parts,2,D] = {sum dy, sum dy*c*rinv}:
+ * reduce with os2s_bn_bwd_finalize(partial, nparts, 2, 1, D, ...) -> dbeta, dgamma */
+int os2s_layernorm_l1_bwd(os2s_stream_t stream, const uint16_t* dy, const uint16_t* x,
+                          const float* gamma, const float* mean, const float* rinv,
+                          const uint16_t* dres, long long N, int D, uint16_t* dx,
+                          float* partial);
+/* Transformer_BatchNorm (parts/transformer/common.py:11-38) over the N tokens of a packed [N, D] batch.
+ * Statistics: os2s_bn_stats + os2s_bn_finalize(count = N; training = 0: moving statistics).
+ * apply: y = x * scale + shift (the finalize's per-column vectors) */
+int os2s_token_bn_apply(os2s_stream_t stream, const uint16_t* x, const float* scale,
+                        const float* shift, long long N, int D, uint16_t* y);
+/* backward pass 1: partial [num_parts,2,D] = {sum dy, sum dy*xhat}, D / 8 a divisor of 256;
+ * reduce with os2s_bn_bwd_finalize(partial, nparts, 2, 1, D, N, ...) -> dgamma, dbeta, c1, c2 */
+int os2s_token_bn_bwd_num_parts(long long N);
+int os2s_token_bn_bwd_reduce(os2s_stream_t stream, const uint16_t* dy, const uint16_t* x,
+                             const float* mean, const float* rstd, long long N, int D,
+                             float* partial);
+/* backward pass 2: dx = gamma*rstd*(dy - c1 - xhat*c2) + dres; gamma NULL = 1 (center_scale off),
+ * dres NULL = 0 */
+int os2s_token_bn_bwd_apply(os2s_stream_t stream, const uint16_t* dy, const uint16_t* x,
+                            const float* gamma, const float* mean, const float* rstd,
+                            const float* c1, const float* c2, const uint16_t* dres,
+                            long long N, int D, uint16_t* dx);
 /* mode 0: d = dout * keepmask/keep (hash mask, PrePostProcessingWrapper dropout);
  * mode 1: d = dout * (out > 0)/keep (Dense+ReLU+dropout of FeedFowardNetwork) */
 int os2s_dropout_bwd(os2s_stream_t stream, const uint16_t* dout, const uint16_t* out,

@@ -1063,6 +1063,61 @@ def layernorm_bwd(dy, x, gamma, mean, rstd, dres, dgamma, dbeta, defer_param_gra
   return dx
 
 
+def layernorm_l1_fwd(x, gamma, beta, eps=1e-6, save=True):
+  """'layernorm_L1': returns (y, mean, rinv) — rinv = 1 / (mean|x - mean| + eps) per row."""
+  N, D = x.shape
+  y = torch.empty_like(x)
+  mean = torch.empty(N, dtype=torch.float32, device=x.device) if save else None
+  rinv = torch.empty(N, dtype=torch.float32, device=x.device) if save else None
+  _lib.C.os2s_layernorm_l1_fwd(_stream(), _ptr(x, torch.bfloat16), _ptr(gamma, torch.float32),
+                               _ptr(beta, torch.float32), float(eps), N, D, _ptr(y),
+                               _ptr(mean, None, True), _ptr(rinv, None, True))
+  return y, mean, rinv
+
+
+def layernorm_l1_bwd(dy, x, gamma, mean, rinv, dres):
+  """Returns (dx, partial): dx = dres + L1'(dy); partial [nparts, 2, D] = {sum dy, sum dy*xhat} for
+  bn_bwd_finalize(partial, 1, ...) -> dgamma, dbeta (the caller picks the stream)."""
+  N, D = x.shape
+  dx = torch.empty_like(x)
+  nparts = int(_lib.C.os2s_layernorm_l1_bwd_num_parts(N))
+  partial = torch.empty((nparts, 2, D), dtype=torch.float32, device=x.device)
+  _lib.C.os2s_layernorm_l1_bwd(_stream(), _ptr(dy, torch.bfloat16), _ptr(x, torch.bfloat16),
+                               _ptr(gamma, torch.float32), _ptr(mean, torch.float32), _ptr(rinv, torch.float32),
+                               _ptr(dres, torch.bfloat16, True), N, D, _ptr(dx), _ptr(partial))
+  return dx, partial
+
+
+def token_bn_apply(x, scale, shift):
+  """y = x * scale + shift on [N, D] rows (scale / shift fp32 [D], from bn_finalize)."""
+  N, D = x.shape
+  y = torch.empty_like(x)
+  _lib.C.os2s_token_bn_apply(_stream(), _ptr(x, torch.bfloat16), _ptr(scale, torch.float32),
+                             _ptr(shift, torch.float32), N, D, _ptr(y))
+  return y
+
+
+def token_bn_bwd_reduce(dy, x, mean, rstd):
+  """partial [nparts, 2, D] = {sum dy, sum dy*xhat} of a token BatchNorm (reduce with bn_bwd_finalize(q=1))."""
+  N, D = x.shape
+  nparts = int(_lib.C.os2s_token_bn_bwd_num_parts(N))
+  partial = torch.empty((nparts, 2, D), dtype=torch.float32, device=x.device)
+  _lib.C.os2s_token_bn_bwd_reduce(_stream(), _ptr(dy, torch.bfloat16), _ptr(x, torch.bfloat16),
+                                  _ptr(mean, torch.float32), _ptr(rstd, torch.float32), N, D, _ptr(partial))
+  return partial
+
+
+def token_bn_bwd_apply(dy, x, gamma, mean, rstd, c1, c2, dres):
+  """dx = gamma*rstd*(dy - c1 - xhat*c2) + dres (gamma None = 1, dres None = 0)."""
+  N, D = x.shape
+  dx = torch.empty_like(x)
+  _lib.C.os2s_token_bn_bwd_apply(_stream(), _ptr(dy, torch.bfloat16), _ptr(x, torch.bfloat16),
+                                 _ptr(gamma, torch.float32, True), _ptr(mean, torch.float32),
+                                 _ptr(rstd, torch.float32), _ptr(c1, torch.float32), _ptr(c2, torch.float32),
+                                 _ptr(dres, torch.bfloat16, True), N, D, _ptr(dx))
+  return dx
+
+
 def dropout_bwd(dout, keep_prob, seed=0, out=None, capped=False):
   """mode 0 (hash mask) when out is None, mode 1 (relu+dropout via saved output) otherwise; capped: mode 2,
   the saved output is dropout(min(relu(.), 20)) — no gradient at the cap either."""

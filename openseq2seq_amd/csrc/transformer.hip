@@ -13,6 +13,7 @@
 //     its gradient: one read of the [N, V] logits, one write of dlogits.
 #include <cstdlib>
 #include "os2s_common.hpp"
+#include "ln_rows.hpp"
 
 namespace os2s {
 
@@ -182,20 +183,6 @@ __global__ __launch_bounds__(256) void layernorm_fwd_kernel(
 // block's rows, so the prefetch past the last row needs no branch: it is out of range, returns zeros
 // and costs no memory request — and a workgroup has 8 waves.
 constexpr int kLnWaves = 8;
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t ln_rows_rsrc(const void* base, long long r0, int n, int D) {
-  const unsigned long long a = (unsigned long long)base + (unsigned long long)r0 * (unsigned)D * 2ull;
-  const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)a);
-  const unsigned hi = __builtin_amdgcn_readfirstlane((unsigned)(a >> 32));
-  const int bytes = __builtin_amdgcn_readfirstlane(base ? n * D * 2 : 0);   // null tensor: everything is out of range
-  return __builtin_amdgcn_make_buffer_rsrc((void*)(((unsigned long long)hi << 32) | lo), 0, bytes, 0x00020000);
-}
-
-template <int VPL>
-struct LnRow {
-  u32x4 a[VPL], t[VPL], r[VPL];
-  float mu, rs;
-};
 
 template <int VPL>
 __global__ __launch_bounds__(64 * kLnWaves) void layernorm_bwd_kernel(

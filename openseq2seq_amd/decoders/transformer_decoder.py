@@ -1,7 +1,7 @@
 """TransformerDecoder — training/eval pass (decode_pass) of
 open_seq2seq/decoders/transformer_decoder.py:20-230 on the HIP kernels (packed token
 layout): shifted shared embedding + position signal + dropout, N x [causal self-attention,
-encoder-decoder attention, FFN] in pre-norm residual form, final LayerNorm, tied softmax
+encoder-decoder attention, FFN] in pre-norm residual form, final normalisation, tied softmax
 projection; and beam-search prediction (predict, :232-326): an incremental decoder step on one
 new position per beam row (append-only K/V caches + an ancestry table, encoder K/V projected
 once) driven by parts/transformer/beam_search.sequence_beam_search."""
@@ -38,6 +38,7 @@ class TransformerDecoder(Decoder):
   def __init__(self, params, model, name="transformer_decoder", mode='train'):
     super(TransformerDecoder, self).__init__(params, model, name, mode)
     self.params['shared_embed'] = True
+    L.check_norm_params(self.params.get("norm_params"))
     self.layers = []
 
   def build(self, store):
@@ -45,21 +46,24 @@ class TransformerDecoder(Decoder):
     D = p["hidden_size"]
     scope = "ForwardPass/" + self._name
     # the encoder-decoder key / value kernels of all layers, created next to each other (L.FusedCrossKV)
-    kvs = [L.Dense(store, "%s/layer_%d/encdec_attention/attention/kv" % (scope, n), D, 2 * D, False)
+    # norm_params / regularizer as in the encoder (transformer_decoder.py:80-84, 135-143)
+    norm, training = p.get("norm_params"), self.mode == "train"
+    l2 = L.regularizer_l2(p)
+    kvs = [L.Dense(store, "%s/layer_%d/encdec_attention/attention/kv" % (scope, n), D, 2 * D, False, l2=l2)
            for n in range(p["num_hidden_layers"])]
     self.cross_kv = L.FusedCrossKV(store, kvs)
     for n in range(p["num_hidden_layers"]):
       ls = "%s/layer_%d" % (scope, n)
       self.layers.append(dict(
-          ln1=L.LayerNorm(store, ls + "/self_attention/layer_normalization", D),
+          ln1=L.make_norm(store, ls + "/self_attention", D, norm, training),
           self_att=L.MultiHeadAttention(store, ls + "/self_attention/self_attention", D,
-                                        p["num_heads"], True),
-          ln2=L.LayerNorm(store, ls + "/encdec_attention/layer_normalization", D),
+                                        p["num_heads"], True, l2=l2),
+          ln2=L.make_norm(store, ls + "/encdec_attention", D, norm, training),
           cross=L.MultiHeadAttention(store, ls + "/encdec_attention/attention", D,
-                                     p["num_heads"], False, kv=kvs[n]),
-          ln3=L.LayerNorm(store, ls + "/ffn/layer_normalization", D),
-          ffn=L.FeedForward(store, ls + "/ffn/feed_foward_network", D, p["filter_size"])))
-    self.output_normalization = L.LayerNorm(store, scope + "/layer_normalization", D)
+                                     p["num_heads"], False, kv=kvs[n], l2=l2),
+          ln3=L.make_norm(store, ls + "/ffn", D, norm, training),
+          ffn=L.FeedForward(store, ls + "/ffn/feed_foward_network", D, p["filter_size"], l2=l2)))
+    self.output_normalization = L.make_norm(store, scope, D, norm, training)
     return self
 
   def _decode(self, input_dict):
@@ -159,9 +163,11 @@ class TransformerDecoder(Decoder):
     initial_ids = torch.zeros(B, dtype=torch.int32, device=dev)
     cache = {"ancestry": torch.zeros((B, max_decode_length), dtype=torch.int32, device=dev)}
     emb = enc['embedding_softmax_layer']
-    decoded_ids, scores = beam_search.sequence_beam_search(
-        fn, initial_ids, cache, emb.V, beam, p["alpha"], max_decode_length, p["EOS_ID"],
-        device_step_fn=fn.device_step_fn if input_dict.get('use_graph', True) else None)
+    norms = [self.output_normalization] + [l[k] for l in self.layers for k in ("ln1", "ln2", "ln3")]
+    with L.frozen_eval_norms(norms):
+      decoded_ids, scores = beam_search.sequence_beam_search(
+          fn, initial_ids, cache, emb.V, beam, p["alpha"], max_decode_length, p["EOS_ID"],
+          device_step_fn=fn.device_step_fn if input_dict.get('use_graph', True) else None)
     top_decoded_ids = decoded_ids[:, 0, 1:].contiguous()
     # the reference re-runs decode_pass on the decoded ids only to fill "logits", which no
     # consumer of the infer/eval modes reads (models/text2text.py:84-225); ask for it explicitly

@@ -1,7 +1,7 @@
 """TransformerEncoder — open_seq2seq/encoders/transformer_encoder.py:20-170 on the HIP
 kernels (packed token layout). Same param schema; pre-norm residual layers
 (parts/transformer/common.py:99-106), shared embedding + sinusoid position signal +
-dropout, final LayerNorm."""
+dropout, final normalisation (norm_params: layernorm_L2, layernorm_L1 or batch_norm)."""
 from __future__ import absolute_import, division, print_function
 
 from .encoder import Encoder
@@ -27,8 +27,7 @@ class TransformerEncoder(Encoder):
 
   def __init__(self, params, model, name="transformer_encoder", mode='train'):
     super(TransformerEncoder, self).__init__(params, model, name=name, mode=mode)
-    if self.params.get("norm_params", {"type": "layernorm_L2"}).get("type") != "layernorm_L2":
-      raise NotImplementedError("only layernorm_L2 has HIP kernels")
+    L.check_norm_params(self.params.get("norm_params"))
     self.layers = []
     self.embedding_softmax_layer = None
 
@@ -42,15 +41,20 @@ class TransformerEncoder(Encoder):
     self.embedding_softmax_layer = L.SharedEmbedding(
         store, scope + "/embedding_shared_weights", p["src_vocab_size"], D,
         pad_vocab_to_eight=p.get('pad_embeddings_2_eight', False))
+    # norm_params picks layernorm_L2 / layernorm_L1 / batch_norm for every pre-norm and the output norm
+    # (common.py:87-98, transformer_encoder.py:126-134); the encoder's l2 regularizer reaches the attention and
+    # FFN variables (transformer_encoder.py:71-75)
+    norm, training = p.get("norm_params"), self.mode == "train"
+    l2 = L.regularizer_l2(p)
     for n in range(p['encoder_layers']):
       ls = "%s/layer_%d" % (scope, n)
       self.layers.append(dict(
-          ln1=L.LayerNorm(store, ls + "/self_attention/layer_normalization", D),
+          ln1=L.make_norm(store, ls + "/self_attention", D, norm, training),
           att=L.MultiHeadAttention(store, ls + "/self_attention/self_attention", D,
-                                   p["num_heads"], True),
-          ln2=L.LayerNorm(store, ls + "/ffn/layer_normalization", D),
-          ffn=L.FeedForward(store, ls + "/ffn/feed_foward_network", D, p["filter_size"])))
-    self.output_normalization = L.LayerNorm(store, scope + "/layer_normalization", D)
+                                   p["num_heads"], True, l2=l2),
+          ln2=L.make_norm(store, ls + "/ffn", D, norm, training),
+          ffn=L.FeedForward(store, ls + "/ffn/feed_foward_network", D, p["filter_size"], l2=l2)))
+    self.output_normalization = L.make_norm(store, scope, D, norm, training)
     return self
 
   def _encode(self, input_dict):

@@ -92,15 +92,17 @@ class Dense(object):
   """tf.layers.Dense on [N, Cin] rows; kernel stored [1, Cout, Cin] (device layout,
   = the transpose of TF's [Cin, Cout])."""
 
-  def __init__(self, store, name, cin, cout, use_bias):
+  def __init__(self, store, name, cin, cout, use_bias, l2=0.0):
     self.cin, self.cout = cin, cout
 
     def init(shape):   # tf.layers.Dense default initializer: glorot_uniform
       lim = math.sqrt(6.0 / (cin + cout))
       return (torch.rand(shape) * 2 - 1) * lim
 
-    self.kernel = store.add(name + "/kernel", (1, cout, cin), init, kind="conv")
-    self.bias = store.add(name + "/bias", (cout,), torch.zeros(cout), kind="vector") \
+    # l2: the scale of the encoder's / decoder's l2_regularizer, on kernel and bias alike
+    # (attention_layer.py:54-62, ffn_layer.py:36-49)
+    self.kernel = store.add(name + "/kernel", (1, cout, cin), init, kind="conv", l2=l2)
+    self.bias = store.add(name + "/bias", (cout,), torch.zeros(cout), kind="vector", l2=l2) \
         if use_bias else None
 
   @property
@@ -193,7 +195,7 @@ class Dense(object):
 
 
 class LayerNorm(object):
-  """LayerNormalization 'layernorm_L2' (common.py:41-68): fp32 scale/bias, eps 1e-6."""
+  """LayerNormalization 'layernorm_L2' (common.py:41-68): fp32 scale/bias, eps norm_params["epsilon"] (1e-6)."""
 
   def __init__(self, store, name, hidden, eps=1e-6):
     self.scale = store.add(name + "/layer_norm_scale", (hidden,), torch.ones(hidden), kind="vector")
@@ -224,24 +226,169 @@ class LayerNorm(object):
     return out
 
 
+class LayerNormL1(object):
+  """LayerNormalization 'layernorm_L1' (common.py:69-80): y = c / (mean|c| + eps) * scale + bias, c = x - mean(x);
+  the same two variables as layernorm_L2. The reference's fp16 saturate_cast has no counterpart: activations are
+  bf16 here, whose exponent range is fp32's."""
+
+  def __init__(self, store, name, hidden, eps=1e-6):
+    self.scale = store.add(name + "/layer_norm_scale", (hidden,), torch.ones(hidden), kind="vector")
+    self.bias = store.add(name + "/layer_norm_bias", (hidden,), torch.zeros(hidden), kind="vector")
+    self.eps = eps
+
+  def forward(self, x, tape):
+    training = tape is not None
+    y, mean, rinv = capi.layernorm_l1_fwd(x.data, self.scale.master, self.bias.master, self.eps, save=training)
+    out = Act(y)
+    if not training:
+      return out
+    ln = self
+
+    def backward():
+      dy = out.grad
+      assert dy is not None
+      dres, x.res_grad = x.res_grad, None
+      dx, partial = capi.layernorm_l1_bwd(dy, x.data, ln.scale.master, mean, rinv, dres)
+      with on_side_stream(dx.device, partial):      # scale / bias gradients: off the main chain
+        scratch = torch.empty((2, partial.shape[2]), dtype=torch.float32, device=dx.device)
+        capi.bn_bwd_finalize(partial, 1, 1, ln.scale.grad, ln.bias.grad, True, scratch[0], scratch[1])
+      _accumulate_grad(x, dx)
+      out.grad = None
+
+    tape.record(backward, [ln.scale, ln.bias])
+    return out
+
+
+class TokenBatchNorm(object):
+  """Transformer_BatchNorm (common.py:11-38): tf.layers.batch_normalization over the [B, T, 1, D] view of the
+  activations, here over the packed [N, D] tokens. Train mode normalises with the batch statistics of the N real
+  tokens (the reference's also count the padded positions of its [B, T_max] batch — the one deliberate departure,
+  see INTEGRATION.md) and moves moving_mean / moving_variance (TF fused-BN conventions, os2s_bn_finalize);
+  eval / infer apply the moving statistics. center_scale False: no gamma / beta variables (gamma 1, beta 0)."""
+
+  def __init__(self, store, name, hidden, training, momentum=0.95, eps=1e-4, center_scale=True, l2=0.0):
+    self.D, self.training, self.momentum, self.eps = hidden, training, momentum, eps
+    self.gamma = self.beta = None
+    if center_scale:
+      self.gamma = store.add(name + "/gamma", (hidden,), torch.ones(hidden), kind="vector", l2=l2)
+      self.beta = store.add(name + "/beta", (hidden,), torch.zeros(hidden), kind="vector", l2=l2)
+    dev = store.device
+    self.moving_mean = torch.zeros(hidden, dtype=torch.float32, device=dev)
+    self.moving_var = torch.ones(hidden, dtype=torch.float32, device=dev)
+    store.add_state(name + "/moving_mean", self.moving_mean)      # checkpoints, the train -> eval copy
+    store.add_state(name + "/moving_variance", self.moving_var)
+    self.frozen = None
+
+  def eval_affine(self):
+    """[2, D]: scale / shift of the moving statistics (eval / infer)."""
+    vec = torch.empty((2, self.D), dtype=torch.float32, device=self.moving_mean.device)
+    capi.bn_finalize(None, 1, self.gamma.master if self.gamma is not None else None,
+                     self.beta.master if self.beta is not None else None, self.eps, self.momentum, False,
+                     self.moving_mean, self.moving_var, None, None, vec[0], vec[1])
+    return vec
+
+  def forward(self, x, tape):
+    N, D = x.data.shape
+    if not self.training:
+      sc = self.frozen if self.frozen is not None else self.eval_affine()
+      return Act(capi.token_bn_apply(x.data, sc[0], sc[1]))
+    dev = x.data.device
+    gamma = self.gamma.master if self.gamma is not None else None
+    beta = self.beta.master if self.beta is not None else None
+    vec = torch.empty((4, D), dtype=torch.float32, device=dev)      # scale, shift, mean, rstd
+    capi.bn_finalize(capi.bn_stats(x.data), N, gamma, beta, self.eps, self.momentum, True, self.moving_mean,
+                     self.moving_var, vec[2], vec[3], vec[0], vec[1])
+    out = Act(capi.token_bn_apply(x.data, vec[0], vec[1]))
+    if tape is None:
+      return out
+    bn = self
+
+    def backward():
+      dy = out.grad
+      assert dy is not None
+      dres, x.res_grad = x.res_grad, None
+      partial = capi.token_bn_bwd_reduce(dy, x.data, vec[2], vec[3])
+      c = torch.empty((2, D), dtype=torch.float32, device=dev)
+      capi.bn_bwd_finalize(partial, 1, N, bn.gamma.grad if bn.gamma is not None else None,
+                           bn.beta.grad if bn.beta is not None else None, True, c[0], c[1])
+      dx = capi.token_bn_bwd_apply(dy, x.data, gamma, vec[2], vec[3], c[0], c[1], dres)
+      _accumulate_grad(x, dx)
+      out.grad = None
+
+    tape.record(backward, [p for p in (bn.gamma, bn.beta) if p is not None])
+    return out
+
+
+class frozen_eval_norms(object):
+  """Within the block, every eval-mode TokenBatchNorm of `norms` applies ONE scale / shift computed on entry from
+  the moving statistics (which that mode does not change): a decode runs one launch per norm site and step, as
+  LayerNorm does, instead of two. The vectors are dropped on exit, so weights copied in later are seen."""
+
+  def __init__(self, norms):
+    self.bns = [n for n in norms if isinstance(n, TokenBatchNorm) and not n.training]
+
+  def __enter__(self):
+    for n in self.bns:
+      n.frozen = n.eval_affine()
+    return self
+
+  def __exit__(self, *exc):
+    for n in self.bns:
+      n.frozen = None
+    return False
+
+
+NORM_TYPES = ("layernorm_L2", "layernorm_L1", "batch_norm")
+
+
+def regularizer_l2(params):
+  """The scale of an l2_regularizer given as (regularizer, regularizer_params) the way the reference's Transformer
+  reads it (encoders/transformer_encoder.py:71-75, common.py:19-24): 0 without a regularizer or with scale <= 0."""
+  if params.get("regularizer", None) is None:
+    return 0.0
+  scale = float(params.get("regularizer_params", {"scale": 0.0}).get("scale", 0.0))
+  return scale if scale > 0.0 else 0.0
+
+
+def check_norm_params(norm_params):
+  t = (norm_params or {}).get("type", "layernorm_L2")
+  if t not in NORM_TYPES:
+    raise ValueError("norm_params type %r: one of %s" % (t, ", ".join(NORM_TYPES)))
+
+
+def make_norm(store, scope, hidden, norm_params, training):
+  """The normalisation of PrePostProcessingWrapper / output_normalization (common.py:87-98): `scope` is the
+  sublayer's (or the stack's) variable scope. Every kind has forward(x, tape)."""
+  p = norm_params if norm_params is not None else {"type": "layernorm_L2"}
+  check_norm_params(p)
+  t = p.get("type", "layernorm_L2")
+  if t == "batch_norm":
+    cs = bool(p.get("center_scale", True))
+    return TokenBatchNorm(store, scope + "/transformer__batch_norm/batch_normalization", hidden, training,
+                          momentum=float(p.get("momentum", 0.95)), eps=float(p.get("epsilon", 1e-4)),
+                          center_scale=cs, l2=regularizer_l2(p) if cs else 0.0)
+  cls = LayerNormL1 if t == "layernorm_L1" else LayerNorm
+  return cls(store, scope + "/layer_normalization", hidden, eps=float(p.get("epsilon", 1e-6)))
+
+
 class MultiHeadAttention(object):
   """Attention / SelfAttention (attention_layer.py:23-227), 'loung' mode, no biases.
   Self-attention uses one fused [3D, D] projection for q,k,v; enc-dec attention a [D, D]
   query projection and a fused [2D, D] key/value projection. (The reference keeps q, k, v
   as three Dense kernels; fusing only changes how the same numbers are laid out.)"""
 
-  def __init__(self, store, name, hidden, num_heads, self_attention, kv=None):
+  def __init__(self, store, name, hidden, num_heads, self_attention, kv=None, l2=0.0):
     self.D, self.H, self.self_att = hidden, num_heads, self_attention
     self.scale = (hidden // num_heads) ** -0.5
     if hidden // num_heads != 64:
       raise NotImplementedError("HIP attention kernel is built for head dim 64")
     if self_attention:
-      self.qkv = Dense(store, name + "/qkv", hidden, 3 * hidden, False)
+      self.qkv = Dense(store, name + "/qkv", hidden, 3 * hidden, False, l2=l2)
     else:
-      self.q = Dense(store, name + "/q", hidden, hidden, False)
+      self.q = Dense(store, name + "/q", hidden, hidden, False, l2=l2)
       # (the decoder creates the key / value projections of all its layers next to each other — FusedCrossKV)
-      self.kv = kv if kv is not None else Dense(store, name + "/kv", hidden, 2 * hidden, False)
-    self.out = Dense(store, name + "/output_transform", hidden, hidden, False)
+      self.kv = kv if kv is not None else Dense(store, name + "/kv", hidden, 2 * hidden, False, l2=l2)
+    self.out = Dense(store, name + "/output_transform", hidden, hidden, False, l2=l2)
 
   def forward(self, x, y, cu_q, cu_k, max_len, causal, tape, seeds, att_keep, post_keep, residual, kv_pre=None):
     """x: queries source (Act [Nq,D]); y: keys/values source (Act [Nk,D]) — y is x for
@@ -366,9 +513,9 @@ class FusedCrossKV(object):
 class FeedForward(object):
   """FeedFowardNetwork (ffn_layer.py:25-85): Dense(filter, relu) -> dropout -> Dense(hidden)."""
 
-  def __init__(self, store, name, hidden, filter_size):
-    self.filter_layer = Dense(store, name + "/filter_layer", hidden, filter_size, True)
-    self.output_layer = Dense(store, name + "/output_layer", filter_size, hidden, True)
+  def __init__(self, store, name, hidden, filter_size, l2=0.0):
+    self.filter_layer = Dense(store, name + "/filter_layer", hidden, filter_size, True, l2=l2)
+    self.output_layer = Dense(store, name + "/output_layer", filter_size, hidden, True, l2=l2)
 
   def forward(self, x, tape, seeds, relu_keep, post_keep, residual):
     s1, s2 = (seeds.next(), seeds.next()) if seeds is not None else (0, 0)
