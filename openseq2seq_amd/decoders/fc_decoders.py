@@ -10,7 +10,7 @@ import torch
 
 from .decoder import Decoder
 from .. import capi
-from ..parts.cnns.conv_blocks import Act
+from ..parts.tape import Act
 
 
 class FullyConnectedTimeDecoder(Decoder):

@@ -21,7 +21,7 @@ import torch
 from .decoder import Decoder
 from .. import capi
 from ..encoders.rnn_encoders import Embedding, apply_scope_initializer, cell_spec, dropout_act, residual_add
-from ..parts.cnns.conv_blocks import Act
+from ..parts.tape import Act
 from ..parts.rnns.rnn_layers import RNNDirection, rnn_directions_forward
 from ..parts.transformer.layers import SeedSeq, _colsum_into
 

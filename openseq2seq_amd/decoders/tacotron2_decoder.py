@@ -21,8 +21,8 @@ import torch
 from .decoder import Decoder
 from .rnn_decoders import AttentionCell
 from .. import capi
-from ..parts.cnns.conv_blocks import (Act, ConvBN, accumulate_grad, conv_bn_actv, reshape_act,
-                                      xavier_normal_conv)
+from ..parts.cnns.conv_blocks import ConvBN, conv_bn_actv, xavier_normal_conv
+from ..parts.tape import Act, accumulate_grad, reshape_act
 from ..parts.transformer.layers import Dense, SeedSeq
 
 

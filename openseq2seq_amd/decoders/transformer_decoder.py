@@ -11,7 +11,7 @@ import torch
 
 from .decoder import Decoder
 from .. import capi
-from ..parts.cnns.conv_blocks import Act
+from ..parts.tape import Act
 from ..parts.transformer import beam_search
 from ..parts.transformer import layers as L
 from ..parts.transformer import packing

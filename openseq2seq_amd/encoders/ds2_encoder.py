@@ -17,7 +17,8 @@ import torch
 
 from .encoder import Encoder
 from .. import capi
-from ..parts.cnns.conv_blocks import Act, act_id
+from ..parts.activations import act_id
+from ..parts.tape import Act
 from ..parts.rnns.rnn_layers import BiRNNStack
 from ..parts.transformer.layers import Dense, SeedSeq
 

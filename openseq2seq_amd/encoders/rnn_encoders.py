@@ -15,7 +15,7 @@ import torch
 
 from .encoder import Encoder
 from .. import capi
-from ..parts.cnns.conv_blocks import Act
+from ..parts.tape import Act
 from ..parts.rnns.rnn_layers import RNNDirection, rnn_directions_forward
 from ..parts.transformer.layers import SeedSeq
 

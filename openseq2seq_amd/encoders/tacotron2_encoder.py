@@ -11,7 +11,8 @@ import torch
 from .encoder import Encoder
 from .rnn_encoders import Embedding
 from .. import capi
-from ..parts.cnns.conv_blocks import Act, ConvBN, conv_bn_actv, reshape_act, xavier_normal_conv
+from ..parts.cnns.conv_blocks import ConvBN, conv_bn_actv, xavier_normal_conv
+from ..parts.tape import Act, reshape_act
 from ..parts.rnns.rnn_layers import RNNDirection, rnn_directions_forward
 from ..parts.transformer.layers import SeedSeq
 

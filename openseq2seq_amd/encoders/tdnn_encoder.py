@@ -14,9 +14,10 @@ from .encoder import Encoder
 from .. import capi
 import os
 
-from ..parts.cnns.conv_blocks import (Act, ConvBN, ConvOnly, ConvSampleNorm, SepConvBN, conv_actv, conv_bn_res_bn_actv,
+from ..parts.cnns.conv_blocks import (ConvBN, ConvOnly, ConvSampleNorm, SepConvBN, conv_actv, conv_bn_res_bn_actv,
                                       xavier_normal_conv, glorot_uniform_conv, launch_residual_early,
                                       launch_dense_residual, conv_bn_dres_actv)
+from ..parts.tape import Act
 from ..parts.cnns.dense_residual import DenseResidualPlan
 
 # which layer of a residual block starts the block end's residual branches on the side stream

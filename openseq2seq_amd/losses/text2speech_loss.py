@@ -9,7 +9,7 @@ import torch
 
 from .loss import Loss
 from .. import capi
-from ..parts.cnns.conv_blocks import accumulate_grad
+from ..parts.tape import accumulate_grad
 
 
 class Text2SpeechLoss(Loss):

@@ -22,7 +22,8 @@ import torch
 from .. import capi
 from ..optimizers.flat_params import FlatParams
 from ..optimizers.optimizers import optimize_loss
-from ..parts.cnns.conv_blocks import Tape, set_side_stream_enabled
+from ..parts.streams import set_side_stream_enabled
+from ..parts.tape import Tape
 from ..utils import distributed as dist_utils
 from ..utils.utils import check_params
 

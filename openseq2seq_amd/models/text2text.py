@@ -64,10 +64,10 @@ class Text2Text(EncoderDecoderModel):
   def _forward_backward_halves(self, batch):
     """Transformer has no batch statistics: the batch's gradient is the token-weighted sum of its halves' gradients.
     Each half runs forward on its own stream, the two backward passes are issued closure by closure in turn
-    (conv_blocks.backward_interleaved); parameter gradients of both halves queue on ONE side stream."""
+    (tape.backward_interleaved); parameter gradients of both halves queue on ONE side stream."""
     import torch
-    from ..parts.cnns import conv_blocks
-    from ..parts.cnns.conv_blocks import Tape
+    from ..parts import streams
+    from ..parts.tape import Tape, backward_interleaved
     from .. import capi
     halves = self._split_batch(batch)
     main = torch.cuda.current_stream()
@@ -76,7 +76,7 @@ class Text2Text(EncoderDecoderModel):
     n_tot = float(sum(h['n_tgt'] for h in halves))
     scale_dev = self._train_op.loss_scale_view if self._train_op is not None else None
     tapes, losses = [], []
-    conv_blocks._SIDE_KEY_OVERRIDE = capi._stream().value
+    streams.set_side_key_override(capi._stream().value)
     try:
       for k, (h, st) in enumerate(zip(halves, self._half_streams)):
         st.wait_stream(main)
@@ -94,10 +94,10 @@ class Text2Text(EncoderDecoderModel):
         tapes.append(tape)
         losses.append(loss * w)
       torch.cuda.set_stream(main)
-      conv_blocks.backward_interleaved(tapes, self._half_streams)
+      backward_interleaved(tapes, self._half_streams)
     finally:
       torch.cuda.set_stream(main)
-      conv_blocks._SIDE_KEY_OVERRIDE = None
+      streams.set_side_key_override(None)
     return losses[0] + losses[1]
 
   def infer_batch(self, batch):

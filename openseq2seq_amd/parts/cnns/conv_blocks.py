@@ -1,10 +1,10 @@
 """conv_bn_actv / conv_bn_res_bn_actv — the conv blocks of
 open_seq2seq/parts/cnns/conv_blocks.py:61-232, re-hosted on the HIP kernels.
 
-There is no graph compiler here: a layer object owns its parameters, `forward`
-enqueues the kernels and records one backward closure on a Tape; `Tape.backward`
-replays them in reverse. Activations are bf16 [B,T,C] channels-last (the
-reference's data_format="channels_last"), always stored ALREADY multiplied by
+A layer object owns its parameters, `forward` enqueues the kernels and records one backward closure on a Tape. The
+engine itself lives outside this module: Tape / Act / accumulate_grad / reshape_act in parts/tape.py, the side
+streams in parts/streams.py, the activation ids in parts/activations.py. Activations are bf16 [B,T,C] channels-last
+(the reference's data_format="channels_last"), always stored ALREADY multiplied by
 the sequence mask of their length vector — the reference multiplies the mask
 onto every conv input (tdnn_encoder.py:185-186,204-205), we fold that multiply
 into the producer's store.
@@ -15,52 +15,11 @@ import os
 import torch
 
 from ... import capi
-
-ACT_IDS = {None: 0, "none": 0, "relu": 1, "tanh": 2, "relu20": 3}
-
-
-class _Probe(object):
-  """Stand-in argument for probing a config's activation lambda under the tensorflow token module
-  (compat/tensorflow_shim.py): its functions return tokens that record their arguments."""
-  __name__ = "x"
-
-
-def _probe_activation(fn):
-  """`lambda x: tf.minimum(tf.nn.relu(x), 20.0)` — the clipped ReLU of the reference's DeepSpeech2 /
-  Wave2Letter configs (ds2_toy_config.py:79, test_speech_configs/*.py) — is recognised by calling it on a
-  probe: the token module returns minimum(relu(x), 20.0) as a tree of tokens. Returns an id or None."""
-  try:
-    r = fn(_Probe())
-  except Exception:
-    return None
-  if getattr(r, "__name__", "") != "minimum" or len(getattr(r, "args", ())) != 2:
-    return None
-  a, b = r.args
-  if isinstance(a, (int, float)):
-    a, b = b, a
-  inner = getattr(a, "__name__", "")
-  if inner == "relu" and isinstance(b, (int, float)) and float(b) == 20.0 and \
-     len(getattr(a, "args", ())) == 1 and isinstance(a.args[0], _Probe):
-    return ACT_IDS["relu20"]
-  return None
-
-
-def act_id(fn):
-  """Maps config tokens (tf.nn.relu, tf.nn.tanh, None, names, the clipped-ReLU lambda) to kernel ids."""
-  if fn is None:
-    return 0
-  name = fn if isinstance(fn, str) else getattr(fn, "__name__", str(fn))
-  name = name.lower()
-  if name not in ACT_IDS and callable(fn):
-    pid = _probe_activation(fn)
-    if pid is not None:
-      return pid
-  if name not in ACT_IDS:
-    raise NotImplementedError("activation %r" % (fn,))
-  return ACT_IDS[name]
-
-
-_SIDE_STREAMS = {}
+from .. import streams, tape as _tape      # (`tape` is the Tape argument of every block function here)
+# compatibility: names that tests, tools and bench.py reach through this module (the same objects, not copies)
+from ..activations import act_id  # noqa: F401
+from ..streams import join_side_streams, on_side_stream, set_side_stream_enabled, side_streams  # noqa: F401
+from ..tape import Act, Tape, accumulate_grad, backward_interleaved, current_tape, reshape_act  # noqa: F401
 
 
 # A/B knob: 0 = every conv + BatchNorm + ReLU layer runs its own BatchNorm-backward reduction pass
@@ -73,22 +32,11 @@ GROUP_WGRAD = os.environ.get("OS2S_GROUP_WGRAD", "1") != "0"
 # TN-GEMM kernel (0 = one lockstep launch each, round 1 - 4)
 GROUP_POINTWISE_WGRAD = os.environ.get("OS2S_GROUP_POINTWISE_WGRAD", "1") != "0"
 POINTWISE_WGRAD_GROUP = int(os.environ.get("OS2S_POINTWISE_WGRAD_GROUP", "5"))
-# how many small Dense weight gradients (Transformer: the 1024 x 1024 projections, 16 tiles each) share one launch
-SMALL_WGRAD_GROUP = int(os.environ.get("OS2S_SMALL_WGRAD_GROUP", "3"))
-# Round 6: convolution weight gradients of same-shape layers CAN be collected until they cover this many units of the
-# ping-pong kernel (128 co x 128 ci x 4 taps each; 256 CUs) and go out as one launch (Tape.defer_conv_wgrad,
-# os2s_conv1d_wgrad_grouped_ws). Alone on the GPU the grouped launches save the reduction splits of the 256 - 640
-# channel layers; in the Jasper step — where the weight gradients run next to the data-gradient chain — holding them
-# back costs what it saves: 37.15 / 37.31 ms without, 37.1 - 37.3 at 64 - 128 units, 37.4 - 38.0 at 160 - 192
-# (same box, interleaved). 0 (default) = every layer alone, as in rounds 2 - 5.
-CONV_WGRAD_UNIT_BUDGET = int(os.environ.get("OS2S_CONV_WGRAD_UNIT_BUDGET", "0"))
 # A/B knob: 0 = the grouped K = 1 weight gradients stay on the lockstep kernel with its atomics (round 2 - 4)
 GROUP_WGRAD_PP = os.environ.get("OS2S_GROUP_WGRAD_PP", "1") != "0"
 # A/B knob: the forward half of the dense-residual algebra (parts/cnns/dense_residual.py: source copy, Gram matrix,
 # block end's residual GEMM) runs on the side stream next to the block's own layers (1) or in front of them (0)
 DRES_FWD_SIDE = os.environ.get("OS2S_DRES_FWD_SIDE", "1") != "0"
-# A/B knob: 0 = the dense-residual chains share the weight-gradient side stream (FIFO behind its backlog)
-DRES_OWN_STREAM = os.environ.get("OS2S_DRES_OWN_STREAM", "1") != "0"
 WGRAD_STREAMS = int(os.environ.get("OS2S_WGRAD_STREAMS", "1"))
 _WGRAD_RR = 0
 # A/B knob: 0 = block ends on the dense-residual algebra keep their own BatchNorm-backward reduction pass
@@ -99,363 +47,6 @@ SEP_FUSE_BN_BWD = os.environ.get("OS2S_SEP_FUSE_BN_BWD", "1") != "0"
 # A/B knob: 0 = a one-tap separable layer (QuartzNet's residual branches) runs its depthwise scale as a launch of
 # its own (rounds 4 - 6); default = one 1x1 convolution with the scale folded into the kernel (SepConvBN.folded)
 FOLD_SEP_K1 = os.environ.get("OS2S_FOLD_SEP_K1", "1") != "0"
-
-
-_SIDE_STREAM_ENABLED = True
-# set while two half-batches of ONE step run on two main streams (backward_interleaved): both share the side streams
-# of the step's own stream — parameter gradients accumulate into the same buffers, one FIFO keeps them in order
-_SIDE_KEY_OVERRIDE = None
-
-
-def set_side_stream_enabled(on):
-  """Per-model switch (config key `os2s_side_stream`, set at the start of every train step): with False
-  every `on_side_stream` body runs on the current stream. Returns the previous setting (the caller
-  restores it when its step is over)."""
-  global _SIDE_STREAM_ENABLED
-  prev, _SIDE_STREAM_ENABLED = _SIDE_STREAM_ENABLED, bool(on)
-  return prev
-
-
-def _side_stream(device, which=0):
-  """Side stream for work that may overlap the main stream inside one backward closure
-  (OS2S_WGRAD_STREAM=0 or the model's `os2s_side_stream: False` keeps everything on one stream).
-  which: 0 = the parameter-gradient stream (nothing on the main stream waits for it before the end of the pass),
-  1 = the stream of side work the main stream DOES wait for (the dense-residual chains): a stream is a FIFO, a
-  chain queued behind a backlog of weight-gradient kernels would stall the main stream until the backlog drained."""
-  if not _SIDE_STREAM_ENABLED or os.environ.get("OS2S_WGRAD_STREAM", "1") == "0" or device.type != "cuda":
-    return None
-  if which == 1 and not DRES_OWN_STREAM:
-    which = 0
-  base = _SIDE_KEY_OVERRIDE if _SIDE_KEY_OVERRIDE is not None else capi._stream().value
-  key = (device.index, base) if not which else (device.index, base, which)
-  st = _SIDE_STREAMS.get(key)
-  if st is None:
-    # OS2S_SIDE_PRIO (experiment): stream priority of the side stream (HIP: lower number = higher
-    # priority; the main stream has 0)
-    prio = int(os.environ.get("OS2S_DRES_PRIO" if which else "OS2S_SIDE_PRIO", "0"))
-    st = _SIDE_STREAMS[key] = torch.cuda.Stream(device=device, priority=prio)
-  return st
-
-
-_STREAM_OBJ = {}       # raw stream handle -> torch.cuda.Stream (torch.cuda.current_stream() builds a new object: 7 us)
-_FORK_EVENT = {}       # side stream -> the event its forks are ordered by (re-recorded per use: a wait captures the
-                       # record that precedes it)
-
-
-def _current_stream_obj():
-  raw = capi._stream().value
-  st = _STREAM_OBJ.get(raw)
-  if st is None:
-    st = _STREAM_OBJ[raw] = torch.cuda.current_stream()
-  return st
-
-
-class on_side_stream(object):
-  """`with on_side_stream(device, *operands):` enqueues the body on the side stream, ordered
-  after everything the current stream has enqueued so far. For parameter-gradient kernels:
-  nothing in the rest of backward reads their result, the main stream re-joins at the end of
-  `Tape.backward` and the gradient reducer waits for the side stream itself. `operands` are the
-  tensors the body reads that the main stream's closures release afterwards (their memory is kept
-  until the side stream is done). With OS2S_WGRAD_STREAM=0 the body runs on the current stream.
-  (Host cost matters here — QuartzNet's step is bound by the Python thread, and this context is entered ~250 times
-  per step: cached stream objects, one re-recorded event per side stream and torch.cuda.set_stream instead of
-  current_stream() / wait_stream() / the torch.cuda.stream context manager: ~35 -> ~10 us per use.)"""
-
-  def __init__(self, device, *operands, which=0):
-    self.side = _side_stream(device, which)
-    self.operands = operands
-    self.main = None
-
-  def __enter__(self):
-    if self.side is not None:
-      self.main = _current_stream_obj()
-      ev = _FORK_EVENT.get(self.side)
-      if ev is None:
-        ev = _FORK_EVENT[self.side] = torch.cuda.Event()
-      ev.record(self.main)
-      self.side.wait_event(ev)
-      torch.cuda.set_stream(self.side)
-    return self
-
-  def __exit__(self, *exc):
-    if self.side is not None:
-      torch.cuda.set_stream(self.main)
-      for t in self.operands:
-        if t is not None:
-          t.record_stream(self.side)
-    return False
-
-  def hand_over(self, *tensors):
-    """Tensors ALLOCATED inside the body (side-stream allocations) that the main stream consumes
-    after it has joined: their memory must not be recycled for later side-stream allocations while
-    main-stream kernels still use them."""
-    if self.side is not None:
-      for t in tensors:
-        if t is not None:
-          t.record_stream(self.main)
-
-
-def side_streams():
-  return list(_SIDE_STREAMS.values())
-
-
-_JOIN_EVENT = {}
-
-
-def join_side_streams():
-  """The current stream waits for everything enqueued on the side streams so far."""
-  if _SIDE_STREAMS:
-    cur = _current_stream_obj()
-    for st in _SIDE_STREAMS.values():
-      ev = _JOIN_EVENT.get(st)
-      if ev is None:
-        ev = _JOIN_EVENT[st] = torch.cuda.Event()
-      ev.record(st)
-      cur.wait_event(ev)
-
-
-class Tape(object):
-  """Reverse-mode tape. `record(fn, params)` also notes which parameters the closure writes
-  gradients of. A parameter is FINAL once every closure that lists it has run; after each
-  closure `on_done(w)` tells the data-parallel reducer the watermark w: every parameter at a flat
-  offset >= w is final (parameters no closure lists receive no gradient), so complete gradient
-  buckets above it can be all-reduced while the rest of backward runs. Variables are created in
-  forward order, so the watermark normally falls with every closure; a variable used out of
-  creation order (a tied embedding, say) only delays it."""
-
-  def __init__(self, on_done=None):
-    self.ops = []
-    self.on_done = on_done
-    # True: backward() leaves the closures (and the activations they hold) to the caller, who drops them AFTER it has
-    # enqueued what follows the pass — releasing a step's few thousand tensors takes the host ~0.5 ms, during which
-    # the GPU (which has caught up with the host by the end of backward) would wait for the optimizer launch
-    self.defer_free = False
-
-  def record(self, fn, params=()):
-    self.ops.append((fn, params))
-
-  def backward(self):
-    # Re-entrant: a closure may run another tape's backward pass (a nested pass gets the zeroed scratch arena
-    # of its own depth — capi.zero_arena_enter — and its own deferred-gradient list; `current_tape()` is the
-    # innermost pass). Work parked on the side streams since the last join must have landed first.
-    depth = len(_TAPE_STACK)
-    join_side_streams()
-    capi.zero_arena_enter(depth)   # the previous pass's statistic partials at this depth are dead: one fill
-    _TAPE_STACK.append(self)
-    self._deferred, self._pending = [], None
-    self._cdeferred, self._ckey = [], None
-    try:
-      if self.on_done is None:
-        for fn, _ in reversed(self.ops):
-          fn()
-        self.flush_deferred()
-        self.flush_conv_wgrads()
-      else:
-        pending, by_id = {}, {}
-        for _, params in self.ops:
-          for p in params:
-            pending[id(p)] = pending.get(id(p), 0) + 1
-            by_id[id(p)] = p
-        self._pending = pending
-        order = sorted(by_id.values(), key=lambda p: -p.offset)
-        ptr = 0
-
-        def advance():
-          nonlocal ptr
-          moved = False
-          while ptr < len(order) and pending[id(order[ptr])] == 0:
-            ptr += 1
-            moved = True
-          if moved:
-            self.on_done(order[ptr - 1].offset)
-
-        for fn, params in reversed(self.ops):
-          fn()
-          if params:
-            for p in params:
-              pending[id(p)] -= 1
-            advance()
-        if self._deferred or self._cdeferred:
-          self.flush_deferred()
-          self.flush_conv_wgrads()
-          advance()
-    finally:
-      _TAPE_STACK.pop()
-      capi.zero_arena_leave(depth)
-    if not self.defer_free:
-      self.ops = []
-    join_side_streams()
-
-  # ---- deferred (grouped) weight gradients -----------------------------------------------------
-  def defer_wgrad(self, param, item, group=None, unit_budget=None, side=True):
-    """A Dense weight gradient too small to fill the chip alone is held back until `group` of them — or, with
-    `unit_budget`, enough of them to cover that many 256 x 256 output tiles — can go out in one launch
-    (capi.gemm_wgrad_grouped: at most 16 per launch). Until then `param` does not count as final for the
-    gradient reducer. Optional keys of `item`: `after` — a callable run behind the grouped launch, on its stream (a
-    folded one-tap separable layer splits its product into two variables' gradients there); `also` — further
-    parameters that become final with that launch (the caller has raised their pending counts)."""
-    # one grouped launch has ONE row count (os2s_gemm_wgrad_grouped takes a single M): a layer fed by
-    # another number of packed rows (the enc-dec attention's k/v projection of the SOURCE tokens among
-    # target-row layers) starts a new group
-    if self._deferred and self._deferred[0][1]["x"].shape[0] != item["x"].shape[0]:
-      self.flush_deferred()
-    self._deferred.append((param, item))
-    self._deferred_side = side        # False: the grouped launch stays on the current stream (serial profiles)
-    if self._pending is not None and id(param) in self._pending:
-      self._pending[id(param)] += 1
-    if unit_budget is not None:
-      units = sum(((it["dy"].shape[1] + 255) // 256) * ((it["x"].shape[1] + 255) // 256) for _, it in self._deferred)
-      if units >= unit_budget or len(self._deferred) >= 16:
-        self.flush_deferred()
-    elif len(self._deferred) >= (group if group is not None else SMALL_WGRAD_GROUP):
-      self.flush_deferred()
-
-  def defer_conv_wgrad(self, param, key, item, units, launch_kw):
-    """The weight gradient of a convolution layer is held back while layers of the SAME shape over the same batch
-    follow (the `repeat` sub-blocks of a Jasper block: 12 - 150 units of work each for 256 CUs): they go out as one
-    launch of the ping-pong kernel (capi.conv1d_wgrad_grouped, at most 8) once CONV_WGRAD_UNIT_BUDGET units are
-    collected, when a layer of another shape arrives, or at the end of the pass. `param` is not final for the
-    gradient reducer until then."""
-    if self._cdeferred and self._ckey != key:
-      self.flush_conv_wgrads()
-    self._ckey, self._ckw = key, launch_kw
-    self._cdeferred.append((param, item))
-    if self._pending is not None and id(param) in self._pending:
-      self._pending[id(param)] += 1
-    if units * len(self._cdeferred) >= CONV_WGRAD_UNIT_BUDGET or len(self._cdeferred) >= 8:
-      self.flush_conv_wgrads()
-
-  def flush_conv_wgrads(self):
-    if not self._cdeferred:
-      return
-    items = [it for _, it in self._cdeferred]
-    with on_side_stream(items[0]["x"].device, *([it["x"] for it in items] + [it["dy"] for it in items])):
-      capi.conv1d_wgrad_grouped(items, **self._ckw)
-    if self._pending is not None:
-      for p, _ in self._cdeferred:
-        if id(p) in self._pending:
-          self._pending[id(p)] -= 1
-    self._cdeferred, self._ckey = [], None
-
-  def flush_deferred(self):
-    if not self._deferred:
-      return
-    items = [it for _, it in self._deferred]
-    if getattr(self, "_deferred_side", True):
-      with on_side_stream(items[0]["x"].device, *([it["x"] for it in items] + [it["dy"] for it in items] +
-                                                  [it["dw"] for it in items if "after" in it])):
-        capi.gemm_wgrad_grouped(items, accumulate=True)
-        for it in items:
-          if "after" in it:       # behind the launch, on its stream (a folded one-tap separable layer splits its dw)
-            it["after"]()
-    else:
-      capi.gemm_wgrad_grouped(items, accumulate=True)
-      for it in items:
-        if "after" in it:
-          it["after"]()
-    if self._pending is not None:
-      for p, it in self._deferred:
-        for q in (p,) + tuple(it.get("also", ())):
-          if id(q) in self._pending:
-            self._pending[id(q)] -= 1
-    self._deferred = []
-
-
-_TAPE_STACK = []
-
-
-def backward_interleaved(tapes, streams):
-  """Tape.backward for several tapes of the SAME structure (the halves of one batch) on several streams: closure i
-  of every tape is issued before closure i + 1 of any, each on its tape's stream — the kernels of one half that keep
-  the matrix pipes idle (LayerNorm, attention, dropout, embedding) run under the other half's GEMMs. The caller has
-  set _SIDE_KEY_OVERRIDE: parameter-gradient launches of all tapes queue on one side stream. Single-process only
-  (no gradient reducer watermark)."""
-  depth = len(_TAPE_STACK)
-  join_side_streams()
-  capi.zero_arena_enter(depth)
-  for t in tapes:
-    assert t.on_done is None
-    t._deferred, t._pending = [], None
-    t._cdeferred, t._ckey = [], None
-  outer = torch.cuda.current_stream()
-  try:
-    n = max(len(t.ops) for t in tapes)
-    for i in range(n):
-      for t, st in zip(tapes, streams):
-        if i < len(t.ops):
-          fn = t.ops[len(t.ops) - 1 - i][0]
-          _TAPE_STACK.append(t)
-          torch.cuda.set_stream(st)
-          try:
-            fn()
-          finally:
-            _TAPE_STACK.pop()
-    for t, st in zip(tapes, streams):
-      _TAPE_STACK.append(t)
-      torch.cuda.set_stream(st)
-      try:
-        t.flush_deferred()
-        t.flush_conv_wgrads()
-      finally:
-        _TAPE_STACK.pop()
-  finally:
-    torch.cuda.set_stream(outer)
-    capi.zero_arena_leave(depth)
-  for t in tapes:
-    t.ops = []
-  for st in streams:
-    outer.wait_stream(st)
-  join_side_streams()
-
-
-def current_tape():
-  """The tape whose backward pass is running — the innermost one (None outside Tape.backward)."""
-  return _TAPE_STACK[-1] if _TAPE_STACK else None
-
-
-class Act(object):
-  """An activation tensor + its valid lengths + (optionally) its gradient."""
-  __slots__ = ("data", "lens", "grad", "grad_init", "requires_grad", "res_grad", "mask_scale",
-               "grad_masked", "bias_part", "bn_y", "bn_scale", "grad_event", "bn_full_rows")
-
-  def __init__(self, data, lens=None, requires_grad=True):
-    self.data, self.lens = data, lens
-    self.grad, self.grad_init = None, False
-    self.requires_grad = requires_grad
-    self.res_grad = None   # gradient arriving through a residual connection (pre-norm blocks)
-    # set by a ReLU (+ dropout) Dense layer on its OUTPUT: the consumer's data-gradient GEMM may
-    # apply (data > 0) * mask_scale in its epilogue (and leave the bias-gradient partials in
-    # bias_part); it then sets grad_masked and the producer skips its own activation backward
-    self.mask_scale = None
-    self.grad_masked = False
-    self.bias_part = None
-    # set by conv_bn_actv on the output of a single-input conv + BatchNorm + ReLU (+ dropout) layer: the
-    # convolution output y. The data gradient of the NEXT layer's main convolution — the last
-    # contribution to this activation's gradient — then applies the ReLU / dropout backward and leaves
-    # the BatchNorm-backward partials (sum dz, sum dz * y) in bias_part (capi.conv1d_dgrad_bnact)
-    self.bn_y = None
-    self.bn_scale = 1.0
-    # the producer's backward reads EVERY row of the finalised gradient (separable layers: their BatchNorm-backward
-    # apply pass is not ragged): only a consumer that defines all rows may finalise it
-    self.bn_full_rows = False
-    # set by a data-gradient contribution enqueued on the SIDE stream (dense_residual.backward_end): the next
-    # writer or reader of the gradient on another stream waits for it first
-    self.grad_event = None
-
-  def wait_grad(self):
-    if self.grad_event is not None:
-      _current_stream_obj().wait_event(self.grad_event)
-      self.grad_event = None
-
-  def grad_buffer(self):
-    # a gradient that already carries its producer's activation backward takes no more addends
-    assert not self.grad_masked, "a second consumer wrote to an activation whose gradient was finalised"
-    if self.grad_event is not None:
-      self.wait_grad()
-    if self.grad is None:
-      self.grad = torch.empty_like(self.data)
-      self.grad_init = False
-    return self.grad
 
 
 def xavier_normal_conv(shape_dev):
@@ -483,10 +74,18 @@ class ConvBN(object):
   def __init__(self, store, name, bn_name, cin, cout, k, stride=1, dilation=1,
                padding="SAME", bn_momentum=0.9, bn_epsilon=1e-3, l2=0.0,
                initializer=xavier_normal_conv):
-    self.name, self.cin, self.cout, self.k = name, cin, cout, k
-    self.stride, self.dil, self.padding = stride, dilation, padding
+    self._set_geometry(name, cin, cout, k, stride, dilation, padding)
     self.momentum, self.eps = bn_momentum, bn_epsilon
     self.kernel = store.add(name + "/kernel", (k, cout, cin), initializer, kind="conv", l2=l2)
+    self._add_bn(store, bn_name, cout, l2)
+
+  def _set_geometry(self, name, cin, cout, k, stride, dilation, padding):
+    self.name, self.cin, self.cout, self.k = name, cin, cout, k
+    self.stride, self.dil, self.padding = stride, dilation, padding
+
+  def _add_bn(self, store, bn_name, cout, l2):
+    """The variables of tf.layers.batch_normalization under `bn_name`, created AFTER the layer's kernels (the order
+    of `store.add` fixes the flat offsets and the checkpoint layout)."""
     self.gamma = store.add(bn_name + "/gamma", (cout,), torch.ones(cout), kind="vector", l2=l2)
     self.beta = store.add(bn_name + "/beta", (cout,), torch.zeros(cout), kind="vector")
     dev = store.device
@@ -535,8 +134,8 @@ class ConvBN(object):
     x = inp.data
     tape = current_tape()
     units = ((self.cout + 127) // 128) * ((self.cin + 127) // 128) * ((self.k + 3) // 4)
-    if CONV_WGRAD_UNIT_BUDGET > 0 and tape is not None and self.stride == 1 and self.k >= 2 and \
-       units < CONV_WGRAD_UNIT_BUDGET and x.dim() == 3 and x.shape[0] <= 64 and self.cout >= 128 and self.cin >= 64 and \
+    if _tape.CONV_WGRAD_UNIT_BUDGET > 0 and tape is not None and self.stride == 1 and self.k >= 2 and \
+       units < _tape.CONV_WGRAD_UNIT_BUDGET and x.dim() == 3 and x.shape[0] <= 64 and self.cout >= 128 and self.cin >= 64 and \
        dy.is_contiguous() and x.stride(2) == 1 and x.stride(0) == x.shape[1] * x.stride(1):
       # (the envelope of the ping-pong weight-gradient kernel; everything else goes out alone as before)
       key = (tuple(x.shape), tuple(dy.shape), x.stride(1), self.k, self.dil, f["pad_left"],
@@ -612,8 +211,7 @@ class SepConvBN(ConvBN):
   def __init__(self, store, name, bn_name, cin, cout, k, stride=1, dilation=1,
                padding="SAME", bn_momentum=0.9, bn_epsilon=1e-3, l2=0.0,
                initializer=xavier_normal_conv):
-    self.name, self.cin, self.cout, self.k = name, cin, cout, k
-    self.stride, self.dil, self.padding = stride, dilation, padding
+    self._set_geometry(name, cin, cout, k, stride, dilation, padding)
     self.momentum, self.eps = bn_momentum, bn_epsilon
 
     def dw_init(shape):   # same initializer family over the TF shape [K, Cin, 1]
@@ -621,14 +219,7 @@ class SepConvBN(ConvBN):
 
     self.depthwise = store.add(name + "/depthwise_kernel", (k, cin), dw_init, kind="vector", l2=l2)
     self.kernel = store.add(name + "/pointwise_kernel", (1, cout, cin), initializer, kind="conv", l2=l2)
-    self.gamma = store.add(bn_name + "/gamma", (cout,), torch.ones(cout), kind="vector", l2=l2)
-    self.beta = store.add(bn_name + "/beta", (cout,), torch.zeros(cout), kind="vector")
-    dev = store.device
-    self.moving_mean = torch.zeros(cout, dtype=torch.float32, device=dev)
-    self.moving_var = torch.ones(cout, dtype=torch.float32, device=dev)
-    if hasattr(store, "add_state"):
-      store.add_state(bn_name + "/moving_mean", self.moving_mean)
-      store.add_state(bn_name + "/moving_variance", self.moving_var)
+    self._add_bn(store, bn_name, cout, l2)
 
   def conv_bn_stats(self, x, training):
     B, Tin, _ = x.data.shape
@@ -682,13 +273,11 @@ class SepConvBN(ConvBN):
         capi.pointwise_fold_bwd(gw, self.kernel.master, self.depthwise.master, self.kernel.grad, self.depthwise.grad)
       if GROUP_POINTWISE_WGRAD and current_tape() is not None and self.cin >= 128 and self.cout >= 128 and \
          rows >= 2048 and x.is_contiguous() and dy.is_contiguous():
-        tape = current_tape()
-        for p in (self.depthwise,):       # the scale's gradient is final with the same launch
-          if tape._pending is not None and id(p) in tape._pending:
-            tape._pending[id(p)] += 1
-        tape.defer_wgrad(self.kernel, dict(x=x.view(rows, self.cin), dy=dy.view(rows, self.cout),
-                                           dw=gw.view(self.cout, self.cin), after=split, also=(self.depthwise,)),
-                         group=POINTWISE_WGRAD_GROUP)
+        # (also: the scale's gradient is final with the same launch)
+        current_tape().defer_wgrad(self.kernel, dict(x=x.view(rows, self.cin), dy=dy.view(rows, self.cout),
+                                                     dw=gw.view(self.cout, self.cin), after=split,
+                                                     also=(self.depthwise,)),
+                                   group=POINTWISE_WGRAD_GROUP)
       else:
         with on_side_stream(dy.device, x, dy, gw):
           capi.conv1d_wgrad(x, dy, 1, pad_left=0, in_len=inp.lens, out=gw, accumulate=True)
@@ -746,8 +335,7 @@ class DepthwiseBN(ConvBN):
   conv_bn_actv runs it."""
 
   def __init__(self, store, name, channels, k, bn_momentum=0.99, bn_epsilon=1e-3, l2=0.0):
-    self.name, self.cin, self.cout, self.k = name, channels, channels, k
-    self.stride, self.dil, self.padding = 1, 1, "SAME"
+    self._set_geometry(name, channels, channels, k, 1, 1, "SAME")
     self.momentum, self.eps = bn_momentum, bn_epsilon
 
     def init(shape):   # tf.get_variable default: glorot_uniform over [K, 1, C, 1]
@@ -755,14 +343,7 @@ class DepthwiseBN(ConvBN):
       return (torch.rand(shape) * 2 - 1) * lim
 
     self.depthwise = store.add(name + "/w", (k, channels), init, kind="vector", l2=l2)
-    self.gamma = store.add(name + "/bn/gamma", (channels,), torch.ones(channels), kind="vector", l2=l2)
-    self.beta = store.add(name + "/bn/beta", (channels,), torch.zeros(channels), kind="vector")
-    dev = store.device
-    self.moving_mean = torch.zeros(channels, dtype=torch.float32, device=dev)
-    self.moving_var = torch.ones(channels, dtype=torch.float32, device=dev)
-    if hasattr(store, "add_state"):
-      store.add_state(name + "/bn/moving_mean", self.moving_mean)
-      store.add_state(name + "/bn/moving_variance", self.moving_var)
+    self._add_bn(store, name + "/bn", channels, l2)
 
   def conv_bn_stats(self, x, training):
     B, Tin, C = x.data.shape
@@ -790,6 +371,28 @@ class DepthwiseBN(ConvBN):
       accumulate_grad(inp, dx)
 
 
+def _bn_act_backward_head(result, dout, out, branches, fw, rows, lens, act, keep_prob, seed, c1, c2):
+  """From the gradient `dout` at a block's output to dz, the gradient at the sum of its BatchNorm'd branches
+  (`branches` with their forward records `fw`): gamma / beta gradients of every branch and the two means per branch
+  in the rows of c1 / c2. Returns (dz, dz_to_len); dz_to_len: rows of dz past the sequence ends were not written."""
+  if result.grad_masked:
+    # the data gradient that finalised `dout` already applied the ReLU / dropout backward and left
+    # (sum dz, sum dz * y) per 128-row window: no reduction pass (ConvBN.backward_branch, final=True)
+    partial, result.bias_part = result.bias_part, None
+    capi.bn_bwd_finalize_raw(partial, rows, fw[0]["mean"], fw[0]["rstd"], branches[0].gamma.grad,
+                             branches[0].beta.grad, True, c1[0], c2[0])
+    return dout, lens is not None       # rows past the sequence ends were not written: zero, unread
+  dz = torch.empty_like(out)
+  partial = torch.empty((capi.bn_act_bwd_num_parts(rows), 1 + len(branches), out.shape[2]), dtype=torch.float32,
+                        device=out.device)
+  capi.bn_act_bwd_reduce(dout, out, [f["y"] for f in fw], [f["mean"] for f in fw],
+                         [f["rstd"] for f in fw], dz, partial, lens, act, keep_prob, seed)
+  # dgamma / dbeta / the two means of every branch in ONE launch
+  capi.bn_bwd_finalize_multi(partial, rows, [br.gamma.grad for br in branches],
+                             [br.beta.grad for br in branches], True, c1, c2)
+  return dz, False
+
+
 def conv_bn_res_bn_actv(main, res_branches, x, res_inputs, out_lens, activation_fn,
                         training, tape, keep_prob=1.0, seed=0, mask_output=True,
                         drop_block_prob=0.0, drop_block=False, res_fw=None):
@@ -809,7 +412,7 @@ def conv_bn_res_bn_actv(main, res_branches, x, res_inputs, out_lens, activation_
   inputs = [x] + list(res_inputs)
   fw_main = main.conv_bn_stats(x, training)
   if res_fw is not None:         # launched earlier on the side stream (launch_residual_early)
-    join_side_streams()
+    streams.join_side_streams()
     global _FWD_SIDE_BUSY
     _FWD_SIDE_BUSY = False
     fw = [fw_main] + res_fw
@@ -852,24 +455,7 @@ def conv_bn_res_bn_actv(main, res_branches, x, res_inputs, out_lens, activation_
     J = len(branches)
     c1 = torch.empty((J, C), dtype=torch.float32, device=out.device)
     c2 = torch.empty((J, C), dtype=torch.float32, device=out.device)
-    dz_to_len = False
-    if result.grad_masked:
-      # the data gradient that finalised `dout` already applied the ReLU / dropout backward and left
-      # (sum dz, sum dz * y) per 128-row window: no reduction pass (ConvBN.backward_branch, final=True)
-      dz, partial = dout, result.bias_part
-      result.bias_part = None
-      capi.bn_bwd_finalize_raw(partial, rows, fw[0]["mean"], fw[0]["rstd"], branches[0].gamma.grad,
-                               branches[0].beta.grad, True, c1[0], c2[0])
-      dz_to_len = lens is not None       # rows past the sequence ends were not written: zero, unread
-    else:
-      dz = torch.empty_like(out)
-      partial = torch.empty((capi.bn_act_bwd_num_parts(rows), 1 + J, C), dtype=torch.float32,
-                            device=out.device)
-      capi.bn_act_bwd_reduce(dout, out, [f["y"] for f in fw], [f["mean"] for f in fw],
-                             [f["rstd"] for f in fw], dz, partial, lens, act, keep_prob, seed)
-      # dgamma / dbeta / the two means of every branch in ONE launch
-      capi.bn_bwd_finalize_multi(partial, rows, [br.gamma.grad for br in branches],
-                                 [br.beta.grad for br in branches], True, c1, c2)
+    dz, dz_to_len = _bn_act_backward_head(result, dout, out, branches, fw, rows, lens, act, keep_prob, seed, c1, c2)
     result.grad = None
     grouped = []        # plain 1x1 residual branches: their data gradients go out in one launch
     wgrouped = []       # ... and so do their weight gradients
@@ -894,13 +480,11 @@ def conv_bn_res_bn_actv(main, res_branches, x, res_inputs, out_lens, activation_
           br.backward_weights(inp, dy, f)
         if inp.requires_grad:
           grouped.append((br, inp, dy))
-      elif j == 0 and br is main and type(br) is ConvBN:
+      elif j == 0 and br is main and type(br) in (ConvBN, SepConvBN):
         # the last contribution to its input's gradient — unless the same activation also feeds a
         # residual branch of THIS call (a residual block with repeat = 1), which runs after it.
         # (With the block dropped, branches[0] is a RESIDUAL branch whose input still has
         # later-running consumers: never final.)
-        br.backward_branch(inp, dy, f, final=all(r is not inp for r in inputs[1:]))
-      elif j == 0 and br is main and type(br) is SepConvBN:
         br.backward_branch(inp, dy, f, final=all(r is not inp for r in inputs[1:]))
       else:
         br.backward_branch(inp, dy, f)
@@ -927,7 +511,7 @@ def launch_dense_residual(dpass, k, x):
   """Registers block k's input `x` as source k of the dense-residual pass and evaluates block end k's residual
   sum — it depends on the block INPUTS only — on the side stream, next to the block's own layers. Returns the
   record conv_bn_dres_actv consumes (it joins the side stream first)."""
-  if not DRES_FWD_SIDE or _side_stream(x.data.device, 1) is None:
+  if not DRES_FWD_SIDE or streams._side_stream(x.data.device, 1) is None:
     dpass.add_source(x)
     return dpass.forward_end(k)
   global _FWD_SIDE_BUSY
@@ -947,7 +531,7 @@ def conv_bn_dres_actv(main, x, dfw, out_lens, activation_fn, training, tape, kee
   dense_residual.backward_end (side stream) and runs the main branch as conv_bn_res_bn_actv does."""
   act = act_id(activation_fn)
   fw = main.conv_bn_stats(x, training)
-  join_side_streams()
+  streams.join_side_streams()
   global _FWD_SIDE_BUSY
   _FWD_SIDE_BUSY = False
   B = x.data.shape[0]
@@ -975,17 +559,7 @@ def conv_bn_dres_actv(main, x, dfw, out_lens, activation_fn, training, tape, kee
     rows = B * tout
     c1 = torch.empty((1, C), dtype=torch.float32, device=out.device)
     c2 = torch.empty((1, C), dtype=torch.float32, device=out.device)
-    dz_to_len = False
-    if result.grad_masked:
-      dz, partial = dout, result.bias_part
-      result.bias_part = None
-      capi.bn_bwd_finalize_raw(partial, rows, fw["mean"], fw["rstd"], main.gamma.grad, main.beta.grad, True, c1[0], c2[0])
-      dz_to_len = lens is not None       # rows past the sequence ends were not written: never read below
-    else:
-      dz = torch.empty_like(out)
-      partial = torch.empty((capi.bn_act_bwd_num_parts(rows), 2, C), dtype=torch.float32, device=out.device)
-      capi.bn_act_bwd_reduce(dout, out, [fw["y"]], [fw["mean"]], [fw["rstd"]], dz, partial, lens, act, keep_prob, seed)
-      capi.bn_bwd_finalize_multi(partial, rows, [main.gamma.grad], [main.beta.grad], True, c1, c2)
+    dz, dz_to_len = _bn_act_backward_head(result, dout, out, [main], [fw], rows, lens, act, keep_prob, seed, c1, c2)
     result.grad = None
     # every residual branch (kernel / gamma / beta gradients) and the finished data gradient of source k
     src = dpass.acts[k]
@@ -1028,7 +602,7 @@ def launch_residual_early(res_branches, res_inputs, training):
   idle (an HBM-bound grouped launch next to MFMA-bound ones). Returns what
   grouped_conv1x1_bn_stats returns, for conv_bn_res_bn_actv(..., res_fw=...) which joins the side
   stream before its BatchNorm sum; None when there is no side stream (OS2S_WGRAD_STREAM=0)."""
-  if not res_branches or _side_stream(res_inputs[0].data.device) is None:
+  if not res_branches or streams._side_stream(res_inputs[0].data.device) is None:
     return None
   global _FWD_SIDE_BUSY
   _FWD_SIDE_BUSY = True
@@ -1094,8 +668,7 @@ class ConvOnly(ConvBN):
 
   def __init__(self, store, name, cin, cout, k, stride=1, dilation=1, padding="SAME", l2=0.0,
                initializer=xavier_normal_conv):
-    self.name, self.cin, self.cout, self.k = name, cin, cout, k
-    self.stride, self.dil, self.padding = stride, dilation, padding
+    self._set_geometry(name, cin, cout, k, stride, dilation, padding)
     self.kernel = store.add(name + "/kernel", (k, cout, cin), initializer, kind="conv", l2=l2)
 
   def trainable(self):
@@ -1174,25 +747,3 @@ def conv_bn_actv(layer, x, out_lens, activation_fn, training, tape, keep_prob=1.
                  mask_output=True):
   return conv_bn_res_bn_actv(layer, [], x, [], out_lens, activation_fn, training, tape,
                              keep_prob, seed, mask_output)
-
-
-def accumulate_grad(x, g):
-  """x.grad (+)= g for an Act consumed by several ops."""
-  if not x.requires_grad:
-    return
-  if x.grad_init and x.grad is not None:
-    capi.add_bf16(x.grad, g, out=x.grad)
-  else:
-    x.grad, x.grad_init = g, True
-
-
-def reshape_act(x, shape, tape, lens=None):
-  """A view of an Act with another shape ([B,T,C] <-> [B*T,C]); gradients flow back."""
-  v = Act(x.data.view(*shape), lens, requires_grad=x.requires_grad)
-  if tape is not None and x.requires_grad:
-    def backward():
-      if v.grad is not None:
-        accumulate_grad(x, v.grad.reshape(x.data.shape))
-      v.grad = None
-    tape.record(backward)
-  return v

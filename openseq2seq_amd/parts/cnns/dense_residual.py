@@ -25,6 +25,7 @@ import os
 import torch
 
 from ... import capi
+from .conv_blocks import ConvBN
 
 # A/B knob: 0 = branch-by-branch residual path everywhere (rounds 1 - 5)
 ENABLED = os.environ.get("OS2S_DENSE_RES_ALGEBRA", "1") != "0"
@@ -49,7 +50,6 @@ class DenseResidualPlan(object):
 
   @staticmethod
   def eligible(ends):
-    from .conv_blocks import ConvBN
     if not ENABLED or len(ends) < 2 or len(ends) > 16:
       return False
     for k, brs in enumerate(ends):

@@ -14,7 +14,8 @@ import os
 import torch
 
 from ... import capi
-from ..cnns.conv_blocks import Act, on_side_stream
+from ..streams import on_side_stream
+from ..tape import Act
 from ..transformer.layers import _colsum_into
 
 CELLS = {"gru_cudnn": capi.CELL_GRU_CUDNN, "lstm_cudnn": capi.CELL_LSTM_CUDNN,

@@ -14,7 +14,7 @@ import torch
 
 from ... import capi
 from ...encoders.ds2_encoder import Conv2dBN
-from ..cnns.conv_blocks import Act, accumulate_grad
+from ..tape import Act, accumulate_grad
 from ..transformer.layers import Dense, _colsum_into
 
 

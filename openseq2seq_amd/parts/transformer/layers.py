@@ -3,7 +3,7 @@
 open_seq2seq/parts/transformer/{attention_layer,ffn_layer,common,embedding_layer}.py).
 
 Every block enqueues its forward kernels and records ONE backward closure on the
-Tape (see parts/cnns/conv_blocks.py). Activations are `Act` holders with 2-D bf16
+Tape (see parts/tape.py). Activations are `Act` holders with 2-D bf16
 data [N_tokens, hidden]. Padding never exists in this layout, so the reference's
 FFN "remove_padding" (ffn_layer.py:56-70) is implicit and extends to every token-wise
 op (LayerNorm, all projections), and padded keys need no -1e9 bias.
@@ -13,7 +13,8 @@ import math
 import torch
 
 from ... import capi
-from ..cnns.conv_blocks import Act, on_side_stream, current_tape
+from ..streams import on_side_stream
+from ..tape import Act, current_tape
 
 
 SKINNY_MAX_ROWS = 512

@@ -167,7 +167,7 @@ class GradientReducer(object):
         self._snap.append((s, e, g[s:e].clone()))
       self._all_reduce(g[s:e])
       return
-    from ..parts.cnns.conv_blocks import side_streams
+    from ..parts.streams import side_streams
     ev = torch.cuda.Event()
     ev.record(torch.cuda.current_stream())
     self.stream.wait_event(ev)

@@ -92,7 +92,7 @@ def test_toy_speech_test_configs_equal_the_reference():
   configurations (DS2 / W2L convergence tests, block-dropout runs): same dictionaries, value for value (the
   clipped-ReLU lambda is compared by what it resolves to)."""
   from openseq2seq_amd.utils.utils import get_base_config
-  from openseq2seq_amd.parts.cnns.conv_blocks import act_id
+  from openseq2seq_amd.parts.activations import act_id
   repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
   def norm(x):

@@ -232,15 +232,15 @@ def test_model_refuses_fewer_replicas_than_the_config_names():
 def test_tape_deferred_weight_gradients_hold_the_watermark(monkeypatch):
   """A weight gradient handed to Tape.defer_wgrad (grouped launch later) is not final when its
   closure returns: the reducer's watermark waits for the flush, then moves past it."""
-  from openseq2seq_amd.parts.cnns import conv_blocks
-  from openseq2seq_amd.parts.cnns.conv_blocks import Tape, current_tape
+  from openseq2seq_amd import capi
+  from openseq2seq_amd.parts.tape import Tape, current_tape
 
   class P(object):
     def __init__(self, offset):
       self.offset = offset
 
   launched = []
-  monkeypatch.setattr(conv_blocks.capi, "gemm_wgrad_grouped",
+  monkeypatch.setattr(capi, "gemm_wgrad_grouped",
                       lambda items, accumulate=True: launched.append([it["tag"] for it in items]))
   a, b, c, d, e = P(0), P(100), P(200), P(300), P(400)
   marks = []

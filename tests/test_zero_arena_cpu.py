@@ -35,11 +35,11 @@ def test_tape_backward_nests_with_an_arena_per_depth():
   """Tape.backward is re-entrant (product hygiene): a pass started from inside a closure of
   another one takes its zeroed scratch from the arena of ITS depth — the outer pass's partials stay as they
   are — and current_tape() is the innermost pass."""
-  from openseq2seq_amd.parts.cnns import conv_blocks as cb
+  from openseq2seq_amd.parts import streams, tape as cb
   from openseq2seq_amd import capi
   dev = torch.device("cpu")
-  saved = cb.join_side_streams
-  cb.join_side_streams = lambda: None
+  saved = streams.join_side_streams
+  streams.join_side_streams = lambda: None
   seen = []
   try:
     for rounds in range(3):          # round 0 teaches the arenas their demand, later rounds hand out arena slices
@@ -85,4 +85,4 @@ def test_tape_backward_nests_with_an_arena_per_depth():
       pass
     assert cb.current_tape() is None and capi._zero_arena is capi._zero_arenas[0]
   finally:
-    cb.join_side_streams = saved
+    streams.join_side_streams = saved

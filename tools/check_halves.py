@@ -2,7 +2,7 @@
 import sys, torch
 sys.path.insert(0, ".")
 from openseq2seq_amd.configs.transformer import transformer_config
-from openseq2seq_amd.parts.cnns.conv_blocks import Tape
+from openseq2seq_amd.parts.tape import Tape
 dev = torch.device("cuda:0")
 model_cls, params = transformer_config(batch_size_per_gpu=64)
 for part in ("encoder_params", "decoder_params"):

@@ -45,7 +45,7 @@ def main():
   args = ap.parse_args()
   lib = build()
   from openseq2seq_amd import capi
-  from openseq2seq_amd.parts.cnns import conv_blocks
+  from openseq2seq_amd.parts import tape
   dev = torch.device("cuda", 0)
   torch.cuda.set_device(dev)
   if args.model == "jasper":
@@ -64,7 +64,7 @@ def main():
   where = torch.full((256,), -1, dtype=torch.int32, device=dev)
   thief_stream = torch.cuda.Stream(device=dev)
   state = {"n": 0, "mode": "off", "bwd_us": 25000.0}
-  orig_backward = conv_blocks.Tape.backward
+  orig_backward = tape.Tape.backward
 
   def backward(self):
     n, mode = state["n"], state["mode"]
@@ -80,7 +80,7 @@ def main():
             lib.cu_thief_launch(ctypes.c_void_p(thief_stream.cuda_stream), n, 450.0, ctypes.c_void_p(sink.data_ptr()), None)
             lib.cu_thief_launch(ctypes.c_void_p(thief_stream.cuda_stream), 1, gap, ctypes.c_void_p(sink.data_ptr()), None)
     return orig_backward(self)
-  conv_blocks.Tape.backward = backward
+  tape.Tape.backward = backward
 
   fell_back = {}
 

@@ -4,22 +4,22 @@ sys.path.insert(0, ".")
 import torch
 dev = torch.device("cuda:0"); torch.cuda.set_device(dev)
 from openseq2seq_amd import capi
-from openseq2seq_amd.parts.cnns import conv_blocks
+from openseq2seq_amd.parts import streams
 
 # join only the side streams that belong to the current (capturing) stream
 def join_side_streams():
-  if conv_blocks._SIDE_STREAMS:
-    cur = conv_blocks._current_stream_obj()
+  if streams._SIDE_STREAMS:
+    cur = streams._current_stream_obj()
     base = capi._stream().value
-    for key, st in conv_blocks._SIDE_STREAMS.items():
+    for key, st in streams._SIDE_STREAMS.items():
       if key[1] != base:
         continue
-      ev = conv_blocks._JOIN_EVENT.get(st)
+      ev = streams._JOIN_EVENT.get(st)
       if ev is None:
-        ev = conv_blocks._JOIN_EVENT[st] = torch.cuda.Event()
+        ev = streams._JOIN_EVENT[st] = torch.cuda.Event()
       ev.record(st)
       cur.wait_event(ev)
-conv_blocks.join_side_streams = join_side_streams
+streams.join_side_streams = join_side_streams
 
 specs = {"jasper": ("openseq2seq_amd.configs.jasper", "jasper10x5_config", {"batch_size_per_gpu": 32, "use_horovod": True}),
          "quartznet": ("openseq2seq_amd.configs.quartznet", "quartznet15x5_config", {}),

@@ -29,12 +29,12 @@ def main():
   op = model.train_op
   orig_run = op.run
   stats = {"done": 0, "n": 0, "host_us_backward_to_opt": []}
-  from openseq2seq_amd.parts.cnns import conv_blocks
-  orig_backward = conv_blocks.Tape.backward
+  from openseq2seq_amd.parts import streams, tape
+  orig_backward = tape.Tape.backward
   marks = {}
 
   joins = []
-  orig_join = conv_blocks.join_side_streams
+  orig_join = streams.join_side_streams
   state = {"in_bwd": False, "n": 0}
 
   def join():
@@ -43,7 +43,7 @@ def main():
     state["n"] += 1
     if state["in_bwd"] and state["n"] == 2:
       tails = []
-      for st in conv_blocks.side_streams():
+      for st in streams.side_streams():
         e = torch.cuda.Event(enable_timing=True)
         e.record(st)
         tails.append(e)
@@ -55,7 +55,7 @@ def main():
       joins.append((tails, last_main, after))
       return
     orig_join()
-  conv_blocks.join_side_streams = join
+  streams.join_side_streams = join
 
   def backward(self):
     state["in_bwd"], state["n"] = True, 0
@@ -74,7 +74,7 @@ def main():
       stats["host_us_backward_to_opt"].append(1e6 * (time.perf_counter() - marks["t"]))
     return orig_run()
 
-  conv_blocks.Tape.backward = backward
+  tape.Tape.backward = backward
   op.run = run
   for _ in range(8):
     model.train_step(batch)
