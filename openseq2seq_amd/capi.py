@@ -618,6 +618,12 @@ def bn_bwd_finalize(partial, q, count, dgamma, dbeta, accumulate, c1, c2):
                               int(accumulate), _ptr(c1, torch.float32), _ptr(c2, torch.float32))
 
 
+def colsum_finalize(partial, dgamma, dbeta):
+  """partial [nparts, 2, C] column sums -> dbeta += plane 0, dgamma (or None) += plane 1, on the current stream."""
+  scratch = torch.empty((2, partial.shape[2]), dtype=torch.float32, device=partial.device)
+  bn_bwd_finalize(partial, 1, 1, dgamma, dbeta, True, scratch[0], scratch[1])
+
+
 def bn_bwd_finalize_multi(partial, count, dgammas, dbetas, accumulate, c1, c2):
   """All J inputs of a block end in one launch: c1, c2 are [J, C] (row j for input j)."""
   import ctypes
@@ -1055,8 +1061,7 @@ def layernorm_bwd(dy, x, gamma, mean, rstd, dres, dgamma, dbeta, defer_param_gra
                             _ptr(gamma, torch.float32), _ptr(mean, torch.float32), _ptr(rstd, torch.float32),
                             _ptr(dres, torch.bfloat16, True), N, D, _ptr(dx), _ptr(partial))
   def finish():
-    scratch = torch.empty((2, D), dtype=torch.float32, device=x.device)
-    bn_bwd_finalize(partial, 1, 1, dgamma, dbeta, True, scratch[0], scratch[1])
+    colsum_finalize(partial, dgamma, dbeta)
   if defer_param_grads:
     return dx, finish, partial
   finish()

@@ -78,10 +78,7 @@ class FullyConnectedTimeDecoder(Decoder):
         assert dl is not None, "loss did not provide dlogits"
         # dW [1,Vpad,A] += dl^T x ; db += column sums ; dX = dl @ W
         capi.conv1d_wgrad(x.data, dl, 1, pad_left=0, out=dec.kernel.grad, accumulate=True)
-        part = capi.bn_stats(dl.view(-1, dec.Vpad))
-        scratch = torch.empty(2, dec.Vpad, dtype=torch.float32, device=dl.device)
-        part2 = part.view(part.shape[0], 2, dec.Vpad)
-        capi.bn_bwd_finalize(part2, 1, 1, None, dec.bias.grad, True, scratch[0], scratch[1])
+        capi.colsum_finalize(capi.bn_stats(dl.view(-1, dec.Vpad)), None, dec.bias.grad)
         if x.requires_grad:
           g = x.grad_buffer()
           capi.conv1d_fwd(dl, dec.kernel.wt16, pad_left=0, tout=T, out=g,

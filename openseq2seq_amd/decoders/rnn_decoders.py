@@ -23,7 +23,7 @@ from .. import capi
 from ..encoders.rnn_encoders import Embedding, apply_scope_initializer, cell_spec, dropout_act, residual_add
 from ..parts.tape import Act
 from ..parts.rnns.rnn_layers import RNNDirection, rnn_directions_forward
-from ..parts.transformer.layers import SeedSeq, _colsum_into
+from ..parts.dense import SeedSeq, bias_grad_from_rows
 
 
 def _round8(n):
@@ -159,7 +159,7 @@ class AttentionCell(object):
       for l in range(cell.L):
         dg2 = out["dg"][l].view(B * T, GH)
         _wgrad_rows(dec.cat[l], out["dg"][l], cell.wcat[l].grad)
-        _colsum_into(dg2, cell.bias[l])
+        bias_grad_from_rows(dg2, cell.bias[l])
       dg0 = out["dg"][0].view(B * T, GH)
       capi.gemm_wgrad(x.data.reshape(B * T, -1), dg0, cell.w_in.grad.view(GH, -1), accumulate=True)
       if x.requires_grad:
@@ -171,7 +171,7 @@ class AttentionCell(object):
         capi.gemm_wgrad(dec.y_top.reshape(B * T, H) if dec.y_top.is_contiguous() else
                         dec.y_top.contiguous().view(B * T, H), dq2, cell.w_q.grad.view(U, H), accumulate=True)
       if cell.b is not None:
-        _colsum_into(dq2, cell.b)
+        bias_grad_from_rows(dq2, cell.b)
       # memory layer + encoder outputs
       dk16 = torch.empty((B * S, U), dtype=torch.bfloat16, device=dev)
       capi.cast_f32_to_bf16(out["dkeys"].view(-1), dk16.view(-1))

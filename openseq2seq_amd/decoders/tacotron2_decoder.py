@@ -23,7 +23,7 @@ from .rnn_decoders import AttentionCell
 from .. import capi
 from ..parts.cnns.conv_blocks import ConvBN, conv_bn_actv, xavier_normal_conv
 from ..parts.tape import Act, accumulate_grad, reshape_act
-from ..parts.transformer.layers import Dense, SeedSeq
+from ..parts.dense import Dense, SeedSeq
 
 
 PRENET_KEEP = 0.5   # tf.layers.dropout(rate=0.5, training=True): on in every mode (:63)

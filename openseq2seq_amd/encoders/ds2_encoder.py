@@ -20,7 +20,7 @@ from .. import capi
 from ..parts.activations import act_id
 from ..parts.tape import Act
 from ..parts.rnns.rnn_layers import BiRNNStack
-from ..parts.transformer.layers import Dense, SeedSeq
+from ..parts.dense import Dense, SeedSeq
 
 
 class Conv2dBN(object):

@@ -17,7 +17,7 @@ from .encoder import Encoder
 from .. import capi
 from ..parts.tape import Act
 from ..parts.rnns.rnn_layers import RNNDirection, rnn_directions_forward
-from ..parts.transformer.layers import SeedSeq
+from ..parts.dense import SeedSeq
 
 
 def cell_spec(core_cell, core_cell_params):

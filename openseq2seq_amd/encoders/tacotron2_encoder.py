@@ -14,7 +14,7 @@ from .. import capi
 from ..parts.cnns.conv_blocks import ConvBN, conv_bn_actv, xavier_normal_conv
 from ..parts.tape import Act, reshape_act
 from ..parts.rnns.rnn_layers import RNNDirection, rnn_directions_forward
-from ..parts.transformer.layers import SeedSeq
+from ..parts.dense import SeedSeq
 
 
 class Tacotron2Encoder(Encoder):

@@ -187,8 +187,8 @@ class Model(object):
     self._build_forward_pass_objects(self._store)
     need_m2 = False
     if self._mode == "train":
-      from ..optimizers.optimizers import _optimizer_id
-      need_m2 = _optimizer_id(self._params['optimizer']) == 3
+      from ..optimizers.optimizers import needs_second_moments
+      need_m2 = needs_second_moments(self._params['optimizer'])
     self._store.finalize(need_m2=need_m2)
     world = self._hvd.size() if self._hvd is not None else 1
     if self._hvd is not None and world > 1:

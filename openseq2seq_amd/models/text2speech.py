@@ -5,7 +5,7 @@ The reference defines no objects-per-step for TTS; benchmarks here count target 
 from __future__ import absolute_import, division, print_function
 
 from .encoder_decoder import EncoderDecoderModel
-from ..parts.transformer.layers import SeedSeq
+from ..parts.dense import SeedSeq
 
 
 class Text2Speech(EncoderDecoderModel):

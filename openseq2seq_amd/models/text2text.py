@@ -4,7 +4,7 @@ metric counts source + target tokens (:227-241)."""
 from __future__ import absolute_import, division, print_function
 
 from .encoder_decoder import EncoderDecoderModel
-from ..parts.transformer.layers import SeedSeq
+from ..parts.dense import SeedSeq
 
 
 class Text2Text(EncoderDecoderModel):

@@ -45,6 +45,11 @@ def _optimizer_id(optimizer):
   return oid
 
 
+def needs_second_moments(optimizer):
+  """Whether the flat store needs the per-element second-moment buffer (the Adam kernel)."""
+  return _optimizer_id(optimizer) == 3
+
+
 def build_opt_config(optimizer, optimizer_params, learning_rate_decay_fn,
                      lr_policy_params, larc_params=None, loss_scaling=1.0,
                      loss_scaling_params=None, clip_gradients=None, dtype="mixed",

@@ -16,7 +16,7 @@ import torch
 from ... import capi
 from ..streams import on_side_stream
 from ..tape import Act
-from ..transformer.layers import _colsum_into
+from ..dense import bias_grad_from_rows
 
 CELLS = {"gru_cudnn": capi.CELL_GRU_CUDNN, "lstm_cudnn": capi.CELL_LSTM_CUDNN,
          "lstm_tf": capi.CELL_LSTM_TF}
@@ -76,9 +76,9 @@ class RNNDirection(object):
     with on_side_stream(dgx.device, dgx, dgr, y, *[x.data for x in xs]):
       for x, w in zip(xs, self.wx):
         capi.gemm_wgrad(x.data.reshape(B * T, -1), d2, w.grad.view(GH, -1), accumulate=True)
-      _colsum_into(d2, self.bx)
+      bias_grad_from_rows(d2, self.bx)
       if self.bh is not None:
-        _colsum_into(dgr.view(B * T, GH), self.bh)
+        bias_grad_from_rows(dgr.view(B * T, GH), self.bh)
       # dWh += dgr^T . h_{t-1}: h_{t-1} is y shifted by one step in processing order
       if B * T >= SHIFTED_WH_MIN_ROWS and H % 8 == 0 and T > 1:
         # as a plain TN GEMM over a shifted copy of y (the 256 x 256 ping-pong weight-gradient kernel:

@@ -15,7 +15,7 @@ import torch
 from ... import capi
 from ...encoders.ds2_encoder import Conv2dBN
 from ..tape import Act, accumulate_grad
-from ..transformer.layers import Dense, _colsum_into
+from ..dense import Dense, bias_grad_from_rows
 
 
 class StyleEncoder(object):
@@ -104,8 +104,8 @@ class StyleEncoder(object):
         dg2, dc2 = dgxg.view(B * Tr, 2 * H), dgxc.view(B * Tr, H)
         capi.gemm_wgrad(flat, dg2, enc.wg_x.grad.view(2 * H, W), accumulate=True)
         capi.gemm_wgrad(flat, dc2, enc.wc_x.grad.view(H, W), accumulate=True)
-        _colsum_into(dg2, enc.bg)
-        _colsum_into(dc2, enc.bc)
+        bias_grad_from_rows(dg2, enc.bg)
+        bias_grad_from_rows(dc2, enc.bc)
         # recurrent kernels: dWg_h [H,2H] = hprev^T dg, dWc_h [H,H] = (r*h)^T dc
         tg = torch.zeros((2 * H, H), dtype=torch.float32, device=dev)
         capi.gemm_wgrad(sv["hprev16"].view(B * Tr, H), dg2, tg, accumulate=False)

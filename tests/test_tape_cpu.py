@@ -1,6 +1,9 @@
 """Where the reverse-mode engine lives: parts/tape.py (Tape, Act), parts/streams.py (side streams),
 parts/activations.py (activation ids); parts/cnns/conv_blocks.py keeps the CNN layers and re-exports the engine's
-classes and functions for the callers that reach them through it."""
+classes and functions for the callers that reach them through it. parts/dense.py (Dense, SeedSeq, the bias gradient of
+row-major activations and the Dense knobs) is the same for parts/transformer/layers.py."""
+import ast
+import os
 
 # module-level state and A/B knobs: a second binding under another module name would diverge silently
 ONE_HOME = {
@@ -11,17 +14,21 @@ ONE_HOME = {
                     "POINTWISE_WGRAD_GROUP", "GROUP_WGRAD_PP", "DRES_FWD_SIDE", "WGRAD_STREAMS", "DRES_FUSE_BN_BWD",
                     "SEP_FUSE_BN_BWD", "FOLD_SEP_K1"),
     "activations": ("ACT_IDS",),
+    "dense": ("SKINNY_MAX_ROWS", "DENSE_WGRAD_STREAM", "FUSE_RELU_BWD", "GROUP_SMALL_WGRAD", "WGRAD_UNIT_BUDGET"),
 }
 
 
 def test_engine_modules_one_home_per_global_and_fresh_tape_flushes():
-  from openseq2seq_amd.parts import activations, streams, tape
+  from openseq2seq_amd.parts import activations, dense, streams, tape
   from openseq2seq_amd.parts.cnns import conv_blocks
-  mods = {"streams": streams, "tape": tape, "conv_blocks": conv_blocks, "activations": activations}
+  from openseq2seq_amd.parts.transformer import layers
+  mods = {"streams": streams, "tape": tape, "conv_blocks": conv_blocks, "activations": activations, "dense": dense,
+          "layers": layers}
   # the re-exports are the same objects (bench.py patches conv_blocks.Tape.backward: an attribute of the one class)
   assert conv_blocks.Tape is tape.Tape and conv_blocks.Act is tape.Act
   assert conv_blocks.on_side_stream is streams.on_side_stream
   assert conv_blocks.current_tape is tape.current_tape and conv_blocks.act_id is activations.act_id
+  assert layers.Dense is dense.Dense and layers.SeedSeq is dense.SeedSeq
   for home, names in ONE_HOME.items():
     for name in names:
       assert [k for k, m in sorted(mods.items()) if hasattr(m, name)] == [home], name
@@ -33,3 +40,48 @@ def test_engine_modules_one_home_per_global_and_fresh_tape_flushes():
   assert streams._SIDE_KEY_OVERRIDE == 7
   streams.set_side_key_override(None)
   assert streams._SIDE_KEY_OVERRIDE is None
+
+
+# the Transformer's own encoder and decoder are built from the layers module; nothing else outside parts/transformer/ is
+LAYERS_CLIENTS = (["encoders", "transformer_encoder"], ["decoders", "transformer_decoder"])
+
+
+def _package_imports(top):
+  """(module path as a list below openseq2seq_amd, its package, imported module, imported names) of every
+  `from ... import ...` inside the package that names a module of the package."""
+  for dirpath, _, files in os.walk(top):
+    for f in sorted(files):
+      if f.endswith(".py"):
+        path = os.path.join(dirpath, f)
+        me = os.path.relpath(path, top)[:-3].split(os.sep)            # ["parts", "rnns", "rnn_layers"]
+        pkg = ["openseq2seq_amd"] + me[:-1]
+        for node in ast.walk(ast.parse(open(path).read(), path)):
+          if isinstance(node, ast.ImportFrom):
+            mod = (pkg[:len(pkg) - (node.level - 1)] if node.level else []) + \
+                (node.module.split(".") if node.module else [])
+            if mod[:1] == ["openseq2seq_amd"]:
+              yield me, pkg, mod, [a.name for a in node.names]
+          elif isinstance(node, ast.Import):
+            assert not any(a.name.startswith("openseq2seq_amd") for a in node.names), path   # relative imports only
+
+
+def test_only_the_transformer_imports_its_layers_and_no_private_name_crosses_a_package():
+  """Source level, over openseq2seq_amd/. (1) No module outside parts/transformer/ imports FROM
+  parts.transformer.layers, and only the Transformer encoder and decoder import the module itself: what the other
+  families share lives in parts/dense.py. (2) No module imports an underscore-prefixed name from another package —
+  one that is neither its own nor one that contains it (`from .. import _lib` in utils/ stays inside openseq2seq_amd)."""
+  import openseq2seq_amd
+  top = os.path.dirname(os.path.abspath(openseq2seq_amd.__file__))
+  layers = ["openseq2seq_amd", "parts", "transformer", "layers"]
+  seen = 0
+  for me, pkg, mod, names in _package_imports(top):
+    seen += 1
+    where = "/".join(me) + ".py"
+    if me[:2] != ["parts", "transformer"]:
+      assert mod != layers, where + " imports from parts.transformer.layers"
+      assert not (mod == layers[:-1] and "layers" in names) or me in LAYERS_CLIENTS, where
+    # the package that owns the names: that of `mod` if it is a module file, `mod` itself if it is a package
+    owner = mod[:-1] if os.path.isfile(os.path.join(os.path.dirname(top), *mod) + ".py") else mod
+    private = [n for n in names if n.startswith("_")]
+    assert not private or pkg[:len(owner)] == owner, "%s imports %s from %s" % (where, private, ".".join(mod))
+  assert seen > 150       # the walk found the package

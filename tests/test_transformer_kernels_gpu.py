@@ -276,8 +276,28 @@ def test_dropout_bwd_colsum(cuda, rows, C):
     d, part = capi.dropout_bwd_colsum(dy, 0.8, **kw)
     assert torch.equal(d, ref)
     acc = torch.full((C,), 3.0, device=cuda)
-    scratch = torch.empty(2, C, device=cuda)
-    capi.bn_bwd_finalize(part, 1, 1, None, acc, True, scratch[0], scratch[1])
+    capi.colsum_finalize(part, None, acc)
     want = 3.0 + ref.float().sum(0)
     tol = 1e-5 * ref.float().abs().sum(0) + 1e-4
     assert bool(((acc - want).abs() <= tol).all())
+
+
+@pytest.mark.parametrize("N,C", [(1, 8), (257, 72), (2049, 136)])
+def test_bias_grad_from_rows(cuda, N, C):
+  """parts/dense.py bias_grad_from_rows (os2s_bn_stats + capi.colsum_finalize): bias.grad += column sums of bf16
+  [N, C] rows, into a gradient that already holds a value. One row; a row count that does not divide the partial
+  block; more than one partial block with a channel count that is no power of two. Against the fp64 column sums of
+  the same bf16 values plus the pre-fill; per column within N * 2^-23 * sum|x|, the bound of an fp32 accumulation
+  of N addends in any order (the pre-fill is not in it: at N = 1 it adds exactly, 3 + a bf16 value is an fp32 number)."""
+  from types import SimpleNamespace
+  from openseq2seq_amd.parts.dense import bias_grad_from_rows
+  bias = SimpleNamespace(grad=torch.full((C,), 3.0, device=cuda))       # all the helper reads of a parameter
+  g = torch.Generator().manual_seed(N + C)
+  x = _bf(torch.randn(N, C, generator=g)).to(cuda)
+  bias_grad_from_rows(x, bias)
+  x64 = x.double()
+  err = (bias.grad.double() - (3.0 + x64.sum(0))).abs()
+  bound = N * 2.0 ** -23 * x64.abs().sum(0)
+  print("bias_grad_from_rows N=%d C=%d: max err %.3e, min bound %.3e, max err / bound %.3e"
+        % (N, C, float(err.max()), float(bound.min()), float((err / bound).max())))
+  assert bool((err <= bound).all())
