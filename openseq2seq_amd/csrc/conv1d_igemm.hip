@@ -38,7 +38,6 @@
 #include <array>
 #include <type_traits>
 #include <map>
-#include <mutex>
 #include <vector>
 
 namespace os2s {
@@ -1042,12 +1041,7 @@ static int launch_conv(hipStream_t stream, ConvArgs& a) {
   size_t epi_bytes = conv_epilogue_lds_bytes<BM, BN, NWIN, NTHR>();
   size_t smem = main_bytes > epi_bytes ? main_bytes : epi_bytes;
   if (smem > 160 * 1024) return OS2S_ERR_UNSUPPORTED;
-  static std::once_flag once;
-  static hipError_t attr_rc = hipSuccess;
-  std::call_once(once, [] {
-    attr_rc = hipFuncSetAttribute((const void*)conv1d_igemm_kernel<BM, BN, WM, WN, NWIN, XSINGLE>,
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  });
+  static const hipError_t attr_rc = opt_in_lds_160k({(const void*)conv1d_igemm_kernel<BM, BN, WM, WN, NWIN, XSINGLE>});
   if (attr_rc != hipSuccess) return OS2S_ERR_LAUNCH;
   const int grid = a.MT8 * 8 * a.NT;
   OS2S_LAUNCH((conv1d_igemm_kernel<BM, BN, WM, WN, NWIN, XSINGLE>), dim3(grid), dim3(NTHR), smem,
@@ -1120,37 +1114,13 @@ static int launch_conv_pp(hipStream_t stream, ConvArgs& a, void* workspace, size
   a.pp_tile = tile;
   a.pp_c256 = g_pp_cost[0]; a.pp_c2 = g_pp_cost[1]; a.pp_c3 = g_pp_cost[2]; a.pp_dgrad_pen = g_pp_cost[3];
   a.pp_prio = g_pp_prio;
-  static std::once_flag once;
-  static hipError_t attr_rc = hipSuccess;
-  static int ncu = 256;
-  std::call_once(once, [] {
-    attr_rc = hipFuncSetAttribute((const void*)conv1d_pp_kernel<false>,
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (attr_rc == hipSuccess)
-      attr_rc = hipFuncSetAttribute((const void*)conv1d_pp_kernel<true>,
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (attr_rc == hipSuccess)
-      attr_rc = hipFuncSetAttribute((const void*)conv1d_ppn_kernel<false>,
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (attr_rc == hipSuccess)
-      attr_rc = hipFuncSetAttribute((const void*)conv1d_ppn_kernel<true>,
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    int dev = 0, n = 0;
-    if (hipGetDevice(&dev) == hipSuccess &&
-        hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0)
-      ncu = n;
-  });
+  static const hipError_t attr_rc = opt_in_lds_160k({
+      (const void*)conv1d_pp_kernel<false>, (const void*)conv1d_pp_kernel<true>,
+      (const void*)conv1d_ppn_kernel<false>, (const void*)conv1d_ppn_kernel<true>});
   if (attr_rc != hipSuccess) return OS2S_ERR_LAUNCH;
-  a.ncu = ncu;
-  a.ws_slabs = nullptr; a.ws_cnt = nullptr; a.ws_nslabs = 0;
-  const size_t slab_bytes = (size_t)kSplitSlabFloats * 4;
-  if (workspace && workspace_bytes >= kSplitTicketBytes + 2 * slab_bytes) {
-    a.ws_cnt = reinterpret_cast<int*>(workspace);
-    a.ws_slabs = reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) + kSplitTicketBytes);
-    size_t n = (workspace_bytes - kSplitTicketBytes) / slab_bytes;
-    const size_t cap = (size_t)3 * ncu;
-    a.ws_nslabs = (int)(n < cap ? n : cap);
-  }
+  a.ncu = split_ncu();
+  const SplitWorkspace ws = split_carve(workspace, workspace_bytes, a.ncu);
+  a.ws_cnt = ws.tickets; a.ws_slabs = ws.slabs; a.ws_nslabs = ws.nslabs;
   // a forward launch whose lengths the host knows (no mask at all, or the caller's host copy): the tile
   // choice is evaluated here — the same pure function the device evaluates — and ONE kernel is enqueued
   if (tile < 0 && !a.out_len && (a.pp_ok2 || a.pp_ok3) &&
@@ -1440,12 +1410,7 @@ static int conv1x1_fwd_grouped_impl(os2s_stream_t stream, const os2s_conv_group_
   constexpr size_t kOP = BN * 2 + 16;
   const size_t epi_bytes = conv_epilogue_lds_bytes<BM, BN, 1, 256>();
   const size_t smem = main_bytes > epi_bytes ? main_bytes : epi_bytes;
-  static std::once_flag once;
-  static hipError_t attr_rc = hipSuccess;
-  std::call_once(once, [] {
-    attr_rc = hipFuncSetAttribute((const void*)conv1d_igemm_grouped_kernel<128, 128, 2, 2>,
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  });
+  static const hipError_t attr_rc = opt_in_lds_160k({(const void*)conv1d_igemm_grouped_kernel<128, 128, 2, 2>});
   if (attr_rc != hipSuccess) return OS2S_ERR_LAUNCH;
   OS2S_LAUNCH((conv1d_igemm_grouped_kernel<128, 128, 2, 2>), dim3(tiles), dim3(256), smem,
               (hipStream_t)stream, a, gt);

@@ -29,7 +29,6 @@
 #include <cstdlib>
 #include "os2s_common.hpp"
 #include "os2s_split_reduce.hpp"
-#include <mutex>
 
 namespace os2s {
 
@@ -1131,20 +1130,6 @@ __global__ __launch_bounds__(512, 2) void conv1d_wgrad1x1_pp_kernel(WgradArgs p,
 
 }  // namespace os2s
 
-// accumulate = 0 : dW = grad;  accumulate = 1 : dW += grad.
-// With a workspace (os2s_conv1d_workspace_bytes(), zero tickets, one per stream — the same
-// contract as os2s_conv1d_fwd_ws) the ping-pong kernel spreads small layers over the chip by
-// cutting the reduction; its result is deterministic and written by one owner per element.
-// The lockstep kernel (stride > 1, K = 1, narrow layers) splits the batch when accumulate = 1 and
-// the layer is too small to fill the chip otherwise: with a workspace the splits' partial dW go to
-// its slab area and are summed in split order (deterministic), without one they add into dW with
-// fp32 atomics.
-static int conv1d_wgrad_impl(os2s_stream_t stream, const uint16_t* x, long long x_row_stride,
-                             const uint16_t* dy, float* dw, const int32_t* in_len, int B,
-                             int Tin, int Cin, int Cout, int K, int stride, int dil,
-                             int padL, int Tout, int accumulate, void* workspace,
-                             size_t workspace_bytes);
-
 static int wgrad_pp_min_units() {   // experiment knob (A/B runs on one box); default 8
   static const int v = [] { const char* e = getenv("OS2S_WGRAD_PP_MIN_UNITS"); return e ? atoi(e) : 8; }();
   return v;
@@ -1182,74 +1167,88 @@ static os2s::StampReg r_wg_stamps("conv1d_wgrad", [](void* stamps, int mode) {
   g_wgrad_dbg_mode = mode;
 });
 
-extern "C" int os2s_conv1d_wgrad_ws(os2s_stream_t stream, const uint16_t* x, long long x_row_stride,
-                                    const uint16_t* dy, float* dw, const int32_t* in_len, int B,
-                                    int Tin, int Cin, int Cout, int K, int stride, int dil,
-                                    int padL, int Tout, int accumulate, void* workspace,
-                                    size_t workspace_bytes) {
-  return conv1d_wgrad_impl(stream, x, x_row_stride, dy, dw, in_len, B, Tin, Cin, Cout, K, stride,
-                           dil, padL, Tout, accumulate, workspace, workspace_bytes);
+// ---- the launch recipe shared by every entry point below ------------------------------------------------------------
+
+// The arguments of one K = 1, stride-1 problem dW[Cout, Cin] (+)= dY^T X over the rows (B, T, in_len): one group, one
+// split, whole units without atomics, no workspace, no stamps, the process-wide options. A launch site states only
+// what its launch has different.
+static os2s::WgradArgs wgrad_args(const uint16_t* x, long long x_ld, const uint16_t* dy, float* dw,
+                                  const int32_t* in_len, int B, int T, int Cin, int Cout, int accumulate) {
+  os2s::WgradArgs a{};               // every pointer null (part, ws_*, gx / gdy / gdw, dbg), every count 0
+  a.x = x; a.dy = dy; a.dw = dw; a.in_len = in_len; a.x_ld = x_ld;
+  a.B = B; a.Tin = T; a.Tout = T; a.Cin = Cin; a.Cout = Cout;
+  a.K = 1; a.stride = 1; a.dil = 1;
+  a.accumulate = accumulate ? 1 : 0;
+  a.NTP = 1; a.NSPLIT = 1; a.NG = 1;
+  a.xrows = 64; a.xrows_pad = 64;
+  a.ncu = 256; a.force_split = g_wgrad_split; a.xcd_order = g_wgrad_xcd;
+  return a;
 }
 
-extern "C" int os2s_conv1d_wgrad_ex(os2s_stream_t stream, const uint16_t* x, long long x_row_stride,
-                                    const uint16_t* dy, float* dw, const int32_t* in_len, int B,
-                                    int Tin, int Cin, int Cout, int K, int stride, int dil,
-                                    int padL, int Tout, int accumulate) {
-  return conv1d_wgrad_impl(stream, x, x_row_stride, dy, dw, in_len, B, Tin, Cin, Cout, K, stride,
-                           dil, padL, Tout, accumulate, nullptr, 0);
+// The units and the LDS geometry of the two kernels that work on (128 co, 128 ci, 4 taps) units: the ping-pong kernel
+// and the one-wave-per-SIMD kernel; xbuf_bytes = the kernel's X ring slot.
+static void wgrad_tap_quad_geometry(os2s::WgradArgs& a, int xbuf_bytes) {
+  using namespace os2s;
+  a.NCO = ceil_div(a.Cout, 128);
+  a.NCI = ceil_div(a.Cin, 128);
+  a.NTP = ceil_div(a.K, kWppTaps);
+  a.xrows = 63 + (kWppTaps - 1) * a.dil + 1;
+  a.xrows_pad = ceil_div(a.xrows, 4) * 4;
+  a.xbuf_bytes = xbuf_bytes;
+  a.steptab_bytes = ceil_div(a.B * ceil_div(a.Tout, 64) * 4, 16) * 16;
 }
 
-extern "C" int os2s_conv1d_wgrad(os2s_stream_t stream, const uint16_t* x,
-                                 const uint16_t* dy, float* dw,
-                                 const int32_t* in_len, int B, int Tin, int Cin,
-                                 int Cout, int K, int stride, int dil, int padL,
-                                 int Tout, int accumulate) {
-  return conv1d_wgrad_impl(stream, x, Cin, dy, dw, in_len, B, Tin, Cin, Cout, K, stride, dil,
-                           padL, Tout, accumulate, nullptr, 0);
+// Hands the split-unit workspace and the CU count to a launch of `units` units and returns its grid: an upper bound
+// (the split factor is decided on the device from the live length of the batch) — whole units, or up to 16 pieces
+// of each unit of the tail.
+static int wgrad_split_grid(os2s::WgradArgs& a, int units, void* workspace, size_t workspace_bytes) {
+  a.ncu = os2s::split_ncu();
+  const os2s::SplitWorkspace ws = os2s::split_carve(workspace, workspace_bytes, a.ncu);
+  a.ws_cnt = ws.tickets; a.ws_slabs = ws.slabs; a.ws_nslabs = ws.nslabs;
+  return units + os2s::split_tail_pieces(units, a.ncu, ws.nslabs);
 }
 
-// groups != nullptr (os2s_conv1d_wgrad_grouped_ws): ngroups layers of this one shape; only the ping-pong kernel takes
-// them — returns OS2S_ERR_UNSUPPORTED when the shape is not its (the caller then launches the layers one by one)
-static int conv1d_wgrad_impl_g(os2s_stream_t stream, const uint16_t* x, long long x_row_stride,
-                               const uint16_t* dy, float* dw, const int32_t* in_len, int B,
-                               int Tin, int Cin, int Cout, int K, int stride, int dil,
-                               int padL, int Tout, int accumulate, void* workspace,
-                               size_t workspace_bytes, const os2s_cwgrad_group_t* groups, int ngroups);
-
-static int conv1d_wgrad_impl(os2s_stream_t stream, const uint16_t* x, long long x_row_stride,
-                             const uint16_t* dy, float* dw, const int32_t* in_len, int B,
-                             int Tin, int Cin, int Cout, int K, int stride, int dil,
-                             int padL, int Tout, int accumulate, void* workspace,
-                             size_t workspace_bytes) {
-  return conv1d_wgrad_impl_g(stream, x, x_row_stride, dy, dw, in_len, B, Tin, Cin, Cout, K, stride, dil, padL, Tout,
-                             accumulate, workspace, workspace_bytes, nullptr, 1);
-}
-
-// Up to 8 convolution layers of ONE shape (Cin, Cout, K, dilation, padding) over one batch (B, T, lengths) in one
-// launch of the ping-pong weight-gradient kernel: the repeated sub-blocks of a Jasper block (conv_blocks.py:61-168:
-// `repeat` x the same tf.layers.conv1d) are 12 - 150 units of work each on 256 CUs — alone each is cut up to 16
-// ways along the reduction (fill, 256 KB slab per piece, one reducer per unit); together they fill the chip whole.
-extern "C" int os2s_conv1d_wgrad_grouped_ws(os2s_stream_t stream, const os2s_cwgrad_group_t* groups, int ngroups,
-                                            const int32_t* in_len, int B, int Tin, int Cin, int Cout, int K,
-                                            int stride, int dil, int padL, int Tout, int accumulate,
-                                            void* workspace, size_t workspace_bytes) {
-  OS2S_REQUIRE(groups && ngroups >= 1 && ngroups <= 8);
-  for (int i = 0; i < ngroups; ++i) OS2S_REQUIRE(groups[i].x && groups[i].dy && groups[i].dw);
-  for (int i = 1; i < ngroups; ++i) OS2S_REQUIRE(groups[i].x_row_stride == groups[0].x_row_stride);
-  int rc = OS2S_ERR_UNSUPPORTED;
-  if (ngroups > 1)
-    rc = conv1d_wgrad_impl_g(stream, groups[0].x, groups[0].x_row_stride, groups[0].dy, groups[0].dw, in_len, B, Tin,
-                             Cin, Cout, K, stride, dil, padL, Tout, accumulate, workspace, workspace_bytes, groups,
-                             ngroups);
-  if (rc != OS2S_ERR_UNSUPPORTED) return rc;
-  for (int i = 0; i < ngroups; ++i) {
-    rc = conv1d_wgrad_impl(stream, groups[i].x, groups[i].x_row_stride, groups[i].dy, groups[i].dw, in_len, B, Tin,
-                           Cin, Cout, K, stride, dil, padL, Tout, accumulate, workspace, workspace_bytes);
-    if (rc != OS2S_OK) return rc;
+// The table of K = 1 problems of a grouped launch, for tiles of edge x edge channels and nsplit units per tile. The
+// kernels select a group by reading every slot, so the unused ones repeat group 0. gt.total_units = the launch's units.
+static os2s::WgradGroupTable wgrad_group_table(const os2s_wgrad_group_t* groups, int ngroups, int edge, int nsplit) {
+  using namespace os2s;
+  WgradGroupTable gt;
+  gt.ngroups = ngroups;
+  int units = 0;
+  for (int i = 0; i < kMaxWgradGroups; ++i) {
+    const os2s_wgrad_group_t& s = groups[i < ngroups ? i : 0];
+    WgradGroup& g = gt.g[i];
+    g.x = s.x; g.dy = s.dy; g.dw = s.dw; g.x_ld = s.x_row_stride;
+    g.Cin = s.Cin; g.Cout = s.Cout; g.NCI = ceil_div(s.Cin, edge);
+    g.unit_begin = units;
+    if (i < ngroups) units += ceil_div(s.Cout, edge) * g.NCI * nsplit;
   }
+  gt.total_units = units;
+  return gt;
+}
+
+// Every launch of conv1d_wgrad1x1_pp_kernel: `units` 256 x 256 tiles (of a.NCO x a.NCI tiles of one problem when
+// gt.ngroups = 0, of the table's groups otherwise) and the pieces of the split tail.
+static int launch_wgrad1x1_pp(hipStream_t stream, os2s::WgradArgs a, const os2s::WgradGroupTable& gt, int units,
+                              void* workspace, size_t workspace_bytes) {
+  using namespace os2s;
+  static const hipError_t attr_rc = opt_in_lds_160k({(const void*)conv1d_wgrad1x1_pp_kernel});
+  if (attr_rc != hipSuccess) return OS2S_ERR_LAUNCH;
+  const int grid = wgrad_split_grid(a, units, workspace, workspace_bytes);
+  OS2S_LAUNCH(conv1d_wgrad1x1_pp_kernel, dim3(grid), dim3(512), (size_t)160 * 1024, stream, a, gt);
   return OS2S_OK;
 }
 
+// accumulate = 0 : dW = grad;  accumulate = 1 : dW += grad.
+// With a workspace (os2s_conv1d_workspace_bytes(), zero tickets, one per stream — the same
+// contract as os2s_conv1d_fwd_ws) the ping-pong kernel spreads small layers over the chip by
+// cutting the reduction; its result is deterministic and written by one owner per element.
+// The lockstep kernel (stride > 1, K = 1, narrow layers) splits the batch when accumulate = 1 and
+// the layer is too small to fill the chip otherwise: with a workspace the splits' partial dW go to
+// its slab area and are summed in split order (deterministic), without one they add into dW with
+// fp32 atomics.
+// groups != nullptr (os2s_conv1d_wgrad_grouped_ws): ngroups layers of this one shape; only the ping-pong kernel takes
+// them — returns OS2S_ERR_UNSUPPORTED when the shape is not its (the caller then launches the layers one by one)
 static int conv1d_wgrad_impl_g(os2s_stream_t stream, const uint16_t* x, long long x_row_stride,
                                const uint16_t* dy, float* dw, const int32_t* in_len, int B,
                                int Tin, int Cin, int Cout, int K, int stride, int dil,
@@ -1261,14 +1260,9 @@ static int conv1d_wgrad_impl_g(os2s_stream_t stream, const uint16_t* x, long lon
   OS2S_REQUIRE(B >= 0 && Tin >= 1 && Tout >= 1 && Cin >= 8 && Cout >= 8 && K >= 1);
   OS2S_REQUIRE(Cin % 8 == 0 && Cout % 8 == 0 && stride >= 1 && dil >= 1);
   if (B == 0) return OS2S_OK;
-  WgradArgs a;
-  a.x = x; a.dy = dy; a.dw = dw; a.in_len = in_len;
-  a.B = B; a.Tin = Tin; a.Tout = Tout; a.Cin = Cin; a.Cout = Cout; a.K = K;
-  a.stride = stride; a.dil = dil; a.padL = padL; a.x_ld = x_row_stride;
-  a.accumulate = accumulate ? 1 : 0;
-  a.part = nullptr; a.ws_slabs = nullptr; a.ws_cnt = nullptr; a.ws_nslabs = 0; a.ncu = 256; a.force_split = g_wgrad_split;
-  a.dbg = g_wgrad_dbg; a.dbg_mode = g_wgrad_dbg_mode; a.xcd_order = g_wgrad_xcd; a.NG = 1;
-  for (int i = 0; i < 8; ++i) { a.gx[i] = nullptr; a.gdy[i] = nullptr; a.gdw[i] = nullptr; }
+  WgradArgs a = wgrad_args(x, x_row_stride, dy, dw, in_len, B, Tin, Cin, Cout, accumulate);
+  a.Tout = Tout; a.K = K; a.stride = stride; a.dil = dil; a.padL = padL;
+  a.dbg = g_wgrad_dbg; a.dbg_mode = g_wgrad_dbg_mode;
   if (groups) {
     a.NG = ngroups;
     for (int i = 0; i < ngroups; ++i) { a.gx[i] = groups[i].x; a.gdy[i] = groups[i].dy; a.gdw[i] = groups[i].dw; }
@@ -1290,103 +1284,43 @@ static int conv1d_wgrad_impl_g(os2s_stream_t stream, const uint16_t* x, long lon
   // cycles per 64-row step at 2.11 GHz where the ping-pong kernel needs 2 400 at 1.75 GHz — 0.648 vs 0.612 ms
   // (profiles/r06_wgrad_sw_ablation.txt, DESIGN.md "Round-6 kernel work").
   if (sw_shape && g_wgrad_variant == 3 && !groups) {
-    a.NCO = ceil_div(Cout, 128);
-    a.NCI = ceil_div(Cin, 128);
-    a.NTP = ceil_div(K, kWppTaps);
-    a.NSPLIT = 1; a.steps_per_split = 0; a.use_atomic = 0;
-    a.xrows = 63 + (kWppTaps - 1) * dil + 1;
-    a.xrows_pad = ceil_div(a.xrows, 4) * 4;
-    a.xbuf_bytes = kSwXBuf;
-    a.steptab_bytes = ceil_div(B * ceil_div(Tout, 64) * 4, 16) * 16;
+    wgrad_tap_quad_geometry(a, kSwXBuf);
     const size_t smem = (size_t)kSwRing * (kSwYBuf + kSwXBuf) + a.steptab_bytes;
     if (smem <= 160 * 1024) {
-      static std::once_flag once_sw;
-      static hipError_t attr_rc = hipSuccess;
-      static int ncu = 256;
-      std::call_once(once_sw, [] {
-        attr_rc = hipFuncSetAttribute((const void*)conv1d_wgrad_sw_kernel<0>,
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+      static const hipError_t attr_rc = opt_in_lds_160k({
+          (const void*)conv1d_wgrad_sw_kernel<0>,
 #ifdef OS2S_SW_ABLATE
-        for (const void* k : {(const void*)conv1d_wgrad_sw_kernel<1>, (const void*)conv1d_wgrad_sw_kernel<2>,
-                              (const void*)conv1d_wgrad_sw_kernel<4>, (const void*)conv1d_wgrad_sw_kernel<8>,
-                              (const void*)conv1d_wgrad_sw_kernel<3>, (const void*)conv1d_wgrad_sw_kernel<5>})
-          if (attr_rc == hipSuccess) attr_rc = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+          (const void*)conv1d_wgrad_sw_kernel<1>, (const void*)conv1d_wgrad_sw_kernel<2>,
+          (const void*)conv1d_wgrad_sw_kernel<4>, (const void*)conv1d_wgrad_sw_kernel<8>,
+          (const void*)conv1d_wgrad_sw_kernel<3>, (const void*)conv1d_wgrad_sw_kernel<5>,
 #endif
-        int dev = 0, n = 0;
-        if (hipGetDevice(&dev) == hipSuccess &&
-            hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0)
-          ncu = n;
       });
       if (attr_rc != hipSuccess) return OS2S_ERR_LAUNCH;
-      a.ncu = ncu;
-      const size_t slab_bytes = (size_t)kSplitSlabFloats * 4;
-      if (workspace && workspace_bytes >= kSplitTicketBytes + 2 * slab_bytes) {
-        a.ws_cnt = reinterpret_cast<int*>(workspace);
-        a.ws_slabs = reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) + kSplitTicketBytes);
-        size_t n = (workspace_bytes - kSplitTicketBytes) / slab_bytes;
-        const size_t cap = (size_t)3 * ncu;
-        a.ws_nslabs = (int)(n < cap ? n : cap);
-      }
-      const int U = a.NCO * a.NCI * a.NTP;
-      const int r = U % ncu;
-      const int pieces = a.ws_nslabs < 16 * r ? a.ws_nslabs : 16 * r;
+      const int grid = wgrad_split_grid(a, pp_units, workspace, workspace_bytes);
 #ifdef OS2S_SW_ABLATE      // measurement build only (tools/sw_ablate.py): the stream with one ingredient removed
       switch (g_wgrad_sw_ablate) {
-        case 1: OS2S_LAUNCH(conv1d_wgrad_sw_kernel<1>, dim3(U + pieces), dim3(256), smem, (hipStream_t)stream, a); return OS2S_OK;
-        case 2: OS2S_LAUNCH(conv1d_wgrad_sw_kernel<2>, dim3(U + pieces), dim3(256), smem, (hipStream_t)stream, a); return OS2S_OK;
-        case 3: OS2S_LAUNCH(conv1d_wgrad_sw_kernel<3>, dim3(U + pieces), dim3(256), smem, (hipStream_t)stream, a); return OS2S_OK;
-        case 4: OS2S_LAUNCH(conv1d_wgrad_sw_kernel<4>, dim3(U + pieces), dim3(256), smem, (hipStream_t)stream, a); return OS2S_OK;
-        case 5: OS2S_LAUNCH(conv1d_wgrad_sw_kernel<5>, dim3(U + pieces), dim3(256), smem, (hipStream_t)stream, a); return OS2S_OK;
-        case 8: OS2S_LAUNCH(conv1d_wgrad_sw_kernel<8>, dim3(U + pieces), dim3(256), smem, (hipStream_t)stream, a); return OS2S_OK;
+        case 1: OS2S_LAUNCH(conv1d_wgrad_sw_kernel<1>, dim3(grid), dim3(256), smem, (hipStream_t)stream, a); return OS2S_OK;
+        case 2: OS2S_LAUNCH(conv1d_wgrad_sw_kernel<2>, dim3(grid), dim3(256), smem, (hipStream_t)stream, a); return OS2S_OK;
+        case 3: OS2S_LAUNCH(conv1d_wgrad_sw_kernel<3>, dim3(grid), dim3(256), smem, (hipStream_t)stream, a); return OS2S_OK;
+        case 4: OS2S_LAUNCH(conv1d_wgrad_sw_kernel<4>, dim3(grid), dim3(256), smem, (hipStream_t)stream, a); return OS2S_OK;
+        case 5: OS2S_LAUNCH(conv1d_wgrad_sw_kernel<5>, dim3(grid), dim3(256), smem, (hipStream_t)stream, a); return OS2S_OK;
+        case 8: OS2S_LAUNCH(conv1d_wgrad_sw_kernel<8>, dim3(grid), dim3(256), smem, (hipStream_t)stream, a); return OS2S_OK;
         default: break;
       }
 #endif
-      OS2S_LAUNCH(conv1d_wgrad_sw_kernel<0>, dim3(U + pieces), dim3(256), smem, (hipStream_t)stream, a);
+      OS2S_LAUNCH(conv1d_wgrad_sw_kernel<0>, dim3(grid), dim3(256), smem, (hipStream_t)stream, a);
       return OS2S_OK;
     }
   }
 
   if (pp_shape && g_wgrad_variant != 0 && (groups || g_wgrad_variant == 1 || pp_units >= wgrad_pp_min_units())) {
-    a.NCO = ceil_div(Cout, 128);
-    a.NCI = ceil_div(Cin, 128);
-    a.NTP = ceil_div(K, kWppTaps);
-    a.NSPLIT = 1; a.steps_per_split = 0; a.use_atomic = 0;
-    a.xrows = 63 + (kWppTaps - 1) * dil + 1;
-    a.xrows_pad = ceil_div(a.xrows, 4) * 4;
-    a.xbuf_bytes = 24 * 1024;                         // 3 DMA rounds of 8 waves x 1 KB
-    a.steptab_bytes = ceil_div(B * ceil_div(Tout, 64) * 4, 16) * 16;
+    wgrad_tap_quad_geometry(a, 24 * 1024);              // 3 DMA rounds of 8 waves x 1 KB
     const size_t smem = (size_t)2 * 64 * 256 + (size_t)3 * a.xbuf_bytes + a.steptab_bytes + (a.dbg ? 2 * 48 * 10 * 8 : 0);
     if (smem <= 160 * 1024) {
-      static std::once_flag once;
-      static hipError_t attr_rc = hipSuccess;
-      static int ncu = 256;
-      std::call_once(once, [] {
-        attr_rc = hipFuncSetAttribute((const void*)conv1d_wgrad_pp_kernel<false>,
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (attr_rc == hipSuccess)
-          attr_rc = hipFuncSetAttribute((const void*)conv1d_wgrad_pp_kernel<true>,
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        int dev = 0, n = 0;
-        if (hipGetDevice(&dev) == hipSuccess &&
-            hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0)
-          ncu = n;
-      });
+      static const hipError_t attr_rc = opt_in_lds_160k({(const void*)conv1d_wgrad_pp_kernel<false>,
+                                                         (const void*)conv1d_wgrad_pp_kernel<true>});
       if (attr_rc != hipSuccess) return OS2S_ERR_LAUNCH;
-      a.ncu = ncu;
-      const size_t slab_bytes = (size_t)kSplitSlabFloats * 4;
-      if (workspace && workspace_bytes >= kSplitTicketBytes + 2 * slab_bytes) {
-        a.ws_cnt = reinterpret_cast<int*>(workspace);
-        a.ws_slabs = reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) + kSplitTicketBytes);
-        size_t n = (workspace_bytes - kSplitTicketBytes) / slab_bytes;
-        const size_t cap = (size_t)3 * ncu;
-        a.ws_nslabs = (int)(n < cap ? n : cap);
-      }
-      // upper bound of the grid (the split factor is decided on the device from the live
-      // length of the batch): whole units, or up to 16 pieces of each unit of the tail
-      const int U = a.NG * a.NCO * a.NCI * a.NTP;
-      const int r = U % ncu;
-      int pieces = a.ws_nslabs < 16 * r ? a.ws_nslabs : 16 * r;
-      const int grid = U + pieces;
+      const int grid = wgrad_split_grid(a, a.NG * pp_units, workspace, workspace_bytes);
       if (a.dbg) {
         OS2S_LAUNCH(conv1d_wgrad_pp_kernel<true>, dim3(grid), dim3(512), smem, (hipStream_t)stream, a);
       } else {
@@ -1406,38 +1340,9 @@ static int conv1d_wgrad_impl_g(os2s_stream_t stream, const uint16_t* x, long lon
       (g_wgrad_variant == 2 || wgrad1x1_pp_auto(B, Tout, Cin, Cout, workspace != nullptr))) {
     a.NCO = ceil_div(Cout, 256);
     a.NCI = ceil_div(Cin, 256);
-    a.NTP = 1;
-    a.NSPLIT = 1; a.steps_per_split = 0; a.use_atomic = 0;
-    a.xrows = 64; a.xrows_pad = 64; a.xbuf_bytes = 0; a.steptab_bytes = 0;
-    static std::once_flag once1;
-    static hipError_t attr_rc1 = hipSuccess;
-    static int ncu1 = 256;
-    std::call_once(once1, [] {
-      attr_rc1 = hipFuncSetAttribute((const void*)conv1d_wgrad1x1_pp_kernel,
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      int dev = 0, n = 0;
-      if (hipGetDevice(&dev) == hipSuccess &&
-          hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0)
-        ncu1 = n;
-    });
-    if (attr_rc1 != hipSuccess) return OS2S_ERR_LAUNCH;
-    a.ncu = ncu1;
-    const size_t slab_bytes = (size_t)kSplitSlabFloats * 4;
-    if (workspace && workspace_bytes >= kSplitTicketBytes + 2 * slab_bytes) {
-      a.ws_cnt = reinterpret_cast<int*>(workspace);
-      a.ws_slabs = reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) + kSplitTicketBytes);
-      size_t n = (workspace_bytes - kSplitTicketBytes) / slab_bytes;
-      const size_t cap = (size_t)3 * ncu1;
-      a.ws_nslabs = (int)(n < cap ? n : cap);
-    }
-    const int U = a.NCO * a.NCI;
-    const int r = U % ncu1;
-    const int pieces = a.ws_nslabs < 16 * r ? a.ws_nslabs : 16 * r;
     WgradGroupTable none;
     none.ngroups = 0; none.total_units = 0;
-    OS2S_LAUNCH(conv1d_wgrad1x1_pp_kernel, dim3(U + pieces), dim3(512), (size_t)160 * 1024,
-                (hipStream_t)stream, a, none);
-    return OS2S_OK;
+    return launch_wgrad1x1_pp((hipStream_t)stream, a, none, a.NCO * a.NCI, workspace, workspace_bytes);
   }
 
   // ---- lockstep kernel ---------------------------------------------------------------------
@@ -1480,20 +1385,10 @@ static int conv1d_wgrad_impl_g(os2s_stream_t stream, const uint16_t* x, long lon
   a.xrows_pad = ceil_div(a.xrows, 4) * 4;
   const size_t smem = (size_t)2 * 64 * 2 * COT + (size_t)2 * a.xrows_pad * 256;
   if (smem > 160 * 1024) return OS2S_ERR_UNSUPPORTED;
-  static std::once_flag once2;
-  static hipError_t attr_rc2 = hipSuccess;
-  std::call_once(once2, [] {
-    if (hipFuncSetAttribute((const void*)conv1d_wgrad_kernel<2, 128>,
-                            hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
-        hipFuncSetAttribute((const void*)conv1d_wgrad_kernel<2, 256>,
-                            hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
-        hipFuncSetAttribute((const void*)conv1d_wgrad_kernel<1, 128>,
-                            hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
-        hipFuncSetAttribute((const void*)conv1d_wgrad_kernel<1, 256>,
-                            hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-      attr_rc2 = hipErrorUnknown;
-  });
-  if (attr_rc2 != hipSuccess) return OS2S_ERR_LAUNCH;
+  static const hipError_t attr_rc = opt_in_lds_160k({
+      (const void*)conv1d_wgrad_kernel<2, 128>, (const void*)conv1d_wgrad_kernel<2, 256>,
+      (const void*)conv1d_wgrad_kernel<1, 128>, (const void*)conv1d_wgrad_kernel<1, 256>});
+  if (attr_rc != hipSuccess) return OS2S_ERR_LAUNCH;
   const int nunits = a.NCO * a.NCI * a.NSPLIT;
   const int grid = ceil_div(nunits, 8) * 8 * a.NTP;
   if (wide) {
@@ -1515,6 +1410,57 @@ static int conv1d_wgrad_impl_g(os2s_stream_t stream, const uint16_t* x, long lon
   return OS2S_OK;
 }
 
+extern "C" int os2s_conv1d_wgrad_ws(os2s_stream_t stream, const uint16_t* x, long long x_row_stride,
+                                    const uint16_t* dy, float* dw, const int32_t* in_len, int B,
+                                    int Tin, int Cin, int Cout, int K, int stride, int dil,
+                                    int padL, int Tout, int accumulate, void* workspace,
+                                    size_t workspace_bytes) {
+  return conv1d_wgrad_impl_g(stream, x, x_row_stride, dy, dw, in_len, B, Tin, Cin, Cout, K, stride,
+                             dil, padL, Tout, accumulate, workspace, workspace_bytes, nullptr, 1);
+}
+
+extern "C" int os2s_conv1d_wgrad_ex(os2s_stream_t stream, const uint16_t* x, long long x_row_stride,
+                                    const uint16_t* dy, float* dw, const int32_t* in_len, int B,
+                                    int Tin, int Cin, int Cout, int K, int stride, int dil,
+                                    int padL, int Tout, int accumulate) {
+  return conv1d_wgrad_impl_g(stream, x, x_row_stride, dy, dw, in_len, B, Tin, Cin, Cout, K, stride,
+                             dil, padL, Tout, accumulate, nullptr, 0, nullptr, 1);
+}
+
+extern "C" int os2s_conv1d_wgrad(os2s_stream_t stream, const uint16_t* x,
+                                 const uint16_t* dy, float* dw,
+                                 const int32_t* in_len, int B, int Tin, int Cin,
+                                 int Cout, int K, int stride, int dil, int padL,
+                                 int Tout, int accumulate) {
+  return conv1d_wgrad_impl_g(stream, x, Cin, dy, dw, in_len, B, Tin, Cin, Cout, K, stride, dil,
+                             padL, Tout, accumulate, nullptr, 0, nullptr, 1);
+}
+
+// Up to 8 convolution layers of ONE shape (Cin, Cout, K, dilation, padding) over one batch (B, T, lengths) in one
+// launch of the ping-pong weight-gradient kernel: the repeated sub-blocks of a Jasper block (conv_blocks.py:61-168:
+// `repeat` x the same tf.layers.conv1d) are 12 - 150 units of work each on 256 CUs — alone each is cut up to 16
+// ways along the reduction (fill, 256 KB slab per piece, one reducer per unit); together they fill the chip whole.
+extern "C" int os2s_conv1d_wgrad_grouped_ws(os2s_stream_t stream, const os2s_cwgrad_group_t* groups, int ngroups,
+                                            const int32_t* in_len, int B, int Tin, int Cin, int Cout, int K,
+                                            int stride, int dil, int padL, int Tout, int accumulate,
+                                            void* workspace, size_t workspace_bytes) {
+  OS2S_REQUIRE(groups && ngroups >= 1 && ngroups <= 8);
+  for (int i = 0; i < ngroups; ++i) OS2S_REQUIRE(groups[i].x && groups[i].dy && groups[i].dw);
+  for (int i = 1; i < ngroups; ++i) OS2S_REQUIRE(groups[i].x_row_stride == groups[0].x_row_stride);
+  int rc = OS2S_ERR_UNSUPPORTED;
+  if (ngroups > 1)
+    rc = conv1d_wgrad_impl_g(stream, groups[0].x, groups[0].x_row_stride, groups[0].dy, groups[0].dw, in_len, B, Tin,
+                             Cin, Cout, K, stride, dil, padL, Tout, accumulate, workspace, workspace_bytes, groups,
+                             ngroups);
+  if (rc != OS2S_ERR_UNSUPPORTED) return rc;
+  for (int i = 0; i < ngroups; ++i) {
+    rc = conv1d_wgrad_impl_g(stream, groups[i].x, groups[i].x_row_stride, groups[i].dy, groups[i].dw, in_len, B, Tin,
+                             Cin, Cout, K, stride, dil, padL, Tout, accumulate, workspace, workspace_bytes, nullptr, 1);
+    if (rc != OS2S_OK) return rc;
+  }
+  return OS2S_OK;
+}
+
 
 // dW_i[co][ci] += sum_(b,t) dY_i[b,t,co] * X_i[b,t,ci] for up to 16 (X_i, dY_i, dW_i) over one ragged
 // batch, in one launch (the K = 1 weight gradients of the dense-residual branches of a block end).
@@ -1525,8 +1471,6 @@ extern "C" int os2s_conv1x1_wgrad_grouped(os2s_stream_t stream, const os2s_wgrad
   using namespace os2s;
   OS2S_REQUIRE(groups && ngroups >= 1 && ngroups <= kMaxWgradGroups && B >= 0 && T >= 1);
   if (B == 0) return OS2S_OK;
-  WgradGroupTable gt;
-  gt.ngroups = ngroups;
   int tiles = 0;
   for (int i = 0; i < ngroups; ++i) {
     const os2s_wgrad_group_t& s = groups[i];
@@ -1540,36 +1484,16 @@ extern "C" int os2s_conv1x1_wgrad_grouped(os2s_stream_t stream, const os2s_wgrad
   const int max_split = total_steps / 8 > 0 ? total_steps / 8 : 1;
   if (nsplit > max_split) nsplit = max_split;
   if (tiles >= 256 || nsplit < 1 || os2s_deterministic()) nsplit = 1;
-  WgradArgs a;
-  a.x = nullptr; a.dy = nullptr; a.dw = nullptr; a.in_len = in_len;
-  a.B = B; a.Tin = T; a.Tout = T; a.Cin = 0; a.Cout = 0; a.K = 1;
-  a.stride = 1; a.dil = 1; a.padL = 0; a.x_ld = 0; a.accumulate = 1;
-  a.part = nullptr; a.ws_slabs = nullptr; a.ws_cnt = nullptr; a.ws_nslabs = 0; a.ncu = 256; a.force_split = -1;
-  a.dbg = nullptr; a.dbg_mode = 0; a.xcd_order = g_wgrad_xcd; a.NG = 1;
-  a.NCO = 0; a.NCI = 0; a.NTP = 1;
+  WgradArgs a = wgrad_args(nullptr, 0, nullptr, nullptr, in_len, B, T, 0, 0, 1);   // the kernel takes x .. Cout from gt
+  a.force_split = -1;
   a.steps_per_split = ceil_div(total_steps, nsplit);
   a.NSPLIT = ceil_div(total_steps, a.steps_per_split);
   a.use_atomic = 1;
-  a.xrows = 64; a.xrows_pad = 64; a.xbuf_bytes = 0; a.steptab_bytes = 0;
-  int units = 0;
-  for (int i = 0; i < kMaxWgradGroups; ++i) {
-    const os2s_wgrad_group_t& s = groups[i < ngroups ? i : 0];
-    WgradGroup& g = gt.g[i];
-    g.x = s.x; g.dy = s.dy; g.dw = s.dw; g.x_ld = s.x_row_stride;
-    g.Cin = s.Cin; g.Cout = s.Cout; g.NCI = ceil_div(s.Cin, 128);
-    g.unit_begin = units;
-    if (i < ngroups) units += ceil_div(s.Cout, 128) * g.NCI * a.NSPLIT;
-  }
-  gt.total_units = units;
+  const WgradGroupTable gt = wgrad_group_table(groups, ngroups, 128, a.NSPLIT);
   const size_t smem = (size_t)2 * 64 * 2 * 128 + (size_t)2 * a.xrows_pad * 256;
-  static std::once_flag once;
-  static hipError_t attr_rc = hipSuccess;
-  std::call_once(once, [] {
-    attr_rc = hipFuncSetAttribute((const void*)conv1d_wgrad_grouped_kernel,
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  });
+  static const hipError_t attr_rc = opt_in_lds_160k({(const void*)conv1d_wgrad_grouped_kernel});
   if (attr_rc != hipSuccess) return OS2S_ERR_LAUNCH;
-  OS2S_LAUNCH(conv1d_wgrad_grouped_kernel, dim3(units), dim3(256), smem, (hipStream_t)stream, a, gt);
+  OS2S_LAUNCH(conv1d_wgrad_grouped_kernel, dim3(gt.total_units), dim3(256), smem, (hipStream_t)stream, a, gt);
   return OS2S_OK;
 }
 
@@ -1595,54 +1519,11 @@ extern "C" int os2s_conv1x1_wgrad_grouped_ws(os2s_stream_t stream, const os2s_wg
          (long long)s.Cout * 2 * 64 < (1ll << 30);
   }
   if (!pp) return os2s_conv1x1_wgrad_grouped(stream, groups, ngroups, in_len, B, T);
-  WgradGroupTable gt;
-  gt.ngroups = ngroups;
-  int units = 0;
-  for (int i = 0; i < kMaxWgradGroups; ++i) {
-    const os2s_wgrad_group_t& s = groups[i < ngroups ? i : 0];
-    WgradGroup& g = gt.g[i];
-    g.x = s.x; g.dy = s.dy; g.dw = s.dw; g.x_ld = s.x_row_stride;
-    g.Cin = s.Cin; g.Cout = s.Cout; g.NCI = ceil_div(s.Cin, 256);
-    g.unit_begin = units;
-    if (i < ngroups) units += ceil_div(s.Cout, 256) * g.NCI;
-  }
-  gt.total_units = units;
-  WgradArgs a;
-  a.x = gt.g[0].x; a.dy = gt.g[0].dy; a.dw = gt.g[0].dw; a.in_len = in_len;
-  a.B = B; a.Tin = T; a.Tout = T; a.Cin = gt.g[0].Cin; a.Cout = gt.g[0].Cout; a.K = 1;
-  a.stride = 1; a.dil = 1; a.padL = 0; a.x_ld = gt.g[0].x_ld;
-  a.accumulate = 1;
-  a.part = nullptr; a.ws_slabs = nullptr; a.ws_cnt = nullptr; a.ws_nslabs = 0; a.ncu = 256; a.force_split = g_wgrad_split;
-  a.dbg = nullptr; a.dbg_mode = 0; a.xcd_order = g_wgrad_xcd; a.NG = 1;
-  a.NCO = units; a.NCI = 1; a.NTP = 1;                   // U = NCO * NCI = all units of all groups
-  a.NSPLIT = 1; a.steps_per_split = 0; a.use_atomic = 0;
-  a.xrows = 64; a.xrows_pad = 64; a.xbuf_bytes = 0; a.steptab_bytes = 0;
-  static std::once_flag once;
-  static hipError_t attr_rc = hipSuccess;
-  static int ncu = 256;
-  std::call_once(once, [] {
-    attr_rc = hipFuncSetAttribute((const void*)conv1d_wgrad1x1_pp_kernel,
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    int dev = 0, n = 0;
-    if (hipGetDevice(&dev) == hipSuccess &&
-        hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0)
-      ncu = n;
-  });
-  if (attr_rc != hipSuccess) return OS2S_ERR_LAUNCH;
-  a.ncu = ncu;
-  const size_t slab_bytes = (size_t)kSplitSlabFloats * 4;
-  if (workspace_bytes >= kSplitTicketBytes + 2 * slab_bytes) {
-    a.ws_cnt = reinterpret_cast<int*>(workspace);
-    a.ws_slabs = reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) + kSplitTicketBytes);
-    size_t n = (workspace_bytes - kSplitTicketBytes) / slab_bytes;
-    const size_t cap = (size_t)3 * ncu;
-    a.ws_nslabs = (int)(n < cap ? n : cap);
-  }
-  const int r = units % ncu;
-  const int pieces = a.ws_nslabs < 16 * r ? a.ws_nslabs : 16 * r;
-  OS2S_LAUNCH(conv1d_wgrad1x1_pp_kernel, dim3(units + pieces), dim3(512), (size_t)160 * 1024,
-              (hipStream_t)stream, a, gt);
-  return OS2S_OK;
+  const WgradGroupTable gt = wgrad_group_table(groups, ngroups, 256, 1);
+  const os2s_wgrad_group_t& g0 = groups[0];
+  WgradArgs a = wgrad_args(g0.x, g0.x_row_stride, g0.dy, g0.dw, in_len, B, T, g0.Cin, g0.Cout, 1);
+  a.NCO = gt.total_units; a.NCI = 1;                     // U = NCO * NCI = all units of all groups
+  return launch_wgrad1x1_pp((hipStream_t)stream, a, gt, gt.total_units, workspace, workspace_bytes);
 }
 
 // The Dense weight gradients dw_i[Cout_i, Cin_i] (+)= dy_i^T x_i of up to 16 layers that see the
@@ -1654,55 +1535,15 @@ extern "C" int os2s_gemm_wgrad_grouped(os2s_stream_t stream, const os2s_wgrad_gr
                                        long long M, int accumulate, void* workspace, size_t workspace_bytes) {
   using namespace os2s;
   OS2S_REQUIRE(groups && ngroups >= 1 && ngroups <= kMaxWgradGroups && M >= 1 && M < (1ll << 30));
-  WgradGroupTable gt;
-  gt.ngroups = ngroups;
-  int units = 0;
-  for (int i = 0; i < kMaxWgradGroups; ++i) {
-    const os2s_wgrad_group_t& s = groups[i < ngroups ? i : 0];
+  for (int i = 0; i < ngroups; ++i) {
+    const os2s_wgrad_group_t& s = groups[i];
     OS2S_REQUIRE(s.x && s.dy && s.dw && s.Cin >= 128 && s.Cout >= 128 && s.Cin % 8 == 0 && s.Cout % 8 == 0);
     OS2S_REQUIRE(s.x_row_stride >= s.Cin && s.x_row_stride % 8 == 0);
     OS2S_REQUIRE(s.x_row_stride * 2 * 64 < (1ll << 30) && (long long)s.Cout * 2 * 64 < (1ll << 30));
-    WgradGroup& g = gt.g[i];
-    g.x = s.x; g.dy = s.dy; g.dw = s.dw; g.x_ld = s.x_row_stride;
-    g.Cin = s.Cin; g.Cout = s.Cout; g.NCI = ceil_div(s.Cin, 256);
-    g.unit_begin = units;
-    if (i < ngroups) units += ceil_div(s.Cout, 256) * g.NCI;
   }
-  gt.total_units = units;
-  WgradArgs a;
-  a.x = gt.g[0].x; a.dy = gt.g[0].dy; a.dw = gt.g[0].dw; a.in_len = nullptr;
-  a.B = 1; a.Tin = (int)M; a.Tout = (int)M; a.Cin = gt.g[0].Cin; a.Cout = gt.g[0].Cout; a.K = 1;
-  a.stride = 1; a.dil = 1; a.padL = 0; a.x_ld = gt.g[0].x_ld;
-  a.accumulate = accumulate ? 1 : 0;
-  a.part = nullptr; a.ws_slabs = nullptr; a.ws_cnt = nullptr; a.ws_nslabs = 0; a.ncu = 256; a.force_split = g_wgrad_split;
-  a.dbg = nullptr; a.dbg_mode = 0; a.xcd_order = g_wgrad_xcd; a.NG = 1;
-  a.NCO = units; a.NCI = 1; a.NTP = 1;                   // U = NCO * NCI = all units of all groups
-  a.NSPLIT = 1; a.steps_per_split = 0; a.use_atomic = 0;
-  a.xrows = 64; a.xrows_pad = 64; a.xbuf_bytes = 0; a.steptab_bytes = 0;
-  static std::once_flag once;
-  static hipError_t attr_rc = hipSuccess;
-  static int ncu = 256;
-  std::call_once(once, [] {
-    attr_rc = hipFuncSetAttribute((const void*)conv1d_wgrad1x1_pp_kernel,
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    int dev = 0, n = 0;
-    if (hipGetDevice(&dev) == hipSuccess &&
-        hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0)
-      ncu = n;
-  });
-  if (attr_rc != hipSuccess) return OS2S_ERR_LAUNCH;
-  a.ncu = ncu;
-  const size_t slab_bytes = (size_t)kSplitSlabFloats * 4;
-  if (workspace && workspace_bytes >= kSplitTicketBytes + 2 * slab_bytes) {
-    a.ws_cnt = reinterpret_cast<int*>(workspace);
-    a.ws_slabs = reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) + kSplitTicketBytes);
-    size_t n = (workspace_bytes - kSplitTicketBytes) / slab_bytes;
-    const size_t cap = (size_t)3 * ncu;
-    a.ws_nslabs = (int)(n < cap ? n : cap);
-  }
-  const int r = units % ncu;
-  const int pieces = a.ws_nslabs < 16 * r ? a.ws_nslabs : 16 * r;
-  OS2S_LAUNCH(conv1d_wgrad1x1_pp_kernel, dim3(units + pieces), dim3(512), (size_t)160 * 1024,
-              (hipStream_t)stream, a, gt);
-  return OS2S_OK;
+  const WgradGroupTable gt = wgrad_group_table(groups, ngroups, 256, 1);
+  const os2s_wgrad_group_t& g0 = groups[0];
+  WgradArgs a = wgrad_args(g0.x, g0.x_row_stride, g0.dy, g0.dw, nullptr, 1, (int)M, g0.Cin, g0.Cout, accumulate);
+  a.NCO = gt.total_units; a.NCI = 1;                     // U = NCO * NCI = all units of all groups
+  return launch_wgrad1x1_pp((hipStream_t)stream, a, gt, gt.total_units, workspace, workspace_bytes);
 }

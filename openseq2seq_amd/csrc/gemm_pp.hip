@@ -25,7 +25,6 @@
 // 256 x 256 tile moves 64 KB per step through the L2->LDS path (128 FLOP per byte — there is no
 // tap reuse as in the convolution), and a CU keeps only ~16 KB of such requests in flight; issued
 // as one burst per step the same traffic ran at 0.5x the speed.
-#include <mutex>
 #include <type_traits>
 
 #include "conv1d_common.hpp"
@@ -567,12 +566,7 @@ int launch_conv1x1_pp(hipStream_t stream, ConvArgs a, ConvGroupTable gt) {
   a.mtiles_per_b = ceil_div(a.Tout, 128);
   a.MT = a.B * a.mtiles_per_b;
   a.R = 128; a.Rpad = 128;
-  static std::once_flag once;
-  static hipError_t attr_rc = hipSuccess;
-  std::call_once(once, [] {
-    attr_rc = hipFuncSetAttribute((const void*)conv1x1_pp_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  160 * 1024);
-  });
+  static const hipError_t attr_rc = opt_in_lds_160k({(const void*)conv1x1_pp_kernel});
   if (attr_rc != hipSuccess) return OS2S_ERR_LAUNCH;
   const int pmax = ceil_div(a.MT, 2);
   const int nzero = a.out_len ? 0 : ceil_div(a.MT, kGppZeroWin) * gt.ngroups;
@@ -626,19 +620,9 @@ static int gemm_nt_impl(os2s_stream_t stream, const uint16_t* A, long long lda, 
   const size_t main_bytes = (size_t)5 * 256 * 128;    // A ring of 3 + W ring of 2 = 160 KB
   const size_t epi_bytes = conv_epilogue_lds_bytes<128, 256, 2, 512>();
   const size_t smem = main_bytes > epi_bytes ? main_bytes : epi_bytes;
-  static std::once_flag once;
-  static hipError_t attr_rc = hipSuccess;
-  static int ncu = 256;
-  std::call_once(once, [] {
-    attr_rc = hipFuncSetAttribute((const void*)gemm_pp_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  160 * 1024);
-    int dev = 0, n = 0;
-    if (hipGetDevice(&dev) == hipSuccess &&
-        hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0)
-      ncu = n;
-  });
+  static const hipError_t attr_rc = opt_in_lds_160k({(const void*)gemm_pp_kernel});
   if (attr_rc != hipSuccess) return OS2S_ERR_LAUNCH;
-  a.ncu = ncu;
+  const int ncu = a.ncu = split_ncu();
   // ---- the 160-row tile (gemm_pp_cols_kernel<5>): when the 256-row tiling is ONE round that leaves more than 40 % of
   // the CUs without a tile and 160-row tiles still fit one round; per-window statistics keep the 128-row windows
   {
@@ -647,12 +631,7 @@ static int gemm_nt_impl(os2s_stream_t stream, const uint16_t* A, long long lda, 
     // (not for launches of a few tiles — nothing to gain — and not while a test forces the tail split of the 256-row tile)
     const bool fits = !stats && u160 <= ncu && u256 * 10 <= ncu * 6 && u160 > u256 && u256 >= 32 && g_gemm_split <= 0;
     if (g_gemm_tile == 160 ? (!stats && u160 <= 4 * ncu) : (g_gemm_tile == 0 && fits)) {
-      static std::once_flag once5;
-      static hipError_t rc5 = hipSuccess;
-      std::call_once(once5, [] {
-        rc5 = hipFuncSetAttribute((const void*)gemm_pp_cols_kernel<5>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  160 * 1024);
-      });
+      static const hipError_t rc5 = opt_in_lds_160k({(const void*)gemm_pp_cols_kernel<5>});
       if (rc5 != hipSuccess) return OS2S_ERR_LAUNCH;
       const size_t main5 = (size_t)3 * 160 * 128 + (size_t)3 * 256 * 128;
       const size_t epi5 = conv_epilogue_lds_bytes<160, 256, 1, 512>();
@@ -665,13 +644,11 @@ static int gemm_nt_impl(os2s_stream_t stream, const uint16_t* A, long long lda, 
   const int U = mblocks * a.NT;
   const int r = U % ncu;
   int f = 1;
-  const size_t slab_bytes = (size_t)kSplitSlabFloats * 4;
-  if (r > 0 && workspace && workspace_bytes >= kSplitTicketBytes + 2 * slab_bytes) {
-    a.ws_cnt = reinterpret_cast<int*>(workspace);
-    a.ws_slabs = reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) + kSplitTicketBytes);
-    size_t n = (workspace_bytes - kSplitTicketBytes) / slab_bytes;
-    const size_t cap = (size_t)3 * ncu;
-    a.ws_nslabs = (int)(n < cap ? n : cap);
+  if (r > 0) {
+    const SplitWorkspace ws = split_carve(workspace, workspace_bytes, ncu);
+    a.ws_cnt = ws.tickets; a.ws_slabs = ws.slabs; a.ws_nslabs = ws.nslabs;
+  }
+  if (a.ws_nslabs > 0) {                                // a tail, and a workspace to cut it in
     int fmax = a.nchunks / 8;                           // >= 8 steps per piece
     fmax = fmax > 16 ? 16 : fmax;
     // a round of whole units: ~1.05 us per 64-deep step + ~10 us of fill and epilogue
