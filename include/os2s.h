@@ -1035,6 +1035,38 @@ int os2s_tts_spectrogram(os2s_stream_t stream, const float* signal, long long si
                          float pad_mel, float pad_mag);
 
 /* ------------------------------------------------------------------------
+ * Griffin-Lim vocoder: griffin_lim (models/text2speech.py:182-198) as called by save_audio (:111-179) from
+ * Text2Speech.finalize_inference (:339-413), with librosa.stft / istft at their defaults: hop = n_fft/4,
+ * periodic Hann(n_fft), center=True with reflect padding, istft divided by the window sum of squares and
+ * trimmed by n_fft/2 at each end. Per utterance b with T_b = lengths[b] frames, K = n_fft/2 + 1 bins:
+ *   M  = clip(mag, 0, clip_max) ** power        (save_audio :148-152; clip_max <= 0: no clipping)
+ *   x  = istft(M * exp(2 pi i phase0));  n_iters times:  X = stft(x), x = istft(M * X / |X|)   (X / |X| = 1 where |X| == 0)
+ * All arithmetic is fp32 (librosa's own: complex64) on the fp32-input matrix instruction; no atomics, so a run is
+ * bit-reproducible and an utterance's result does not depend on its batch-mates.
+ *   mag, phase0  fp32 [B, T_max, K]; phase0 in [0, 1) (the reference draws np.random.rand)
+ *   lengths      int32 [B] (device), 4 <= T_b <= T_max; an utterance outside that range is left zero
+ *   basis_analysis  fp32 [n_fft, 2 * Kp], Kp = os2s_griffin_lim_kpad(n_fft): column k < K = cos(2 pi k n / n_fft) *
+ *                window[n], column Kp + k = -sin(..) * window[n], all other columns zero
+ *   basis_synthesis fp32 [2 * Kp, 4, hopP], hopP = os2s_griffin_lim_hop_pad(n_fft): row k, block r, column i < hop =
+ *                w_k / n_fft * cos(2 pi k n / n_fft) * window[n] at n = r * hop + i, row Kp + k the same with -sin;
+ *                w_k = 1 for DC and Nyquist, else 2; all other entries zero
+ *   inv_wss      fp32 [3, hopP]: 1 / sum of window^2 over the frames that cover the first kept hop block (frames
+ *                0..2), an interior one (four frames) and the last one (frames T_b-3 .. T_b-1)
+ *   out          fp32 [B, hop * (T_max - 1)]; utterance b fills the first hop * (T_b - 1) samples, the rest is zero
+ *   flags        int32 [B]: 1 when a magnitude of the utterance or a sample of its first istft is not finite
+ *                (the reference's np.isfinite check, :190-192), else 0
+ *   workspace    os2s_griffin_lim_workspace_bytes(B, T_max, n_fft) bytes: spectra and the second signal buffer
+ * Requirements: n_fft % 8 == 0, 64 <= n_fft <= 2048, T_max >= 4, B <= 65535.
+ * ---------------------------------------------------------------------- */
+int os2s_griffin_lim_kpad(int n_fft);
+int os2s_griffin_lim_hop_pad(int n_fft);
+size_t os2s_griffin_lim_workspace_bytes(int B, int T_max, int n_fft);
+int os2s_griffin_lim(os2s_stream_t stream, const float* mag, const int32_t* lengths, const float* phase0,
+                     const float* basis_analysis, const float* basis_synthesis, const float* inv_wss,
+                     int B, int T_max, int n_fft, float power, float clip_max, int n_iters, float* out,
+                     int32_t* flags, void* workspace, size_t workspace_bytes);
+
+/* ------------------------------------------------------------------------
  * Depthwise half of tf.layers.separable_conv1d (layer type "sep_conv1d",
  * parts/cnns/conv_blocks.py:11-16; QuartzNet): y[b,t,c] = sum_k x[b, t*stride + k*dil -
  * padL, c] * w[k,c]; x, y bf16 channels-last, w fp32 [K, C] (TF depthwise_kernel [K, C, 1]),

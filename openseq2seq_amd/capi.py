@@ -1810,6 +1810,28 @@ def tts_spectrogram(signal, n_samples, window, *, n_fft, hop, T, mag_power, data
   return mel, mag
 
 
+def griffin_lim_pads(n_fft):
+  """(Kp, hopP): the padded bin / hop counts of the Griffin-Lim basis layouts (include/os2s.h)."""
+  return int(_lib.C.os2s_griffin_lim_kpad(n_fft)), int(_lib.C.os2s_griffin_lim_hop_pad(n_fft))
+
+
+def griffin_lim(mag, lengths, phase0, basis_analysis, basis_synthesis, inv_wss, *, n_fft, n_iters, power=1.0,
+                clip_max=0.0):
+  """mag / phase0 fp32 [B, T, n_fft/2 + 1], lengths int32 [B] -> (signal fp32 [B, hop * (T - 1)], flags int32 [B])."""
+  B, T, K = mag.shape
+  if K != n_fft // 2 + 1 or phase0.shape != mag.shape or lengths.shape != (B,):
+    raise ValueError("griffin_lim: mag / phase0 must be [B, T, n_fft/2 + 1] and lengths [B]")
+  f32, dev = torch.float32, mag.device
+  out = torch.empty((B, (n_fft // 4) * (T - 1)), dtype=f32, device=dev)
+  flags = torch.empty((B,), dtype=torch.int32, device=dev)
+  nbytes = int(_lib.C.os2s_griffin_lim_workspace_bytes(B, T, n_fft))
+  ws = torch.empty((max(nbytes, 16),), dtype=torch.uint8, device=dev)
+  _lib.C.os2s_griffin_lim(_stream(), _ptr(mag, f32), _ptr(lengths, torch.int32), _ptr(phase0, f32),
+                          _ptr(basis_analysis, f32), _ptr(basis_synthesis, f32), _ptr(inv_wss, f32), B, T, n_fft,
+                          float(power), float(clip_max), int(n_iters), _ptr(out), _ptr(flags), _ptr(ws), nbytes)
+  return out, flags
+
+
 # --------------------------------------------------------------------------
 # depthwise conv1d (sep_conv1d)
 # --------------------------------------------------------------------------

@@ -4,7 +4,9 @@ per-utterance arithmetic runs on the GPU (csrc/tts_features.hip, os2s_tts_spectr
 the host prepares the constant tables: the periodic Hann window librosa.stft uses by default
 (scipy.signal.get_window('hann', n_fft, fftbins=True)) and the mel filterbank
 librosa.filters.mel(sr, n_fft, n_mels, htk=True, norm=None) (mel_type 'htk', :160-172) or the
-Slaney / area-normalised one (mel_type 'slaney')."""
+Slaney / area-normalised one (mel_type 'slaney'). `inverse_mel` (:236-284) is the way back from a
+predicted log-mel spectrogram to magnitudes that the infer mode's Griffin-Lim export reads: host NumPy, one small
+product per utterance, as in the reference."""
 from __future__ import absolute_import, division, print_function
 
 import math
@@ -30,6 +32,28 @@ def mel_basis_htk(sample_freq, n_fft, n_mels, fmin=0.0, fmax=None):
   for i in range(n_mels):
     w[i] = np.maximum(0, np.minimum(-ramps[i] / fdiff[i], ramps[i + 2] / fdiff[i + 1]))
   return w.astype(np.float32)
+
+
+def normalize(features, mean, std):
+  return (features - mean) / std
+
+
+def denormalize(features, mean, std):
+  return features * std + mean
+
+
+def inverse_mel(log_mel_spec, fs=22050, n_fft=1024, n_mels=80, power=2., feature_normalize=False, mean=0, std=1,
+                mel_basis=None, htk=True, norm=None):
+  """speech_utils.py:236-284: magnitude spectrogram [time, n_fft/2 + 1] from a log-mel one by the transposed mel
+  basis: exp(denormalised log-mel) . mel_basis, then ** (1 / power). `mel_basis` [n_mels, n_fft/2 + 1]; when
+  None it is built as librosa.filters.mel(fs, n_fft, n_mels, htk=htk, norm=norm) would be."""
+  if mel_basis is None:
+    mel_basis = (mel_basis_htk if htk else mel_basis_slaney)(fs, n_fft, n_mels)
+  if feature_normalize:
+    log_mel_spec = denormalize(log_mel_spec, mean, std)
+  mel_spec = np.exp(log_mel_spec)
+  mag_spec = np.dot(mel_spec, mel_basis)
+  return np.power(mag_spec, 1. / power)
 
 
 class TTSFeatureFrontEnd(object):

@@ -9,7 +9,9 @@ exp(log_mag) when exp_mag (:486-488); pad_EOS appends frames carrying log(data_m
 data_min and stop token 1 and the returned lengths include them (:494-545). The character
 vocabulary is the file + 3 special symbols (:137-148). The csv/wav reading path is
 host-side; feature extraction itself is the GPU kernel behind
-data/text2speech/speech_utils.py. `synthetic_batch` draws SURVEY.md 8d's cfg-5 workload."""
+data/text2speech/speech_utils.py. `synthetic_batch` draws SURVEY.md 8d's cfg-5 workload.
+`get_magnitude_spec` (:656-715) turns a predicted spectrogram back into the magnitudes the Griffin-Lim export
+of the infer mode reads (models/text2speech.py)."""
 from __future__ import absolute_import, division, print_function
 
 import io
@@ -19,6 +21,8 @@ import numpy as np
 import torch
 
 from ..data_layer import DataLayer
+from ..speech2text.speech_utils import mel_basis_slaney
+from .speech_utils import denormalize, inverse_mel, mel_basis_htk
 
 
 class Text2SpeechDataLayer(DataLayer):
@@ -57,6 +61,14 @@ class Text2SpeechDataLayer(DataLayer):
     p['src_vocab_size'] = len(p['char2idx'])
     self._both = p['output_type'] == "both"
     self._exp_mag = bool(p.get('exp_mag', False)) and self._both
+    self._mel = "mel" in p['output_type']
+    # text2speech.py:137-142: LJSpeech 22.05 kHz with n_fft 1024 unless set, M-AILABS 16 kHz with n_fft 800
+    if p.get('dataset') == 'LJ':
+      self._sampling_rate, self._n_fft = 22050, p.get('n_fft', 1024)
+    else:
+      self._sampling_rate, self._n_fft = 16000, 800
+    self.max_normalization = p.get('max_normalization', False)
+    self._mel_basis_cache = None
 
   def build_graph(self):
     return self
@@ -64,6 +76,60 @@ class Text2SpeechDataLayer(DataLayer):
   @property
   def input_tensors(self):
     return {}
+
+  @property
+  def sampling_rate(self):
+    return self._sampling_rate
+
+  @property
+  def n_fft(self):
+    return self._n_fft
+
+  @property
+  def _mel_basis(self):
+    """librosa.filters.mel of the configuration (text2speech.py:214-229), [n_mels, n_fft/2 + 1]; None for a
+    magnitude-only layer. Built on first use."""
+    if not (self._mel or self._both):
+      return None
+    if self._mel_basis_cache is None:
+      n_mels = self.feature_sizes()[0]
+      make = mel_basis_slaney if self.params.get('mel_type', 'htk') == 'slaney' else mel_basis_htk
+      self._mel_basis_cache = make(self._sampling_rate, self._n_fft, n_mels, fmax=self.params.get('fmax', None))
+    return self._mel_basis_cache
+
+  def get_magnitude_spec(self, spectrogram, is_mel=False):
+    """text2speech.py:656-715: the energy magnitude spectrogram [time, n_fft/2 + 1] of a model output
+    [time, features]. A mel layer (or the mel half of a "both" layer, is_mel=True) goes through inverse_mel; a
+    magnitude output is denormalised, padded with data_min up to n_fft/2 + 1 bins and scaled by 1 / mag_power
+    (and exponentiated when the layer stores log magnitudes)."""
+    p = self.params
+    spectrogram = np.asarray(spectrogram).astype(float)
+    mean, std = p.get("feature_normalize_mean", 0.), p.get("feature_normalize_std", 1.)
+    if self._mel or (is_mel and self._both):
+      slaney = p.get('mel_type', 'htk') == 'slaney'
+      return inverse_mel(spectrogram, fs=self._sampling_rate, n_fft=self._n_fft, n_mels=self.feature_sizes()[0],
+                         power=p.get('mag_power', 2), feature_normalize=p["feature_normalize"], mean=mean, std=std,
+                         mel_basis=self._mel_basis, htk=not slaney, norm=1 if slaney else None)
+    if p["feature_normalize"]:
+      spectrogram = denormalize(spectrogram, mean, std)
+    n_feats = p['num_audio_features']
+    data_min = p.get("data_min", 1e-5)
+    if self._both:
+      n_feats = n_feats["magnitude"]
+      if isinstance(data_min, dict):
+        data_min = data_min["magnitude"]
+      if not self._exp_mag:
+        data_min = np.log(data_min)
+    else:
+      data_min = np.log(data_min)
+    n_bins = self._n_fft // 2 + 1
+    if n_feats < n_bins:
+      spectrogram = np.pad(spectrogram, ((0, 0), (0, n_bins - spectrogram.shape[1])), "constant",
+                           constant_values=data_min)
+    mag_spec = spectrogram * 1.0 / p.get('mag_power', 2)
+    if not self._both and not self._exp_mag:
+      mag_spec = np.exp(mag_spec)
+    return mag_spec
 
   def feature_sizes(self):
     naf = self.params['num_audio_features']
