@@ -1,6 +1,5 @@
 // Free-running Tacotron2 decoding (eval / infer) and the small-code kernels of the location-sensitive decoder's
-// training pass, gfx950. Included at the end of attn_decoder.hip (one translation unit: the training driver
-// launches these kernels, and they share its argument structs).
+// training pass (launched by attn_decoder.hip through the functions in attn_decoder_common.hpp), gfx950.
 //
 // Reference: Tacotron2Decoder._decode in eval / infer mode (open_seq2seq/decoders/tacotron2_decoder.py:378-428)
 // = tf.contrib.seq2seq.dynamic_decode(TacotronDecoder(helper = TacotronHelper), impute_finished = False,
@@ -32,7 +31,10 @@
 // The stop decision stays on the device: the launch that sees the last sample finish writes the step count to
 // state[1]; every later launch returns at once, so the host may enqueue steps ahead and poll every N steps —
 // the result does not depend on N.
-#pragma once
+#include <cstdio>
+#include <cstdlib>
+#include "attn_decoder_common.hpp"
+#include "rnn_tile.hpp"
 
 namespace os2s {
 
@@ -45,25 +47,6 @@ namespace os2s {
 #else
 #define TI_WLOAD(p) (*(p))
 #endif
-
-struct TiLstm {
-  int B, H, K, Ka;                   // K = Ka + Kb input columns
-  const bf16_t* in_a; long long lda; // row b: in_a + b * lda  (Ka columns; Ka == 0: unused)
-  const bf16_t* in_b; long long ldb; // row b: in_b + b * ldb  (K - Ka columns)
-  const void* w;                     // [4H, K] e4m3 (FP8) or bf16
-  const float* scale;                // [4H] row scales (FP8)
-  const float* bias;                 // [4H] or null
-  float forget_bias;
-  const float* c_prev; long long ldc_prev;   // row b at c_prev + b * ldc_prev, or null (zeros)
-  float* c_out; long long ldc_out;
-  bf16_t* h1; long long ldh1;        // h destinations (row b at h + b * ld; either may be null)
-  bf16_t* h2; long long ldh2;        //   h2 takes the output dropout (training: the cell's OUTPUT, not its state)
-  const int32_t* state;              // state[1] != 0: decoding has ended (null: no stop flag — the training pass)
-  // training pass (os2s_attn_decoder_fwd): input projection of the step, saved gates, output dropout
-  const bf16_t* gx; long long ldgx;  // row b: gx + b * ldgx, [4H] (or null)
-  bf16_t* gates; long long ldgates;  // row b: gates + b * ldgates, [4H] = i, f, g, o activations (or null)
-  float out_keep; unsigned long long out_seed; long long drop_t, drop_T;   // element index ((b * T + t) * H + j)
-};
 
 // rows of a 16-row tile: r = 4 * unit + gate, so that after the MFMA (acc[i] = row 4 * (lane >> 4) + i,
 // column lane & 15) a lane holds the four gates of ONE (unit, sample). MT row tiles (4 * MT units) x NT
@@ -242,7 +225,6 @@ __device__ __forceinline__ float row16_sum(float x) {
   x += dpp_mov<0x128, 0xf>(0.f, x);   // row_ror:8
   return x;
 }
-
 
 // ---- context + frame ----------------------------------------------------------------------------------
 struct TiTail {
@@ -751,6 +733,11 @@ __global__ __launch_bounds__(kAttnThreads) void ti_scores_kernel(AdAttn p, AdLoc
   else if (!(q.dbg & 2)) ti_scores_part(p, x, lds_raw);
 }
 
+__global__ __launch_bounds__(kAttnThreads) void ad_loc_scores_mfma_kernel(AdAttn p, AdLoc x) {
+  extern __shared__ float lds_raw[];
+  ti_scores_part(p, x, lds_raw);
+}
+
 }  // namespace os2s
 
 using namespace os2s;
@@ -835,6 +822,19 @@ static int ti_launch_cell(hipStream_t stream, const TiLstm& c, bool fp8) {
   return fp8 ? ti_launch_lstm<true>(stream, c) : ti_launch_lstm<false>(stream, c);
 }
 
+// layer l, step t, training or free-running: cell state rows, h1 = recurrent slot of the next step's input row, h2
+// = the layer's output row (the layer above, or y_top)
+static void ti_fill_cell_state(TiLstm& c, const os2s_attn_decoder_t* d, int l, int t) {
+  const int T = d->T, H = d->H, M = d->M, L = d->L;
+  const int Kc = l == 0 ? M + H : 2 * H;
+  c.B = d->B; c.H = H; c.forget_bias = d->forget_bias;
+  c.c_prev = t > 0 ? d->c_seq[l] + (long long)(t - 1) * H : nullptr; c.ldc_prev = (long long)T * H;
+  c.c_out = d->c_seq[l] + (long long)t * H; c.ldc_out = (long long)T * H;
+  c.h1 = (bf16_t*)d->cat[l] + (long long)(t + 1) * Kc + (l == 0 ? M : H); c.ldh1 = (long long)(T + 1) * Kc;
+  if (l == L - 1) { c.h2 = (bf16_t*)d->y_top + (long long)t * d->y_top_ts; c.ldh2 = d->y_top_bs; }
+  else { c.h2 = (bf16_t*)d->cat[l + 1] + (long long)t * 2 * H; c.ldh2 = (long long)(T + 1) * 2 * H; }
+}
+
 extern "C" int os2s_tacotron_infer_steps(os2s_stream_t stream_, const os2s_tacotron_infer_t* x, int t_begin,
                                          int t_end) {
   const int rc = ti_check(x);
@@ -867,9 +867,8 @@ extern "C" int os2s_tacotron_infer_steps(os2s_stream_t stream_, const os2s_tacot
   q.wstop = (const bf16_t*)x->wstop; q.bstop = x->bstop; q.mh = x->mh;
   q.x_seq = (bf16_t*)x->x_seq; q.mel = (bf16_t*)x->mel; q.stop = x->stop; q.state = x->state;
   if (t_begin == 0) {
-    const int n = (d->loc_k + 1) * d->U;
-    OS2S_LAUNCH(ad_fold_location_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, stream, d->conv_w, d->conv_b,
-                d->dense_w, d->loc_k, d->loc_f, d->U, d->loc_ws);
+    const int r0 = ad_launch_fold_location(stream, d);
+    if (r0 != OS2S_OK) return r0;
     TiTail q0 = q;
     q0.first = 1;
     at.t = 0;
@@ -879,8 +878,8 @@ extern "C" int os2s_tacotron_infer_steps(os2s_stream_t stream_, const os2s_tacot
   for (int t = t_begin; t < t_end; ++t) {
     for (int l = 0; l < L; ++l) {
       TiLstm c;
-      c.B = B; c.H = H; c.forget_bias = d->forget_bias; c.state = x->state;
-      c.gx = nullptr; c.ldgx = 0; c.gates = nullptr; c.ldgates = 0; c.out_keep = 1.f; c.out_seed = 0; c.drop_t = 0; c.drop_T = 0;
+      ti_fill_cell_state(c, d, l, t);
+      c.state = x->state; c.gx = nullptr; c.ldgx = 0; c.gates = nullptr; c.ldgates = 0; c.out_keep = 1.f; c.out_seed = 0; c.drop_t = 0; c.drop_T = 0;
       if (l == 0) {
         c.K = P + M + H; c.Ka = P;
         c.in_a = (const bf16_t*)x->x_seq + (long long)t * P; c.lda = (long long)(T + 1) * P;
@@ -893,13 +892,6 @@ extern "C" int os2s_tacotron_infer_steps(os2s_stream_t stream_, const os2s_tacot
         c.w = fp8 ? (const void*)d->wcat8[1] : (const void*)d->wcat[1]; c.scale = d->wcat8_scale[1];
         c.bias = d->bias[1];
       }
-      c.c_prev = t > 0 ? d->c_seq[l] + (long long)(t - 1) * H : nullptr; c.ldc_prev = (long long)T * H;
-      c.c_out = d->c_seq[l] + (long long)t * H; c.ldc_out = (long long)T * H;
-      // recurrent slot of the next step's input row
-      const int Kc = l == 0 ? M + H : 2 * H;
-      c.h1 = (bf16_t*)d->cat[l] + (long long)(t + 1) * Kc + (l == 0 ? M : H); c.ldh1 = (long long)(T + 1) * Kc;
-      if (l == L - 1) { c.h2 = (bf16_t*)d->y_top + (long long)t * d->y_top_ts; c.ldh2 = d->y_top_bs; }
-      else { c.h2 = (bf16_t*)d->cat[l + 1] + (long long)t * 2 * H; c.ldh2 = (long long)(T + 1) * 2 * H; }
       const int r2 = fp8 ? ti_launch_lstm<true>(stream, c) : ti_launch_lstm<false>(stream, c);
       if (r2 != OS2S_OK) return r2;
     }
@@ -915,235 +907,7 @@ extern "C" int os2s_tacotron_infer_steps(os2s_stream_t stream_, const os2s_tacot
 // for the cells (+ input projection of the step, saved gates, output dropout) and ti_scores_part for the scores:
 // 13.3 -> ~8.7 us per cell launch and 10.4 -> ~6.5 us per score launch of a Tacotron2 decoder step. OS2S_AD_FAST=0
 // keeps the round-3 kernels.
-namespace os2s {
-__global__ __launch_bounds__(kAttnThreads) void ad_loc_scores_mfma_kernel(AdAttn p, AdLoc x) {
-  extern __shared__ float lds_raw[];
-  ti_scores_part(p, x, lds_raw);
-}
-}  // namespace os2s
-
-// ---- score gradient of the location-sensitive attention on the matrix cores ------------------------------------
-// ad_loc_score_bwd_kernel's arithmetic (softmax backward, score gradient of one 32-unit part of one sample) with its
-// 36 KB of unrolled register-window code replaced by four small MFMA products:
-//   x[s,u]     = keys + q + bias + sum_k cum[s+k-p] Wck[k,u]            (as the forward: A = Toeplitz rows of cum)
-//   d0[s,u]    = de[s] v[u] (1 - tanh^2 x)                               -> dpre_seq (bf16), dq = sum_s d0, dv += sum_s de tanh x
-//   dWck[k,u] += sum_s cum[s+k-p] d0[s,u]        A = Toeplitz COLUMNS of cum (taps x positions), B = d0^T[u][s]
-//   G[s,k]     = sum_u d0[s,u] Wck[k,u]          A = d0[s][u], B = Wck;   dcum[c] = sum_k G[c + p - k][k]
-// every operand bf16 hi + lo (three MFMAs per product). Waves 0-3 own the four 16x16 tiles of dWck over all
-// positions, waves 4-7 the position tiles of G: no cross-wave sums, fixed summation order (deterministic).
-namespace os2s {
-constexpr int kSbD0sPitch = 40;                      // bf16 elements per position row of d0[s][u]
-__host__ __device__ inline size_t ad_score_bwd_mfma_lds_floats(int S) {
-  const size_t Sp = ((size_t)S + 31) & ~(size_t)31;
-  return 64 + (Sp + 48) + 3 * Sp + Sp * kLocUnits / 2 + Sp * kSbD0sPitch + (size_t)kLocUnits * (Sp + 8) +
-         Sp * 33 + 2 * (size_t)kAttnWaves * 4 * kLocUnits + 64;
-}
-
-__global__ __launch_bounds__(kAttnThreads) void ad_loc_score_bwd_mfma_kernel(AdAttn p, AdLoc x) {
-  extern __shared__ float lds_raw[];
-  const int part = blockIdx.x, b = blockIdx.y, tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int U = p.U, S = p.S, K = p.loc_k;
-  const int Sp = (S + 31) & ~31, TP = Sp + 8;
-  float* qb = lds_raw;                               // [32]
-  float* nv = qb + kLocUnits;                        // [32]
-  float* cum = nv + kLocUnits;                       // [Sp + 48] zero padded, cum[i] = cumulative[i - padl]
-  float* de = cum + Sp + 48;                         // [Sp] softmax-backward of the alignments, zero past the length
-  float* ea = de + Sp;                               // [Sp] alignments   (scratch of the preamble)
-  float* da = ea + Sp;                               // [Sp] d(alignment)
-  uint16_t* keys = reinterpret_cast<uint16_t*>(da + Sp);                    // [Sp][32] bf16
-  uint16_t* d0s_hi = keys + (size_t)Sp * kLocUnits;                         // [Sp][40] bf16: d0[s][u]
-  uint16_t* d0s_lo = d0s_hi + (size_t)Sp * kSbD0sPitch;
-  uint16_t* d0t_hi = d0s_lo + (size_t)Sp * kSbD0sPitch;                     // [32][Sp + 8] bf16: d0^T[u][s]
-  uint16_t* d0t_lo = d0t_hi + (size_t)kLocUnits * TP;
-  float* G = reinterpret_cast<float*>(d0t_lo + (size_t)kLocUnits * TP);     // [Sp][33]
-  float* pq = G + (size_t)Sp * 33;                   // [waves][4][32] partial dq
-  float* pn = pq + kAttnWaves * 4 * kLocUnits;       // [waves][4][32] partial dv terms
-  float* red = pn + kAttnWaves * 4 * kLocUnits;      // [64]
-  const int slen = min(max(p.src_len[b], 0), S);
-  const int u0 = part * kLocUnits;
-  const long long row = (long long)b * p.T + p.t;
-  const int padl = (K - 1) / 2;
-  const int r16 = lane & 15, kb = lane >> 4;
-  // the folded location filter: forward B operand (taps x units) ...
-  float wf[2][8];
-#pragma unroll
-  for (int ut = 0; ut < 2; ++ut)
-#pragma unroll
-    for (int j = 0; j < 8; ++j) wf[ut][j] = p.wck[(long long)min(kb * 8 + j, K - 1) * U + u0 + ut * 16 + r16];
-  // ... and as the B operand of G (units x taps): tap = nt * 16 + r16, units kb * 8 ... + 8 (contiguous)
-  float wg[2][8];
-#pragma unroll
-  for (int nt = 0; nt < 2; ++nt) {
-    const float* wr = p.wck + (long long)min(nt * 16 + r16, K - 1) * U + u0 + kb * 8;
-    const f32x4 a = *reinterpret_cast<const f32x4*>(wr), c = *reinterpret_cast<const f32x4*>(wr + 4);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) { wg[nt][j] = a[j]; wg[nt][4 + j] = c[j]; }
-  }
-  {
-    const float* cs = p.cum_seq + ((long long)b * (p.T + 1) + p.t) * S;
-    for (int i = tid; i < Sp + 48; i += kAttnThreads) {
-      const int sp = i - padl;
-      cum[i] = (sp >= 0 && sp < S) ? cs[sp] : 0.f;
-    }
-    const bf16_t* kp = p.keys + (long long)b * S * U + u0;
-    for (int i = tid; i < slen * 4; i += kAttnThreads) {
-      const int sp = i >> 2, c = i & 3;
-      *reinterpret_cast<u32x4*>(keys + sp * kLocUnits + c * 8) = *reinterpret_cast<const u32x4*>(kp + (long long)sp * U + c * 8);
-    }
-    for (int sp = tid; sp < Sp; sp += kAttnThreads) {
-      ea[sp] = sp < slen ? p.align_seq[row * S + sp] : 0.f;
-      da[sp] = sp < slen ? x.dal[(long long)b * S + sp] : 0.f;
-    }
-  }
-  if (tid < kLocUnits) {
-    const int u = u0 + tid;
-    qb[tid] = p.q_seq[row * U + u] + ((p.use_bias && p.bias) ? p.bias[u] : 0.f) + p.wck[(long long)K * U + u];
-    nv[tid] = p.v[u];
-  }
-  __syncthreads();
-  // softmax backward: de[s] = a[s] (dal[s] - sum_s' a[s'] dal[s'])
-  float dot = 0.f;
-  for (int sp = tid; sp < slen; sp += kAttnThreads) dot += ea[sp] * da[sp];
-  dot = block_sum(dot, red);
-  for (int sp = tid; sp < Sp; sp += kAttnThreads) de[sp] = sp < slen ? ea[sp] * (da[sp] - dot) : 0.f;
-  bf16x8 bh[2], bl[2];
-#pragma unroll
-  for (int ut = 0; ut < 2; ++ut)
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const float w = kb * 8 + j < K ? wf[ut][j] : 0.f;
-      const __bf16 hi = (__bf16)w;
-      bh[ut][j] = hi;
-      bl[ut][j] = (__bf16)(w - (float)hi);
-    }
-  __syncthreads();
-  // ---- phase A: score gradient of every 16-position tile (all tiles up to Sp: dead ones write zeros) ----------
-  const float q0 = qb[r16], q1 = qb[16 + r16], v0 = nv[r16], v1 = nv[16 + r16];
-  float dq0 = 0.f, dq1 = 0.f, dn0 = 0.f, dn1 = 0.f;
-  bf16_t* dps = p.dpre_seq + (row * S) * U + u0;
-#pragma unroll 1
-  for (int pt = wave; pt < Sp / 16; pt += kAttnWaves) {
-    const float* cp = cum + pt * 16 + r16 + kb * 8;
-    bf16x8 ah, al;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const float c = cp[j];
-      const __bf16 hi = (__bf16)c;
-      ah[j] = hi;
-      al[j] = (__bf16)(c - (float)hi);
-    }
-    f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
-    acc0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bh[0], acc0, 0, 0, 0);
-    acc1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bh[1], acc1, 0, 0, 0);
-    acc0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, bh[0], acc0, 0, 0, 0);
-    acc1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, bh[1], acc1, 0, 0, 0);
-    acc0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bl[0], acc0, 0, 0, 0);
-    acc1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bl[1], acc1, 0, 0, 0);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int sp = pt * 16 + 4 * kb + i;
-      const bool on = sp < slen;
-      const uint16_t* kr = keys + sp * kLocUnits + r16;
-      const float t0 = tanh_fast(acc0[i] + q0 + (on ? bf2f(kr[0]) : 0.f));
-      const float t1 = tanh_fast(acc1[i] + q1 + (on ? bf2f(kr[16]) : 0.f));
-      const float des = de[sp];
-      const float d0 = des * v0 * (1.f - t0 * t0), d1 = des * v1 * (1.f - t1 * t1);
-      dq0 += d0; dq1 += d1;
-      dn0 += des * t0; dn1 += des * t1;
-      const bf16_t h0 = f2bf(d0), h1 = f2bf(d1);
-      const bf16_t l0 = f2bf(d0 - bf2f(h0)), l1 = f2bf(d1 - bf2f(h1));
-      if (on) {
-        dps[(long long)sp * U + r16] = h0;
-        dps[(long long)sp * U + 16 + r16] = h1;
-      }
-      d0s_hi[sp * kSbD0sPitch + r16] = h0; d0s_hi[sp * kSbD0sPitch + 16 + r16] = h1;
-      d0s_lo[sp * kSbD0sPitch + r16] = l0; d0s_lo[sp * kSbD0sPitch + 16 + r16] = l1;
-      d0t_hi[r16 * TP + sp] = h0; d0t_hi[(16 + r16) * TP + sp] = h1;
-      d0t_lo[r16 * TP + sp] = l0; d0t_lo[(16 + r16) * TP + sp] = l1;
-    }
-  }
-  pq[(wave * 4 + kb) * kLocUnits + r16] = dq0; pq[(wave * 4 + kb) * kLocUnits + 16 + r16] = dq1;
-  pn[(wave * 4 + kb) * kLocUnits + r16] = dn0; pn[(wave * 4 + kb) * kLocUnits + 16 + r16] = dn1;
-  __syncthreads();
-  if (wave < 4) {
-    // ---- phase B: dWck tile (taps mt * 16 ..., units nt * 16 ...) over all positions ---------------------------
-    const int mt = wave >> 1, nt = wave & 1;
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll 1
-    for (int ks = 0; ks < Sp / 32; ++ks) {
-      const float* cp = cum + ks * 32 + kb * 8 + mt * 16 + r16;      // row = tap, 8 consecutive positions
-      bf16x8 ah, al;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const float c = cp[j];
-        const __bf16 hi = (__bf16)c;
-        ah[j] = hi;
-        al[j] = (__bf16)(c - (float)hi);
-      }
-      const bf16x8 th = *reinterpret_cast<const bf16x8*>(d0t_hi + (nt * 16 + r16) * TP + ks * 32 + kb * 8);
-      const bf16x8 tl = *reinterpret_cast<const bf16x8*>(d0t_lo + (nt * 16 + r16) * TP + ks * 32 + kb * 8);
-      acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, th, acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, th, acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, tl, acc, 0, 0, 0);
-    }
-    float* dwa = p.dwck_acc + (long long)b * K * U + u0 + nt * 16 + r16;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int k = mt * 16 + 4 * kb + i;
-      if (k < K) dwa[(long long)k * U] += acc[i];
-    }
-  } else {
-    // ---- phase C: G[s, k] = sum_u d0[s, u] Wck[k, u] for the position tiles of this wave ---------------------------
-    bf16x8 gh[2], gl[2];
-#pragma unroll
-    for (int nt = 0; nt < 2; ++nt)
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const float w = nt * 16 + r16 < K ? wg[nt][j] : 0.f;
-        const __bf16 hi = (__bf16)w;
-        gh[nt][j] = hi;
-        gl[nt][j] = (__bf16)(w - (float)hi);
-      }
-#pragma unroll 1
-    for (int pt = wave - 4; pt < Sp / 16; pt += 4) {
-      const bf16x8 sh = *reinterpret_cast<const bf16x8*>(d0s_hi + (pt * 16 + r16) * kSbD0sPitch + kb * 8);
-      const bf16x8 sl = *reinterpret_cast<const bf16x8*>(d0s_lo + (pt * 16 + r16) * kSbD0sPitch + kb * 8);
-#pragma unroll
-      for (int nt = 0; nt < 2; ++nt) {
-        f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(sh, gh[nt], acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(sl, gh[nt], acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(sh, gl[nt], acc, 0, 0, 0);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) G[(pt * 16 + 4 * kb + i) * 33 + nt * 16 + r16] = acc[i];
-      }
-    }
-  }
-  __syncthreads();
-  // ---- phase D: state gradient along the anti-diagonals of G; dq / dv sums in a fixed order ------------------------
-  float* dpo = x.dcum_part + ((long long)b * kLocParts + part) * S;
-  for (int c = tid; c < S; c += kAttnThreads) {
-    float a = 0.f;
-    for (int k = 0; k < K; ++k) {
-      const int sp = c + padl - k;
-      if (sp >= 0 && sp < Sp) a += G[sp * 33 + k];
-    }
-    dpo[c] = a;
-  }
-  if (tid < kLocUnits) {
-    float dq = 0.f, dn = 0.f;
-    for (int w = 0; w < kAttnWaves * 4; ++w) { dq += pq[w * kLocUnits + tid]; dn += pn[w * kLocUnits + tid]; }
-    p.dq_seq[row * U + u0 + tid] = f2bf(dq);
-    p.dnv_acc[(long long)b * U + u0 + tid] += dn;
-    p.dbd_acc[(long long)b * U + u0 + tid] += dq;
-  }
-}
-}  // namespace os2s
-
-static bool ad_fast_score_bwd(const os2s_attn_decoder_t* d);
-
-static bool ad_fast_cells(const os2s_attn_decoder_t* d) {
+bool os2s::ad_fast_cells(const os2s_attn_decoder_t* d) {
   static const int on = [] { const char* e = getenv("OS2S_AD_FAST"); return e ? atoi(e) : 1; }();
   if (!on || d->tgt_len || d->score_mode != 2 || d->B > 32 || d->H > 1024 || d->H % 64 || d->M % 64 || d->loc_k > 32)
     return false;
@@ -1153,21 +917,16 @@ static bool ad_fast_cells(const os2s_attn_decoder_t* d) {
   return true;
 }
 
-static int ad_launch_fast_cell(hipStream_t stream, const os2s_attn_decoder_t* d, int l, int t) {
-  const int B = d->B, T = d->T, H = d->H, M = d->M, L = d->L;
+int os2s::ad_launch_fast_cell(hipStream_t stream, const os2s_attn_decoder_t* d, int l, int t) {
+  const int T = d->T, H = d->H, M = d->M;
   const int Kc = l == 0 ? M + H : 2 * H;
   TiLstm c;
-  c.B = B; c.H = H; c.K = Kc; c.Ka = 0; c.in_a = nullptr; c.lda = 0;
+  ti_fill_cell_state(c, d, l, t);
+  c.K = Kc; c.Ka = 0; c.in_a = nullptr; c.lda = 0;
   c.in_b = (const bf16_t*)d->cat[l] + (long long)t * Kc; c.ldb = (long long)(T + 1) * Kc;
   const bool fp8 = d->wcat8[l] != nullptr;
   if (fp8 && !d->wcat8_scale[l]) return OS2S_ERR_INVALID_ARG;
   c.w = fp8 ? (const void*)d->wcat8[l] : (const void*)d->wcat[l]; c.scale = d->wcat8_scale[l]; c.bias = d->bias[l];
-  c.forget_bias = d->forget_bias;
-  c.c_prev = t > 0 ? d->c_seq[l] + (long long)(t - 1) * H : nullptr; c.ldc_prev = (long long)T * H;
-  c.c_out = d->c_seq[l] + (long long)t * H; c.ldc_out = (long long)T * H;
-  c.h1 = (bf16_t*)d->cat[l] + (long long)(t + 1) * Kc + (l == 0 ? M : H); c.ldh1 = (long long)(T + 1) * Kc;
-  if (l == L - 1) { c.h2 = (bf16_t*)d->y_top + (long long)t * d->y_top_ts; c.ldh2 = d->y_top_bs; }
-  else { c.h2 = (bf16_t*)d->cat[l + 1] + (long long)t * 2 * H; c.ldh2 = (long long)(T + 1) * 2 * H; }
   c.state = nullptr;
   c.gx = l == 0 ? (const bf16_t*)d->gx0 + (long long)t * 4 * H : nullptr; c.ldgx = (long long)T * 4 * H;
   c.gates = d->gates[l] ? (bf16_t*)d->gates[l] + (long long)t * 4 * H : nullptr; c.ldgates = (long long)T * 4 * H;
@@ -1175,27 +934,9 @@ static int ad_launch_fast_cell(hipStream_t stream, const os2s_attn_decoder_t* d,
   return ti_launch_cell(stream, c, fp8);
 }
 
-static int ad_launch_fast_scores(hipStream_t stream, const os2s::AdAttn& at, const os2s::AdLoc& lx,
-                                 const os2s_attn_decoder_t* d) {
+int os2s::ad_launch_fast_scores(hipStream_t stream, const AdAttn& at, const AdLoc& lx,
+                                const os2s_attn_decoder_t* d) {
   const size_t lds = ti_scores_lds_floats(d->S) * sizeof(float);
   OS2S_LAUNCH(ad_loc_scores_mfma_kernel, dim3(kLocParts, d->B), dim3(kAttnThreads), lds, stream, at, lx);
-  return OS2S_OK;
-}
-
-// the backward pass's score-gradient launch on the MFMA kernel (same conditions as the forward fast path)
-static bool ad_fast_score_bwd(const os2s_attn_decoder_t* d) {
-  return ad_fast_cells(d) && ad_score_bwd_mfma_lds_floats(d->S) * sizeof(float) <= 160 * 1024 && d->U % 4 == 0;
-}
-static int ad_launch_fast_score_bwd(hipStream_t stream, const os2s::AdAttn& at, const os2s::AdLoc& lx,
-                                    const os2s_attn_decoder_t* d) {
-  const size_t lds = ad_score_bwd_mfma_lds_floats(d->S) * sizeof(float);
-  static size_t attr_for = 0;
-  if (lds > 64 * 1024 && lds > attr_for) {
-    if (hipFuncSetAttribute((const void*)ad_loc_score_bwd_mfma_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)lds) != hipSuccess)
-      return OS2S_ERR_LAUNCH;
-    attr_for = lds;
-  }
-  OS2S_LAUNCH(ad_loc_score_bwd_mfma_kernel, dim3(kLocParts, d->B), dim3(kAttnThreads), lds, stream, at, lx);
   return OS2S_OK;
 }

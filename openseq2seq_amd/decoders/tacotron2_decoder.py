@@ -228,7 +228,7 @@ class Tacotron2Decoder(Decoder):
   POLL_STEPS = 32      # host looks at the device-resident stop decision every POLL_STEPS steps
 
   def _infer_weights(self, fp8):
-    """Inference copies the fused step kernels read (csrc/tacotron_infer.hpp), rebuilt when the bf16
+    """Inference copies the fused step kernels read (csrc/tacotron_infer.hip), rebuilt when the bf16
     weights changed: layer 0 with the pre-net columns in front of the attention / state columns
     ([kernel_inputs | kernel_attention_state], optionally e4m3 with per-row scales) and the output
     projection split into its cell-output and context column blocks."""

@@ -1,6 +1,6 @@
 """GPU parity of free-running Tacotron2 decoding (Tacotron2Decoder in eval / infer mode,
 decoders/tacotron2_decoder.py:378-428; TacotronHelper parts/tacotron/tacotron_helper.py:138-226) on the
-fused step kernels (csrc/tacotron_infer.hpp: os2s_tacotron_infer_steps, four launches per step, the stop
+fused step kernels (csrc/tacotron_infer.hip: os2s_tacotron_infer_steps, four launches per step, the stop
 decision on the device) against the CPU oracle (oracle/tacotron.py:decoder_infer), plus the eval-mode loss
 (Text2SpeechLoss with prediction and target padded to a common length, losses/text2speech_loss.py:80-131).
 
