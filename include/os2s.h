@@ -571,6 +571,40 @@ int os2s_psf_logfbank(os2s_stream_t stream, const void* signal, int sample_is_in
                       int B, long long Nmax, int n_win, int n_step, int pad_to, int nfilt, int nfft,
                       const float* fb, int Tpad, uint16_t* out_bf16, float* out_f32, int32_t* out_len,
                       void* workspace, size_t workspace_bytes);
+/* 'mfcc' features of the python_speech_features backend (get_speech_features_psf,
+ * open_seq2seq/data/speech2text/speech_utils.py:504-515 -> psf.mfcc(numcep = F, nfilt = 2F, nfft = 512, lowfreq = 0,
+ * highfreq = sr / 2, preemph = 0.97, ceplifter = 2F, appendEnergy = False); example_configs/speech2text/
+ * lstm_small_1gpu.py): everything of os2s_psf_logfbank up to the ln of the nfilt filter energies, then
+ * dctl [numcep][nfilt] (device, fp32: lifter(m) * orthonormal DCT-II(m, j)) applied to the frame's log energies
+ * inside the kernel, then (x - mean) / std over the utterance incl. the pad_to frames. Workspace:
+ * os2s_psf_spectrogram_workspace_bytes(B, Tpad, numcep). */
+int os2s_psf_mfcc(os2s_stream_t stream, const void* signal, int sample_is_int16, const int32_t* n_samples, int B,
+                  long long Nmax, int n_win, int n_step, int pad_to, int numcep, int nfilt, int nfft,
+                  const float* fb, const float* dctl, int Tpad, uint16_t* out_bf16, float* out_f32,
+                  int32_t* out_len, void* workspace, size_t workspace_bytes);
+/* The 'mfcc' and 'spectrogram' features of the librosa backend (get_speech_features_librosa,
+ * open_seq2seq/data/speech2text/speech_utils.py:383-395 and :367-381). Signal, gain, dither, frame count
+ * (1 + n_samples / hop), zero padding to Tpad and norm_per_feature as os2s_logmel; window [n_fft] and the tables
+ * are fp64 device arrays. features_mean / features_std [F] (fp64, device) or NULL: the 'features_mean' /
+ * 'features_std_dev' of the configuration, used in place of the utterance's own statistics (:412-417).
+ *   os2s_librosa_mfcc: pre-emphasis, stft(n_fft, win_length) and then — as the reference's call
+ *       librosa.feature.mfcc(S = power spectrum) computes it — dct [n_mfcc][n_fft/2 + 1], the orthonormal DCT-II
+ *       along the LINEAR frequency bins of the power spectrum: no mel filter bank, no logarithm.
+ *   os2s_librosa_spectrogram: no pre-emphasis, stft(n_fft = win_length = n_win) (any length, 320 at the
+ *       defaults), 10 log10 max(|.|^2, 1e-30), the first num_features <= n_win / 2 + 1 bins. */
+size_t os2s_librosa_features_workspace_bytes(int B, int Tmax, int F);
+int os2s_librosa_mfcc(os2s_stream_t stream, const void* signal, const int32_t* n_samples, int sample_is_int16,
+                      int B, long long Nmax, int n_fft, int win_length, int hop, int n_mfcc, const double* window,
+                      const double* dct, float preemph, float dither, unsigned long long seed, float fixed_gain,
+                      int norm_per_feature, const double* features_mean, const double* features_std, int Tmax,
+                      int Tpad, uint16_t* out_bf16, float* out_f32, int32_t* out_len, void* workspace,
+                      size_t workspace_bytes);
+int os2s_librosa_spectrogram(os2s_stream_t stream, const void* signal, const int32_t* n_samples,
+                             int sample_is_int16, int B, long long Nmax, int n_win, int hop, int num_features,
+                             const double* window, float dither, unsigned long long seed, float fixed_gain,
+                             int norm_per_feature, const double* features_mean, const double* features_std,
+                             int Tmax, int Tpad, uint16_t* out_bf16, float* out_f32, int32_t* out_len,
+                             void* workspace, size_t workspace_bytes);
 size_t os2s_logmel_workspace_bytes(int B, int Tmax, int n_mels);
 int os2s_logmel(os2s_stream_t stream, const void* signal, const int32_t* n_samples,
                 int sample_is_int16, int B, long long Nmax, int n_fft, int hop,

@@ -889,6 +889,76 @@ def psf_logfbank(signal, n_samples, fb, *, n_win, n_step, pad_to, nfft, tpad, wa
   return out, olen, out32
 
 
+def psf_mfcc(signal, n_samples, fb, dctl, *, n_win, n_step, pad_to, nfft, tpad, want_f32=False):
+  """signal [B,Nmax] float32|int16, fb [nfilt, nfft/2+1] fp32, dctl [numcep, nfilt] fp32 (lifter x DCT-II) ->
+  (features bf16 [B,tpad,numcep], frames int32 [B], f32|None): the psf backend's 'mfcc' features (os2s_psf_mfcc)."""
+  B, Nmax = signal.shape
+  dev = signal.device
+  is_i16 = signal.dtype == torch.int16
+  assert is_i16 or signal.dtype == torch.float32
+  nfilt = fb.shape[0]
+  numcep = dctl.shape[0]
+  assert fb.is_contiguous() and fb.shape[1] == nfft // 2 + 1 and dctl.is_contiguous() and dctl.shape[1] == nfilt
+  nbytes = int(_lib.C.os2s_psf_spectrogram_workspace_bytes(B, tpad, numcep))
+  ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+  out = torch.empty((B, tpad, numcep), dtype=torch.bfloat16, device=dev)
+  out32 = torch.empty((B, tpad, numcep), dtype=torch.float32, device=dev) if want_f32 else None
+  olen = torch.empty((B,), dtype=torch.int32, device=dev)
+  _lib.C.os2s_psf_mfcc(_stream(), _ptr(signal), int(is_i16), _ptr(n_samples, torch.int32), B, Nmax, n_win, n_step,
+                       pad_to, numcep, nfilt, nfft, _ptr(fb, torch.float32), _ptr(dctl, torch.float32), tpad,
+                       _ptr(out), _ptr(out32, None, True), _ptr(olen), _ptr(ws), nbytes)
+  return out, olen, out32
+
+
+def _librosa_buffers(signal, F, tmax, tpad, want_f32):
+  B, _ = signal.shape
+  dev = signal.device
+  assert signal.dtype in (torch.int16, torch.float32)
+  nbytes = int(_lib.C.os2s_librosa_features_workspace_bytes(B, tmax, F))
+  ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+  out = torch.empty((B, tpad, F), dtype=torch.bfloat16, device=dev)
+  out32 = torch.empty((B, tpad, F), dtype=torch.float32, device=dev) if want_f32 else None
+  olen = torch.empty((B,), dtype=torch.int32, device=dev)
+  return ws, nbytes, out, out32, olen
+
+
+def librosa_mfcc(signal, n_samples, window, dct, *, win_length, hop, tmax, tpad, preemph=0.97, dither=0.0, seed=0,
+                 fixed_gain=-1.0, norm_per_feature=False, features_mean=None, features_std=None, want_f32=False):
+  """signal [B,Nmax] float32|int16, window [n_fft] fp64, dct [n_mfcc, n_fft/2+1] fp64 -> (features bf16
+  [B,tpad,n_mfcc], frames int32 [B], f32|None): the librosa backend's 'mfcc' features (os2s_librosa_mfcc).
+  features_mean / features_std: fp64 [n_mfcc] or None."""
+  B, Nmax = signal.shape
+  n_fft, F = window.numel(), dct.shape[0]
+  assert dct.is_contiguous() and dct.shape[1] == n_fft // 2 + 1
+  assert all(t is None or t.numel() == F for t in (features_mean, features_std))
+  ws, nbytes, out, out32, olen = _librosa_buffers(signal, F, tmax, tpad, want_f32)
+  _lib.C.os2s_librosa_mfcc(_stream(), _ptr(signal), _ptr(n_samples, torch.int32), int(signal.dtype == torch.int16),
+                           B, Nmax, n_fft, int(win_length), int(hop), F, _ptr(window, torch.float64),
+                           _ptr(dct, torch.float64), float(preemph), float(dither), int(seed) & (2**64 - 1),
+                           float(fixed_gain), int(bool(norm_per_feature)), _ptr(features_mean, torch.float64, True),
+                           _ptr(features_std, torch.float64, True), tmax, tpad, _ptr(out), _ptr(out32, None, True),
+                           _ptr(olen), _ptr(ws), nbytes)
+  return out, olen, out32
+
+
+def librosa_spectrogram(signal, n_samples, window, *, hop, num_features, tmax, tpad, dither=0.0, seed=0,
+                        fixed_gain=-1.0, norm_per_feature=False, features_mean=None, features_std=None,
+                        want_f32=False):
+  """signal [B,Nmax] float32|int16, window [n_win] fp64 -> (features bf16 [B,tpad,num_features], frames int32 [B],
+  f32|None): the librosa backend's 'spectrogram' features (os2s_librosa_spectrogram)."""
+  B, Nmax = signal.shape
+  n_win, F = window.numel(), int(num_features)
+  assert all(t is None or t.numel() == F for t in (features_mean, features_std))
+  ws, nbytes, out, out32, olen = _librosa_buffers(signal, F, tmax, tpad, want_f32)
+  _lib.C.os2s_librosa_spectrogram(_stream(), _ptr(signal), _ptr(n_samples, torch.int32),
+                                  int(signal.dtype == torch.int16), B, Nmax, n_win, int(hop), F,
+                                  _ptr(window, torch.float64), float(dither), int(seed) & (2**64 - 1),
+                                  float(fixed_gain), int(bool(norm_per_feature)),
+                                  _ptr(features_mean, torch.float64, True), _ptr(features_std, torch.float64, True),
+                                  tmax, tpad, _ptr(out), _ptr(out32, None, True), _ptr(olen), _ptr(ws), nbytes)
+  return out, olen, out32
+
+
 def augment_signal(signal, n_in, n_out, ratio, noise_amp, interp_win, num_table, nout_max, seed=0,
                    fixed_gain=-1.0):
   """signal [B,Nmax] int16|float32 -> normalised, speed-perturbed, noised fp32 [B,nout_max]."""

@@ -142,16 +142,24 @@ __global__ __launch_bounds__(256) void psf_normalize_kernel(const float* __restr
 // One workgroup per frame: direct real DFT of the n_win live samples against a 512-entry twiddle table in
 // LDS (nfft = 512 has a fast transform, but this is a data-layer op of ~82 k MAC per frame), power spectrum
 // in LDS, one thread per filter.
+//
+// MFCC = true: the 'mfcc' features of the same backend (speech_utils.py:504-515 -> psf.mfcc(numcep = F,
+// nfilt = 2F, nfft = 512, lowfreq = 0, highfreq = sr / 2, preemph = 0.97, ceplifter = 2F, appendEnergy = False),
+// rectangular window): the nfilt log energies of the frame stay in LDS and one thread per coefficient applies
+// the host table dctl [ncep][nfilt] = lifter(m) * orthonormal DCT-II(m, j); the plane holds the ncep cepstra.
+// A pad_to frame has ln(eps) in every filter: its cepstrum is a constant c0 and (rounding aside) zeros.
+template <bool MFCC>
 __global__ __launch_bounds__(256) void psf_logfbank_kernel(
     const void* __restrict__ signal, int is_i16, long long sig_stride, const int32_t* __restrict__ n_samples,
     const float* __restrict__ denom, int n_win, int n_step, int pad_to, int nfilt, int nfft,
-    const float* __restrict__ fb, int T, float* __restrict__ plane, double* __restrict__ partial,
-    int32_t* __restrict__ frames_out) {
+    const float* __restrict__ fb, const float* __restrict__ dctl, int ncep, int T, float* __restrict__ plane,
+    double* __restrict__ partial, int32_t* __restrict__ frames_out) {
   extern __shared__ float sm[];
   float* x = sm;                 // [n_win] pre-emphasised frame
   float* cs = sm + n_win;        // [nfft]
   float* sn = cs + nfft;         // [nfft]
   float* ps = sn + nfft;         // [nfft / 2 + 1]
+  float* le = ps + nfft / 2 + 1; // [nfilt] log filterbank energies (MFCC only)
   __shared__ double red[2][4];
   const int b = blockIdx.y, t = blockIdx.x, tid = threadIdx.x;
   const int nbins = nfft / 2 + 1;
@@ -208,9 +216,24 @@ __global__ __launch_bounds__(256) void psf_logfbank_kernel(
     const float* const f = fb + (long long)m * nbins;
     for (int k = 0; k < nbins; ++k) e += ps[k] * f[k];
     const float v = logf(e == 0.f ? 2.220446049250313e-16f : e);
-    plane[((long long)b * T + t) * nfilt + m] = v;
-    s1 += (double)v;
-    s2 += (double)v * (double)v;
+    if (MFCC) {
+      le[m] = v;
+    } else {
+      plane[((long long)b * T + t) * nfilt + m] = v;
+      s1 += (double)v;
+      s2 += (double)v * (double)v;
+    }
+  }
+  if (MFCC) {
+    __syncthreads();
+    for (int m = tid; m < ncep; m += 256) {
+      float c = 0.f;
+      const float* const d = dctl + (long long)m * nfilt;
+      for (int j = 0; j < nfilt; ++j) c += le[j] * d[j];
+      plane[((long long)b * T + t) * ncep + m] = c;
+      s1 += (double)c;
+      s2 += (double)c * (double)c;
+    }
   }
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) {
@@ -251,9 +274,40 @@ extern "C" int os2s_psf_logfbank(os2s_stream_t stream_, const void* signal, int 
   off += (size_t)B * Tpad * 2 * 8;
   float* plane = reinterpret_cast<float*>(ws + off);
   OS2S_LAUNCH(psf_absmax_kernel, dim3(B), dim3(256), 0, stream, signal, sample_is_int16, Nmax, n_samples, denom);
-  OS2S_LAUNCH(psf_logfbank_kernel, dim3(Tpad, B), dim3(256), lds, stream, signal, sample_is_int16, Nmax, n_samples,
-              denom, n_win, n_step, pad_to, nfilt, nfft, fb, Tpad, plane, partial, out_len);
+  OS2S_LAUNCH(psf_logfbank_kernel<false>, dim3(Tpad, B), dim3(256), lds, stream, signal, sample_is_int16, Nmax,
+              n_samples, denom, n_win, n_step, pad_to, nfilt, nfft, fb, (const float*)nullptr, 0, Tpad, plane, partial,
+              out_len);
   OS2S_LAUNCH(psf_normalize_kernel, dim3(64, B), dim3(256), 0, stream, plane, partial, out_len, nfilt, Tpad,
+              out_bf16, out_f32);
+  return OS2S_OK;
+}
+
+// 'mfcc' of the psf backend (psf_logfbank_kernel<true>): fb = [nfilt][nfft/2 + 1] filter table as for
+// os2s_psf_logfbank, dctl = [numcep][nfilt] fp32 DCT-II x lifter table (device; the host layer builds both).
+// Workspace as os2s_psf_spectrogram_workspace_bytes(B, Tpad, numcep): only the cepstra reach memory.
+extern "C" int os2s_psf_mfcc(os2s_stream_t stream_, const void* signal, int sample_is_int16,
+                             const int32_t* n_samples, int B, long long Nmax, int n_win, int n_step, int pad_to,
+                             int numcep, int nfilt, int nfft, const float* fb, const float* dctl, int Tpad,
+                             uint16_t* out_bf16, float* out_f32, int32_t* out_len, void* workspace,
+                             size_t workspace_bytes) {
+  OS2S_REQUIRE(signal && n_samples && fb && dctl && out_bf16 && out_len && workspace);
+  OS2S_REQUIRE(B >= 1 && n_win >= 16 && n_step >= 1 && Tpad >= 1 && nfilt >= 1 && nfilt <= 4096);
+  OS2S_REQUIRE(numcep >= 1 && numcep <= nfilt);
+  OS2S_REQUIRE(nfft >= n_win && (nfft & (nfft - 1)) == 0);
+  if (workspace_bytes < os2s_psf_spectrogram_workspace_bytes(B, Tpad, numcep)) return OS2S_ERR_WORKSPACE;
+  const size_t lds = ((size_t)n_win + 2 * (size_t)nfft + nfft / 2 + 1 + nfilt) * sizeof(float);
+  if (lds > 48 * 1024) return OS2S_ERR_UNSUPPORTED;
+  hipStream_t stream = (hipStream_t)stream_;
+  char* ws = reinterpret_cast<char*>(workspace);
+  float* denom = reinterpret_cast<float*>(ws);
+  size_t off = ((size_t)B * 4 + 63) / 64 * 64;
+  double* partial = reinterpret_cast<double*>(ws + off);
+  off += (size_t)B * Tpad * 2 * 8;
+  float* plane = reinterpret_cast<float*>(ws + off);
+  OS2S_LAUNCH(psf_absmax_kernel, dim3(B), dim3(256), 0, stream, signal, sample_is_int16, Nmax, n_samples, denom);
+  OS2S_LAUNCH(psf_logfbank_kernel<true>, dim3(Tpad, B), dim3(256), lds, stream, signal, sample_is_int16, Nmax,
+              n_samples, denom, n_win, n_step, pad_to, nfilt, nfft, fb, dctl, numcep, Tpad, plane, partial, out_len);
+  OS2S_LAUNCH(psf_normalize_kernel, dim3(64, B), dim3(256), 0, stream, plane, partial, out_len, numcep, Tpad,
               out_bf16, out_f32);
   return OS2S_OK;
 }

@@ -322,7 +322,9 @@ class Speech2TextDataLayer(DataLayer):
 
   # ------------------------------------------------------------------------
   def _psf(self):
-    return self.params.get('backend', 'psf') == 'psf' and self.params.get('input_type') == 'spectrogram'
+    """The psf order of operations: augmentation on the raw samples, framesig's frame count. True for the
+    'spectrogram' and 'mfcc' features of the psf backend; psf 'logfbank' keeps the behaviour it has had."""
+    return self.params.get('backend', 'psf') == 'psf' and self.params.get('input_type') in ('spectrogram', 'mfcc')
 
   def frames_for_samples(self, n_samples):
     sr = self.params.get('sample_freq', 16000)

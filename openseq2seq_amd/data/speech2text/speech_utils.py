@@ -1,9 +1,10 @@
 """Speech feature extraction front end — host side of
 open_seq2seq/data/speech2text/speech_utils.py (get_speech_features :275-319,
-get_speech_features_librosa :322-441). The per-sample arithmetic runs on the GPU
-(csrc/logmel.hip, os2s_logmel); the host only prepares constant tables once:
-the analysis window and the mel filterbank (what the reference precomputes with
-librosa.filters.mel in speech2text.py:167-183).
+get_speech_features_librosa :322-441, get_speech_features_psf :444-535): one launcher class per
+(backend, input_type), see FRONT_ENDS. The per-sample arithmetic runs on the GPU
+(csrc/logmel.hip, csrc/psf_features.hip); the host only prepares constant tables once:
+the analysis window, the mel filterbank (what the reference precomputes with
+librosa.filters.mel in speech2text.py:167-183) and the DCT matrices of the 'mfcc' paths.
 
 librosa 0.6.3 conventions used by the reference's call sites (librosa itself is not
 vendored in the reference): window passed as the CALLABLE np.hanning => symmetric
@@ -192,14 +193,168 @@ class PsfLogfbankFrontEnd(PsfSpectrogramFrontEnd):
                              pad_to=self.pad_to, nfft=self.nfft, tpad=self.frames(nmax), want_f32=want_f32)
 
 
+def dct_ortho_table(n_out, n_in):
+  """scipy.fftpack.dct(x, type=2, norm='ortho') over n_in points, first n_out coefficients: [n_out, n_in]."""
+  m = np.arange(n_out)[:, None]
+  j = np.arange(n_in)[None, :]
+  d = np.sqrt(2.0 / n_in) * np.cos(np.pi * m * (2 * j + 1) / (2.0 * n_in))
+  d[0] *= np.sqrt(0.5)
+  return d
+
+
+def psf_mfcc_table(numcep, nfilt, ceplifter):
+  """What psf.mfcc applies to the nfilt log filterbank energies of a frame, as one [numcep, nfilt] matrix: the
+  orthonormal DCT-II along the filters, the first numcep coefficients, then psf.lifter: coefficient m times
+  1 + (L / 2) sin(pi m / L)."""
+  d = dct_ortho_table(numcep, nfilt)
+  if ceplifter > 0:
+    d *= 1.0 + (ceplifter / 2.0) * np.sin(np.pi * np.arange(numcep)[:, None] / ceplifter)
+  return d
+
+
+class PsfMfccFrontEnd(PsfLogfbankFrontEnd):
+  """Launcher for the 'mfcc' features of the python_speech_features backend (get_speech_features_psf,
+  speech_utils.py:504-515: psf.mfcc with numcep = F, nfilt = 2F, nfft = 512, preemph = 0.97, ceplifter = 2F,
+  appendEnergy = False, rectangular window; example_configs/speech2text/lstm_small_1gpu.py). Framing and padding
+  as the other psf paths."""
+
+  def __init__(self, params, device):
+    self.device = device
+    sr = params.get('sample_freq', 16000)
+    self.sample_freq = sr
+    if params.get('backend', 'psf') != 'psf' or params.get('input_type') != 'mfcc':
+      raise NotImplementedError("PsfMfccFrontEnd implements backend='psf', input_type='mfcc'")
+    self.num_features = params['num_audio_features']
+    self.win_length = int(sr * params.get('window_size', 20e-3))
+    self.hop = int(sr * params.get('window_stride', 10e-3))
+    self.pad_to = params.get('pad_to', 8)
+    self.gain = None
+    self.nfft = 512
+    if self.win_length > self.nfft:
+      raise NotImplementedError("psf.mfcc truncates frames longer than nfft = 512 (window_size > 32 ms)")
+    nfilt = 2 * self.num_features
+    fb = psf_filterbanks(nfilt, self.nfft, sr, 0.0, sr / 2.0)
+    self.fb = torch.from_numpy(np.ascontiguousarray(fb, np.float32)).to(device)
+    dctl = psf_mfcc_table(self.num_features, nfilt, nfilt)
+    self.dctl = torch.from_numpy(np.ascontiguousarray(dctl, np.float32)).to(device)
+
+  def __call__(self, signal, n_samples, max_samples=None, seed=0, want_f32=False):
+    nmax = int(max_samples) if max_samples is not None else signal.shape[1]
+    return capi.psf_mfcc(signal, n_samples, self.fb, self.dctl, n_win=self.win_length, n_step=self.hop,
+                         pad_to=self.pad_to, nfft=self.nfft, tpad=self.frames(nmax), want_f32=want_f32)
+
+
+class _LibrosaFrontEnd(object):
+  """What the 'mfcc' and 'spectrogram' launchers of the librosa backend share: the parameters of
+  get_speech_features (speech_utils.py:289-311), the frame count of a centred STFT and the padding to pad_to."""
+  input_type = None
+
+  def __init__(self, params, device):
+    self.device = device
+    sr = params.get('sample_freq', 16000)
+    self.sample_freq = sr
+    if params.get('backend', 'psf') != 'librosa' or params.get('input_type') != self.input_type:
+      raise NotImplementedError("%s implements backend='librosa', input_type='%s'"
+                                % (type(self).__name__, self.input_type))
+    self.num_features = params['num_audio_features']
+    window_size = params.get('window_size', 20e-3)
+    self.win_length = int(sr * window_size)
+    self.hop = int(sr * params.get('window_stride', 10e-3))
+    self.n_fft = self._transform_length(params, window_size * sr)
+    self.dither = params.get('dither', 0.0)
+    self.norm_per_feature = params.get('norm_per_feature', False)
+    self.gain = params.get('gain', None)
+    self.pad_to = params.get('pad_to', 8)
+    wfn = WINDOWS_FNS[params.get('window', 'hanning')]
+    win = wfn(self.win_length) if wfn is not None else np.ones(self.win_length)
+    full = np.zeros(self.n_fft, np.float64)
+    lp = (self.n_fft - self.win_length) // 2
+    full[lp:lp + self.win_length] = win
+    self.window = torch.from_numpy(full).to(device)
+    self.features_mean = self._given(params.get('features_mean'))
+    self.features_std = self._given(params.get('features_std_dev'))
+
+  def _given(self, value):
+    if value is None:
+      return None
+    full = np.array(np.broadcast_to(np.asarray(value, np.float64), (self.num_features,)))
+    return torch.from_numpy(full).to(self.device)
+
+  def frames(self, n_samples):
+    return 1 + int(n_samples) // self.hop
+
+  def _shape(self, signal, max_samples):
+    nmax = int(max_samples) if max_samples is not None else signal.shape[1]
+    tmax = self.frames(nmax)
+    return tmax, (-(-tmax // self.pad_to) * self.pad_to if self.pad_to > 0 else tmax)
+
+  def _common(self, seed, want_f32):
+    return dict(hop=self.hop, dither=self.dither, seed=seed,
+                fixed_gain=self.gain if self.gain is not None else -1.0, norm_per_feature=self.norm_per_feature,
+                features_mean=self.features_mean, features_std=self.features_std, want_f32=want_f32)
+
+
+class LibrosaMfccFrontEnd(_LibrosaFrontEnd):
+  """Launcher for the 'mfcc' features of the librosa backend (get_speech_features_librosa, speech_utils.py:383-395).
+  The reference hands librosa.feature.mfcc the LINEAR power STFT as S; librosa uses a given S as it stands (the mel
+  filter bank and the dB conversion run only when S is None, n_mels is ignored), so the features are
+  dct(S, axis=0, type=2, norm='ortho')[:F].T — the DCT-II along the n_fft / 2 + 1 frequency bins of the power
+  spectrum, with no mel scale and no logarithm. This class reproduces that."""
+  input_type = 'mfcc'
+
+  def _transform_length(self, params, win):
+    return params.get('num_fft', None) or 2 ** math.ceil(math.log2(win))
+
+  def __init__(self, params, device):
+    super(LibrosaMfccFrontEnd, self).__init__(params, device)
+    self.dct = torch.from_numpy(dct_ortho_table(self.num_features, self.n_fft // 2 + 1)).to(device)
+
+  def __call__(self, signal, n_samples, max_samples=None, seed=0, want_f32=False):
+    tmax, tpad = self._shape(signal, max_samples)
+    return capi.librosa_mfcc(signal, n_samples, self.window, self.dct, win_length=self.win_length, tmax=tmax,
+                             tpad=tpad, **self._common(seed, want_f32))
+
+
+class LibrosaSpectrogramFrontEnd(_LibrosaFrontEnd):
+  """Launcher for the 'spectrogram' features of the librosa backend (speech_utils.py:367-381): no pre-emphasis,
+  stft(n_fft = win_length = int(sr * window_size)), 10 log10 of the power clamped at 1e-30, the first F bins."""
+  input_type = 'spectrogram'
+
+  def _transform_length(self, params, win):
+    return self.win_length
+
+  def __init__(self, params, device):
+    super(LibrosaSpectrogramFrontEnd, self).__init__(params, device)
+    if self.num_features > self.win_length // 2 + 1:        # speech_utils.py:377-378
+      raise AssertionError("num_features for spectrogram should be <= (sample_freq * window_size // 2 + 1)")
+
+  def __call__(self, signal, n_samples, max_samples=None, seed=0, want_f32=False):
+    tmax, tpad = self._shape(signal, max_samples)
+    return capi.librosa_spectrogram(signal, n_samples, self.window, num_features=self.num_features, tmax=tmax,
+                                    tpad=tpad, **self._common(seed, want_f32))
+
+
+FRONT_ENDS = {
+    ('psf', 'spectrogram'): PsfSpectrogramFrontEnd,        # DeepSpeech2
+    ('psf', 'logfbank'): PsfLogfbankFrontEnd,              # the toy Wave2Letter configs
+    ('psf', 'mfcc'): PsfMfccFrontEnd,                      # lstm_small_1gpu.py
+    ('librosa', 'logfbank'): LogMelFrontEnd,               # Jasper, QuartzNet, Wave2Letter+
+    ('librosa', 'mfcc'): LibrosaMfccFrontEnd,
+    ('librosa', 'spectrogram'): LibrosaSpectrogramFrontEnd,
+}
+
+
+def front_end_class(params):
+  """The front-end class of a Speech2TextDataLayer configuration, by (backend, input_type)."""
+  key = (params.get('backend', 'psf'), params.get('input_type'))
+  if key not in FRONT_ENDS:
+    raise NotImplementedError("no GPU front end for backend=%r, input_type=%r" % key)
+  return FRONT_ENDS[key]
+
+
 def make_front_end(params, device):
-  """The GPU front end of a Speech2TextDataLayer configuration: log-mel (librosa backend, the
-  Jasper / wav2letter configs) or psf spectrogram (the DeepSpeech2 configs)."""
-  if params.get('backend', 'psf') == 'psf' and params.get('input_type') == 'spectrogram':
-    return PsfSpectrogramFrontEnd(params, device)
-  if params.get('backend', 'psf') == 'psf' and params.get('input_type') == 'logfbank':
-    return PsfLogfbankFrontEnd(params, device)
-  return LogMelFrontEnd(params, device)
+  """The GPU front end of a Speech2TextDataLayer configuration."""
+  return front_end_class(params)(params, device)
 
 
 # ---- speed perturbation filter (resampy 'kaiser_best') --------------------------------------------

@@ -36,7 +36,7 @@ def _guarded(slot, wt=False):
 
 class Param(object):
   __slots__ = ("name", "shape", "index", "offset", "numel", "l2", "kind", "store",
-               "_master", "_grad", "_w16", "_wt16", "wt_offset", "trainable_mask", "logical_out")
+               "_master", "_grad", "_w16", "_wt16", "wt_offset", "trainable_mask", "logical_out", "logical_in")
   master = _guarded("_master")
   grad = _guarded("_grad")
   w16 = _guarded("_w16")
@@ -48,6 +48,9 @@ class Param(object):
     # output layers padded to an MFMA-friendly width: number of REAL output units (rows of a
     # [1, Vpad, H] kernel / entries of a [Vpad] bias); checkpoints carry the logical shape
     self.logical_out = logical_out
+    # an input width padded to the GEMMs' multiple of 8: number of REAL input units (columns of a
+    # [1, Cout, Cin_pad] kernel; the rest stay zero); checkpoints carry the logical shape
+    self.logical_in = None
     self.store = None
     self._master = self._grad = self._w16 = self._wt16 = None
 

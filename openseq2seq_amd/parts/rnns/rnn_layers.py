@@ -27,21 +27,30 @@ SHIFTED_WH_MIN_ROWS = int(os.environ.get("OS2S_RNN_WH_GEMM_ROWS", "4096"))
 
 
 class RNNDirection(object):
-  def __init__(self, store, name, cell, input_sizes, hidden, reverse=False, forget_bias=1.0):
+  def __init__(self, store, name, cell, input_sizes, hidden, reverse=False, forget_bias=1.0, logical_in=None):
+    """logical_in: the real width of a (single) input that the caller zero-pads to input_sizes[0]: the kernel's
+    extra columns start at zero — and stay there, their inputs being zero —, the glorot limit counts the real
+    fan-in and checkpoints carry the logical shape."""
     self.cell_name, self.cell = cell, CELLS[cell]
     self.H, self.G = hidden, 3 if cell == "gru_cudnn" else 4
     self.reverse, self.forget_bias = reverse, (forget_bias if cell == "lstm_tf" else 0.0)
     GH = self.G * hidden
-    tot_in = sum(input_sizes)
+    assert logical_in is None or (len(input_sizes) == 1 and logical_in <= input_sizes[0])
+    tot_in = sum(input_sizes) if logical_in is None else logical_in
 
-    def init_w(fan_in):
+    def init_w(fan_in, live=None):
       def f(shape):   # glorot-uniform over the full [in + H, G*H] matrix (TF LSTMCell default)
         lim = math.sqrt(6.0 / (fan_in + hidden + GH))
-        return (torch.rand(shape) * 2 - 1) * lim
+        w = (torch.rand(shape) * 2 - 1) * lim
+        if live is not None:
+          w[:, :, live:] = 0
+        return w
       return f
 
-    self.wx = [store.add("%s/wx_%d" % (name, i), (1, GH, n), init_w(tot_in), kind="conv")
+    self.wx = [store.add("%s/wx_%d" % (name, i), (1, GH, n), init_w(tot_in, logical_in), kind="conv")
                for i, n in enumerate(input_sizes)]
+    if logical_in is not None:
+      self.wx[0].logical_in = logical_in
     self.wh = store.add(name + "/wh", (1, GH, hidden), init_w(tot_in), kind="conv")
     self.bx = store.add(name + "/bias", (GH,), torch.zeros(GH), kind="vector")
     self.bh = store.add(name + "/bias_h", (GH,), torch.zeros(GH), kind="vector") \
@@ -151,21 +160,42 @@ class BiRNNStack(object):
                forget_bias=1.0):
     self.layers = []
     self.H, self.ndir = hidden, 2 if bidirectional else 1
-    in_size = input_size
+    # the input GEMMs need a width that is a multiple of 8: a narrower input (13 MFCCs straight into the first
+    # layer) is zero-padded in forward(), and the first layer's input kernels carry the logical width
+    self.input_size, self.input_pad = input_size, -input_size % 8
+    in_size = input_size + self.input_pad
     for l in range(num_layers):
+      logical = input_size if (l == 0 and self.input_pad) else None
       dirs = [RNNDirection(store, "%s/layer_%d/fw" % (name, l), cell, [in_size], hidden, False,
-                           forget_bias)]
+                           forget_bias, logical_in=logical)]
       if bidirectional:
         dirs.append(RNNDirection(store, "%s/layer_%d/bw" % (name, l), cell, [in_size], hidden,
-                                 True, forget_bias))
+                                 True, forget_bias, logical_in=logical))
       self.layers.append(dirs)
       in_size = hidden * self.ndir
     self.output_dim = in_size
 
+  def _padded(self, x, tape):
+    """x [B,T,In] with zero columns up to the next multiple of 8 (the first layer's kernels are zero there)."""
+    n = self.input_size
+    wide = Act(torch.nn.functional.pad(x.data, (0, self.input_pad)), x.lens, requires_grad=x.requires_grad)
+    if tape is not None and x.requires_grad:
+      def backward():
+        g = x.grad_buffer()
+        if x.grad_init:
+          g += wide.grad[:, :, :n]
+        else:
+          g.copy_(wide.grad[:, :, :n])
+        x.grad_init = True
+        wide.grad = None
+
+      tape.record(backward)
+    return wide
+
   def forward(self, x, lens, tape, keep_prob=1.0, seeds=None):
     """x: Act [B,T,In] -> Act [B,T,ndir*H]."""
     H = self.H
-    cur = x
+    cur = self._padded(x, tape) if self.input_pad else x
     for li, dirs in enumerate(self.layers):
       B, T, _ = cur.data.shape
       ybuf = (torch.zeros if lens is not None else torch.empty)(

@@ -14,6 +14,8 @@ reference's variable name, in the reference's layout:
   shared embedding device [1, V, D]            -> embedding_and_softmax/weights [V, D]
   depthwise       device [K, C]                -> separable_conv1d depthwise_kernel [K, C, 1]
   BatchNorm       gamma / beta / moving_mean / moving_variance  (fp32, as is)
+  padded widths   output layers padded to an MFMA-friendly width (logical_out) and the first recurrent layer of a
+                  narrow input (logical_in: 13 MFCCs -> 16 columns) are written with the reference's logical shape
   LSTM cell       device wx_0 [1, 4H, in0], wx_1 ..., wh [1, 4H, H] (or kernel_inputs +
                   kernel_attention_state)      -> ONE lstm_cell/kernel [in0 + in1 + ... + H, 4H] per cell
                   (rows: the cell's inputs in order, then h; gate order i, j, f, o on both sides), under the
@@ -248,6 +250,14 @@ def cudnn_groups(params):
   return {k: v for k, v in groups.items() if len(v) == 4}
 
 
+def _logical_in(p):
+  """Real input width of an input kernel [1, G H, in]: narrower than the stored one when the layer zero-pads its
+  input to the GEMMs' multiple of 8 (13 MFCCs into DeepSpeech2's first recurrent layer, parts/rnns/rnn_layers.py).
+  Checkpoints carry the logical shape, [13 + H, 4 H] there."""
+  n = getattr(p, "logical_in", None)
+  return p.shape[2] if n is None else n
+
+
 def cudnn_canonical_prefix(scope, layer, tag, bidirectional, gates):
   cell = "cudnn_compatible_gru_cell" if gates == 3 else "cudnn_compatible_lstm_cell"
   if bidirectional:
@@ -329,6 +339,7 @@ def model_variables(model):
   bidir = {scope for scope, _, tag in cgroups if tag == "bw"}
   for (scope, layer, tag), parts in cgroups.items():
     dev = {k: parts[k].master.detach().cpu().numpy() for k in parts}
+    dev["wx_0"] = dev["wx_0"][:, :, :_logical_in(parts["wx_0"])]      # a zero-padded input: the real columns
     gates = parts["wh"].shape[1] // parts["wh"].shape[2]
     prefix = cudnn_canonical_prefix(scope, layer, tag, scope in bidir, gates)
     for suffix, arr in cudnn_to_canonical(dev["wx_0"], dev["wh"], dev["bias"], dev["bias_h"]).items():
@@ -455,7 +466,7 @@ def load(model, prefix, restore_optimizer=True, strict=True):
   bidir = {scope for scope, _, tag in cgroups if tag == "bw"}
   for (scope, layer, tag), parts in cgroups.items():
     H = parts["wh"].shape[2]
-    gates, n_in = parts["wh"].shape[1] // H, parts["wx_0"].shape[2]
+    gates, n_in = parts["wh"].shape[1] // H, _logical_in(parts["wx_0"])
     prefix = cudnn_canonical_prefix(scope, layer, tag, scope in bidir, gates)
 
     def get(suffix, prefix=prefix):
@@ -467,6 +478,9 @@ def load(model, prefix, restore_optimizer=True, strict=True):
     if got is not None:               # else: the per-parameter names of this repository's older files, below
       for key, a in zip(("wx_0", "wh", "bias", "bias_h"), got):
         split[parts[key].name] = a
+      wx = np.zeros(parts["wx_0"].shape, np.float32)      # zero columns of a padded input width
+      wx[:, :, :n_in] = split[parts["wx_0"].name]
+      split[parts["wx_0"].name] = wx
   for p in store.params:
     a = split.get(p.name)
     if a is None:
