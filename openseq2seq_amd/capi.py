@@ -829,20 +829,27 @@ def conv_weight_dgrad_copy(w16, wt16, descs, total_tiles):
 # --------------------------------------------------------------------------
 # log-mel front end
 # --------------------------------------------------------------------------
+def _feature_buffers(signal, F, t_ws, tpad, want_f32, workspace_bytes_fn):
+  """What every front-end wrapper allocates for a [B,Nmax] float32|int16 signal: (workspace, its size, features bf16
+  [B,tpad,F], fp32 copy or None, frames int32 [B]); t_ws: the frame count the workspace is sized for."""
+  B, dev = signal.shape[0], signal.device
+  assert signal.dtype in (torch.int16, torch.float32)
+  nbytes = int(workspace_bytes_fn(B, t_ws, F))
+  ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+  out = torch.empty((B, tpad, F), dtype=torch.bfloat16, device=dev)
+  out32 = torch.empty((B, tpad, F), dtype=torch.float32, device=dev) if want_f32 else None
+  olen = torch.empty((B,), dtype=torch.int32, device=dev)
+  return ws, nbytes, out, out32, olen
+
+
 def logmel(signal, n_samples, window, mel_start, mel_len, mel_wt, *, hop, n_mels, tmax, tpad,
            preemph=0.97, dither=0.0, seed=0, fixed_gain=-1.0, log_floor=1e-20,
            norm_per_feature=True, want_f32=False, n_fft=512):
   """signal [B,Nmax] float32|int16 -> (features bf16 [B,tpad,n_mels], frames int32 [B], f32|None)."""
   B, Nmax = signal.shape
-  dev = signal.device
-  is_i16 = signal.dtype == torch.int16
-  assert is_i16 or signal.dtype == torch.float32
-  nbytes = int(_lib.C.os2s_logmel_workspace_bytes(B, tmax, n_mels))
-  ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
-  out = torch.empty((B, tpad, n_mels), dtype=torch.bfloat16, device=dev)
-  out32 = torch.empty((B, tpad, n_mels), dtype=torch.float32, device=dev) if want_f32 else None
-  olen = torch.empty((B,), dtype=torch.int32, device=dev)
-  _lib.C.os2s_logmel(_stream(), _ptr(signal), _ptr(n_samples, torch.int32), int(is_i16), B, Nmax,
+  ws, nbytes, out, out32, olen = _feature_buffers(signal, n_mels, tmax, tpad, want_f32,
+                                                  _lib.C.os2s_logmel_workspace_bytes)
+  _lib.C.os2s_logmel(_stream(), _ptr(signal), _ptr(n_samples, torch.int32), int(signal.dtype == torch.int16), B, Nmax,
                      n_fft, hop, n_mels, _ptr(window, torch.float32), _ptr(mel_start, torch.int32),
                      _ptr(mel_len, torch.int32), _ptr(mel_wt, torch.float32), mel_wt.shape[0],
                      float(preemph), float(dither), int(seed) & (2**64 - 1), float(fixed_gain),
@@ -855,17 +862,11 @@ def psf_spectrogram(signal, n_samples, *, n_win, n_step, pad_to, num_features, t
   """signal [B,Nmax] float32|int16 -> (features bf16 [B,tpad,F], frames int32 [B], f32|None): the psf
   backend's 'spectrogram' features (os2s_psf_spectrogram)."""
   B, Nmax = signal.shape
-  dev = signal.device
-  is_i16 = signal.dtype == torch.int16
-  assert is_i16 or signal.dtype == torch.float32
-  nbytes = int(_lib.C.os2s_psf_spectrogram_workspace_bytes(B, tpad, num_features))
-  ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
-  out = torch.empty((B, tpad, num_features), dtype=torch.bfloat16, device=dev)
-  out32 = torch.empty((B, tpad, num_features), dtype=torch.float32, device=dev) if want_f32 else None
-  olen = torch.empty((B,), dtype=torch.int32, device=dev)
-  _lib.C.os2s_psf_spectrogram(_stream(), _ptr(signal), int(is_i16), _ptr(n_samples, torch.int32), B, Nmax, n_win,
-                              n_step, pad_to, num_features, tpad, _ptr(out), _ptr(out32, None, True), _ptr(olen),
-                              _ptr(ws), nbytes)
+  ws, nbytes, out, out32, olen = _feature_buffers(signal, num_features, tpad, tpad, want_f32,
+                                                  _lib.C.os2s_psf_spectrogram_workspace_bytes)
+  _lib.C.os2s_psf_spectrogram(_stream(), _ptr(signal), int(signal.dtype == torch.int16), _ptr(n_samples, torch.int32),
+                              B, Nmax, n_win, n_step, pad_to, num_features, tpad, _ptr(out), _ptr(out32, None, True),
+                              _ptr(olen), _ptr(ws), nbytes)
   return out, olen, out32
 
 
@@ -873,19 +874,13 @@ def psf_logfbank(signal, n_samples, fb, *, n_win, n_step, pad_to, nfft, tpad, wa
   """signal [B,Nmax] float32|int16, fb [nfilt, nfft/2+1] fp32 -> (features bf16 [B,tpad,nfilt], frames int32 [B],
   f32|None): the psf backend's 'logfbank' features (os2s_psf_logfbank)."""
   B, Nmax = signal.shape
-  dev = signal.device
-  is_i16 = signal.dtype == torch.int16
-  assert is_i16 or signal.dtype == torch.float32
   nfilt = fb.shape[0]
   assert fb.is_contiguous() and fb.shape[1] == nfft // 2 + 1
-  nbytes = int(_lib.C.os2s_psf_spectrogram_workspace_bytes(B, tpad, nfilt))
-  ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
-  out = torch.empty((B, tpad, nfilt), dtype=torch.bfloat16, device=dev)
-  out32 = torch.empty((B, tpad, nfilt), dtype=torch.float32, device=dev) if want_f32 else None
-  olen = torch.empty((B,), dtype=torch.int32, device=dev)
-  _lib.C.os2s_psf_logfbank(_stream(), _ptr(signal), int(is_i16), _ptr(n_samples, torch.int32), B, Nmax, n_win, n_step,
-                           pad_to, nfilt, nfft, _ptr(fb, torch.float32), tpad, _ptr(out), _ptr(out32, None, True),
-                           _ptr(olen), _ptr(ws), nbytes)
+  ws, nbytes, out, out32, olen = _feature_buffers(signal, nfilt, tpad, tpad, want_f32,
+                                                  _lib.C.os2s_psf_spectrogram_workspace_bytes)
+  _lib.C.os2s_psf_logfbank(_stream(), _ptr(signal), int(signal.dtype == torch.int16), _ptr(n_samples, torch.int32), B,
+                           Nmax, n_win, n_step, pad_to, nfilt, nfft, _ptr(fb, torch.float32), tpad, _ptr(out),
+                           _ptr(out32, None, True), _ptr(olen), _ptr(ws), nbytes)
   return out, olen, out32
 
 
@@ -893,33 +888,15 @@ def psf_mfcc(signal, n_samples, fb, dctl, *, n_win, n_step, pad_to, nfft, tpad, 
   """signal [B,Nmax] float32|int16, fb [nfilt, nfft/2+1] fp32, dctl [numcep, nfilt] fp32 (lifter x DCT-II) ->
   (features bf16 [B,tpad,numcep], frames int32 [B], f32|None): the psf backend's 'mfcc' features (os2s_psf_mfcc)."""
   B, Nmax = signal.shape
-  dev = signal.device
-  is_i16 = signal.dtype == torch.int16
-  assert is_i16 or signal.dtype == torch.float32
-  nfilt = fb.shape[0]
-  numcep = dctl.shape[0]
+  nfilt, numcep = fb.shape[0], dctl.shape[0]
   assert fb.is_contiguous() and fb.shape[1] == nfft // 2 + 1 and dctl.is_contiguous() and dctl.shape[1] == nfilt
-  nbytes = int(_lib.C.os2s_psf_spectrogram_workspace_bytes(B, tpad, numcep))
-  ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
-  out = torch.empty((B, tpad, numcep), dtype=torch.bfloat16, device=dev)
-  out32 = torch.empty((B, tpad, numcep), dtype=torch.float32, device=dev) if want_f32 else None
-  olen = torch.empty((B,), dtype=torch.int32, device=dev)
-  _lib.C.os2s_psf_mfcc(_stream(), _ptr(signal), int(is_i16), _ptr(n_samples, torch.int32), B, Nmax, n_win, n_step,
-                       pad_to, numcep, nfilt, nfft, _ptr(fb, torch.float32), _ptr(dctl, torch.float32), tpad,
-                       _ptr(out), _ptr(out32, None, True), _ptr(olen), _ptr(ws), nbytes)
+  ws, nbytes, out, out32, olen = _feature_buffers(signal, numcep, tpad, tpad, want_f32,
+                                                  _lib.C.os2s_psf_spectrogram_workspace_bytes)
+  _lib.C.os2s_psf_mfcc(_stream(), _ptr(signal), int(signal.dtype == torch.int16), _ptr(n_samples, torch.int32), B,
+                       Nmax, n_win, n_step, pad_to, numcep, nfilt, nfft, _ptr(fb, torch.float32),
+                       _ptr(dctl, torch.float32), tpad, _ptr(out), _ptr(out32, None, True), _ptr(olen), _ptr(ws),
+                       nbytes)
   return out, olen, out32
-
-
-def _librosa_buffers(signal, F, tmax, tpad, want_f32):
-  B, _ = signal.shape
-  dev = signal.device
-  assert signal.dtype in (torch.int16, torch.float32)
-  nbytes = int(_lib.C.os2s_librosa_features_workspace_bytes(B, tmax, F))
-  ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
-  out = torch.empty((B, tpad, F), dtype=torch.bfloat16, device=dev)
-  out32 = torch.empty((B, tpad, F), dtype=torch.float32, device=dev) if want_f32 else None
-  olen = torch.empty((B,), dtype=torch.int32, device=dev)
-  return ws, nbytes, out, out32, olen
 
 
 def librosa_mfcc(signal, n_samples, window, dct, *, win_length, hop, tmax, tpad, preemph=0.97, dither=0.0, seed=0,
@@ -931,7 +908,8 @@ def librosa_mfcc(signal, n_samples, window, dct, *, win_length, hop, tmax, tpad,
   n_fft, F = window.numel(), dct.shape[0]
   assert dct.is_contiguous() and dct.shape[1] == n_fft // 2 + 1
   assert all(t is None or t.numel() == F for t in (features_mean, features_std))
-  ws, nbytes, out, out32, olen = _librosa_buffers(signal, F, tmax, tpad, want_f32)
+  ws, nbytes, out, out32, olen = _feature_buffers(signal, F, tmax, tpad, want_f32,
+                                                  _lib.C.os2s_librosa_features_workspace_bytes)
   _lib.C.os2s_librosa_mfcc(_stream(), _ptr(signal), _ptr(n_samples, torch.int32), int(signal.dtype == torch.int16),
                            B, Nmax, n_fft, int(win_length), int(hop), F, _ptr(window, torch.float64),
                            _ptr(dct, torch.float64), float(preemph), float(dither), int(seed) & (2**64 - 1),
@@ -949,7 +927,8 @@ def librosa_spectrogram(signal, n_samples, window, *, hop, num_features, tmax, t
   B, Nmax = signal.shape
   n_win, F = window.numel(), int(num_features)
   assert all(t is None or t.numel() == F for t in (features_mean, features_std))
-  ws, nbytes, out, out32, olen = _librosa_buffers(signal, F, tmax, tpad, want_f32)
+  ws, nbytes, out, out32, olen = _feature_buffers(signal, F, tmax, tpad, want_f32,
+                                                  _lib.C.os2s_librosa_features_workspace_bytes)
   _lib.C.os2s_librosa_spectrogram(_stream(), _ptr(signal), _ptr(n_samples, torch.int32),
                                   int(signal.dtype == torch.int16), B, Nmax, n_win, int(hop), F,
                                   _ptr(window, torch.float64), float(dither), int(seed) & (2**64 - 1),

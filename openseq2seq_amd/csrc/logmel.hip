@@ -17,7 +17,7 @@
 //      a compact per-filter table (start, length, weights) — one mel bin per lane;
 //   3. per-utterance, per-feature mean / std (two-pass, fp64 accumulators) +
 //      normalise + bf16 store into the zero-padded [B, Tpad, F] batch.
-#include "os2s_common.hpp"
+#include "speech_frontend.hpp"
 #include <mutex>
 
 namespace os2s {
@@ -54,14 +54,6 @@ __device__ __forceinline__ void dft8(float (&r)[8], float (&i)[8]) {
     r[2 * m] = ar[m]; i[2 * m] = ai[m];
     r[2 * m + 1] = br[m]; i[2 * m + 1] = bi[m];
   }
-}
-
-__device__ __forceinline__ float gauss_noise(unsigned long long seed, int b, long long i) {
-  const uint32_t h1 = hash_u32(seed, ((unsigned long long)b << 40) ^ (unsigned long long)(2 * i));
-  const uint32_t h2 = hash_u32(seed, ((unsigned long long)b << 40) ^ (unsigned long long)(2 * i + 1));
-  const float u1 = ((float)(h1 >> 8) + 1.0f) * (1.0f / 16777217.0f);
-  const float u2 = (float)(h2 >> 8) * (1.0f / 16777216.0f);
-  return sqrtf(-2.f * logf(u1)) * cospif(2.f * u2);
 }
 
 struct LogmelArgs {
@@ -112,6 +104,8 @@ __global__ __launch_bounds__(256) void absmax_kernel(LogmelArgs p) {
   const long long lo = (long long)fb * kFB * p.hop;
   const long long hi = fb == p.nblk - 1 ? n : min(n, lo + (long long)kFB * p.hop);
   float m = 0.f;
+  // (the sample load is written out here and in the frames kernel: through load_sample both kernels compile to
+  // different code, and these are the timed ones)
   for (long long i = lo + threadIdx.x; i < hi; i += 256) {
     const float v = p.sample_is_int16 ? (float)reinterpret_cast<const int16_t*>(p.signal)[b * p.Nmax + i]
                                       : reinterpret_cast<const float*>(p.signal)[b * p.Nmax + i];
@@ -160,8 +154,7 @@ __global__ __launch_bounds__(256) void logmel_frames_kernel(LogmelArgs p) {
   }
   __syncthreads();
   auto pre = [&](long long pidx) -> float {   // pre-emphasised signal at reflect-padded index
-    long long i = pidx < 0 ? -pidx : (pidx >= N ? 2 * (N - 1) - pidx : pidx);
-    i = i < 0 ? 0 : (i >= N ? N - 1 : i);
+    const long long i = reflect_index(pidx, N);
     int k = (int)(i - s0);
     k = k < 0 ? 0 : (k >= L ? L - 1 : k);     // (never taken: the staged range covers every reflected index)
     const float sv = sig[k];
@@ -339,183 +332,20 @@ __global__ __launch_bounds__(256) void logmel_normalize_kernel(
 }
 
 
-// ---- the other two feature types of the librosa backend: 'mfcc' and 'spectrogram' ---------------------------------
-// (get_speech_features_librosa, speech_utils.py:354-417.) Neither is on a benchmarked path: one workgroup per
-// frame, a direct real DFT of the frame against a twiddle table in LDS (the 'spectrogram' transform length is
-// n_fft = win_length = int(sr * window_size) — 320 points at the defaults, not a power of two, and zero-padding
-// would move the bins), one thread per bin, everything after the fp32 sample arithmetic in fp64.
-//
-//   'spectrogram' (:367-381): gain -> dither -> stft(n_fft = win_length, centred reflect padding, window_fn) ->
-//       |.|^2, values <= 1e-30 raised to 1e-30 -> 10 log10 -> the first F bins. No pre-emphasis.
-//   'mfcc' (:383-395): gain -> dither -> pre-emphasis 0.97 -> stft(n_fft, win_length) -> S = |.|^2 ->
-//       librosa.feature.mfcc(sr, S = S, n_mfcc = F, n_mels = 2F). librosa uses a given S AS IT STANDS: the mel
-//       filter bank and power_to_db run only when S is None, and n_mels is ignored. The reference therefore
-//       computes  dct(S, axis = 0, type = 2, norm = 'ortho')[:F]  — the orthonormal DCT-II along the n_fft / 2 + 1
-//       LINEAR frequency bins of the POWER spectrum, with no mel scale and no logarithm — and so does this kernel
-//       (dct: the host's [F][n_fft / 2 + 1] table). A drop-in reproduces what the reference computes, not what
-//       the name suggests.
-// Both end as the 'logfbank' path does (:411-417): per-feature (norm_per_feature) or global mean / std over the
-// utterance's frames, each replaced by features_mean / features_std_dev when the configuration gives them.
-// The gain, the dither and the pre-emphasis are float32 operations in the reference too (it normalises
-// signal.astype(np.float32)); they are done here with the same roundings, so with dither = 0 the transform's
-// input is the reference's bit for bit.
-struct SpecArgs {
-  const void* signal;      // [B, Nmax] float32 or int16
-  const int32_t* n_samples;
-  int sample_is_int16;
-  int B;
-  long long Nmax;
-  int n_fft, win_length, hop, F;
-  int mfcc;                // 1: pre-emphasis + DCT projection of the power spectrum; 0: 10 log10 of the first F bins
-  const double* window;    // [n_fft]: window_fn(win_length), centred, zero padded
-  const double* dct;       // [F][n_fft / 2 + 1] (mfcc)
-  float preemph, dither, fixed_gain;
-  unsigned long long seed;
-  const float* absmax;     // [B]
-  double* plane;           // [B, Tmax, F] features before the normalisation
-  int Tmax;
-};
-
-__global__ __launch_bounds__(256) void spec_frames_kernel(SpecArgs p) {
-  extern __shared__ __attribute__((aligned(16))) double lds_spec[];
-  const int n_fft = p.n_fft, nbins = n_fft / 2 + 1;
-  double* const x = lds_spec;          // [n_fft] windowed frame
-  double* const cs = x + n_fft;        // [n_fft]
-  double* const sn = cs + n_fft;       // [n_fft]
-  double* const ps = sn + n_fft;       // [nbins] power spectrum
-  const int b = blockIdx.y, t = blockIdx.x, tid = threadIdx.x;
-  const long long N = min((long long)p.n_samples[b], p.Nmax);      // never past the row
-  const int Tb = 1 + (int)(N / p.hop);
-  if (t >= Tb || N < 1) return;                                     // (workgroup-uniform)
-  const float gain = p.fixed_gain > 0.f ? p.fixed_gain : 1.0f / (p.absmax[b] + 1e-5f);
-  auto sample = [&](long long i) -> float {
-    float v = p.sample_is_int16 ? (float)reinterpret_cast<const int16_t*>(p.signal)[b * p.Nmax + i]
-                                : reinterpret_cast<const float*>(p.signal)[b * p.Nmax + i];
-    v *= gain;
-    if (p.dither > 0.f) v += p.dither * gauss_noise(p.seed, b, i);
-    return v;
-  };
-  for (int j = tid; j < n_fft; j += 256) {
-    const double w = p.window[j];
-    double xv = 0.0;
-    if (w != 0.0) {
-      const long long pidx = (long long)t * p.hop - n_fft / 2 + j;   // index into the reflect-padded signal
-      long long i = pidx < 0 ? -pidx : (pidx >= N ? 2 * (N - 1) - pidx : pidx);
-      i = i < 0 ? 0 : (i >= N ? N - 1 : i);       // (clips shorter than n_fft / 2 + 1: undefined in the reference)
-      float v = sample(i);
-      if (p.mfcc && i > 0) v = __fsub_rn(v, __fmul_rn(p.preemph, sample(i - 1)));
-      xv = w * (double)v;
-    }
-    x[j] = xv;
-    sincospi(2.0 * (double)j / (double)n_fft, &sn[j], &cs[j]);
-  }
-  __syncthreads();
-  const int lo = (n_fft - p.win_length) / 2, hi = lo + p.win_length;   // the window's support
-  for (int k = tid; k < nbins; k += 256) {
-    double re = 0.0, im = 0.0;
-    int idx = (int)(((long long)k * lo) % n_fft);
-    for (int i = lo; i < hi; ++i) {
-      re += x[i] * cs[idx];
-      im -= x[i] * sn[idx];
-      idx += k;
-      if (idx >= n_fft) idx -= n_fft;
-    }
-    ps[k] = re * re + im * im;
-  }
-  __syncthreads();
-  double* const out = p.plane + ((long long)b * p.Tmax + t) * p.F;
-  for (int m = tid; m < p.F; m += 256) {
-    double v;
-    if (p.mfcc) {
-      v = 0.0;
-      const double* const d = p.dct + (long long)m * nbins;
-      for (int k = 0; k < nbins; ++k) v += d[k] * ps[k];
-    } else {
-      v = 10.0 * log10(fmax(ps[m], 1e-30));
-    }
-    out[m] = v;
-  }
-}
-
-constexpr int kSpecMaxF = 1024;
-
-// mean and 1 / std of one utterance, two passes over its plane in frame order (np.mean, np.std with ddof = 0):
-// per feature, or — norm_per_feature = 0 — one pair for the whole utterance (the per-feature sums added in
-// feature order). Given statistics replace the computed ones. stats [B][2][F].
-__global__ __launch_bounds__(256) void spec_stats_kernel(const double* __restrict__ plane,
-                                                         const int32_t* __restrict__ n_samples, long long Nmax, int hop,
-                                                         int Tmax, int F, int norm_per_feature,
-                                                         const double* __restrict__ given_mean,
-                                                         const double* __restrict__ given_std,
-                                                         double* __restrict__ stats) {
-  __shared__ double red[kSpecMaxF];
-  __shared__ double total;
-  const int b = blockIdx.x, tid = threadIdx.x;
-  const long long N = min((long long)n_samples[b], Nmax);
-  const int Tb = min(1 + (int)(N / hop), Tmax);
-  const double* const x = plane + (long long)b * Tmax * F;
-  for (int f = tid; f < F; f += 256) {
-    double s = 0.0;
-    for (int t = 0; t < Tb; ++t) s += x[(long long)t * F + f];
-    red[f] = s;
-  }
-  __syncthreads();
-  if (tid == 0 && !norm_per_feature) {
-    double s = 0.0;
-    for (int f = 0; f < F; ++f) s += red[f];
-    total = s / ((double)Tb * F);
-  }
-  __syncthreads();
-  double mu[kSpecMaxF / 256];
-  for (int f = tid, j = 0; f < F; f += 256, ++j) mu[j] = norm_per_feature ? red[f] / (double)Tb : total;
-  __syncthreads();
-  for (int f = tid, j = 0; f < F; f += 256, ++j) {
-    double s = 0.0;
-    for (int t = 0; t < Tb; ++t) {
-      const double d = x[(long long)t * F + f] - mu[j];
-      s += d * d;
-    }
-    red[f] = s;
-  }
-  __syncthreads();
-  if (tid == 0 && !norm_per_feature) {
-    double s = 0.0;
-    for (int f = 0; f < F; ++f) s += red[f];
-    total = s / ((double)Tb * F);
-  }
-  __syncthreads();
-  for (int f = tid, j = 0; f < F; f += 256, ++j) {
-    const double var = norm_per_feature ? red[f] / (double)Tb : total;
-    stats[((long long)b * 2 + 0) * F + f] = given_mean ? given_mean[f] : mu[j];
-    stats[((long long)b * 2 + 1) * F + f] = 1.0 / (given_std ? given_std[f] : sqrt(var));
-  }
-}
-
-__global__ __launch_bounds__(256) void spec_normalize_kernel(const double* __restrict__ plane,
-                                                             const double* __restrict__ stats,
-                                                             const int32_t* __restrict__ n_samples, long long Nmax,
-                                                             int hop, int Tmax, int Tpad, int F,
-                                                             bf16_t* __restrict__ out_bf16, float* __restrict__ out_f32,
-                                                             int32_t* __restrict__ out_len) {
-  const int b = blockIdx.y, tid = threadIdx.x;
-  const long long N = min((long long)n_samples[b], Nmax);
-  const int Tb = min(1 + (int)(N / hop), Tmax);
-  const long long per = (long long)Tpad * F;
-  for (long long i = (long long)blockIdx.x * 256 + tid; i < per; i += (long long)gridDim.x * 256) {
-    const int t = (int)(i / F), f = (int)(i - (long long)t * F);
-    float v = 0.f;
-    if (t < Tb)
-      v = (float)((plane[((long long)b * Tmax + t) * F + f] - stats[((long long)b * 2 + 0) * F + f]) *
-                  stats[((long long)b * 2 + 1) * F + f]);
-    out_bf16[(long long)b * per + i] = f2bf(v);
-    if (out_f32) out_f32[(long long)b * per + i] = v;
-  }
-  if (blockIdx.x == 0 && tid == 0) out_len[b] = Tb;
-}
-
 }  // namespace os2s
 
 using namespace os2s;
+
+// The max |x| pass from explicit arguments: absmax_kernel reads exactly the fields set here.
+int os2s::launch_absmax(hipStream_t stream, const void* signal, const int32_t* n_samples, int sample_is_int16, int B,
+                        long long Nmax, int hop, int nblk, float* absmax) {
+  LogmelArgs a = {};
+  a.signal = signal; a.n_samples = n_samples; a.sample_is_int16 = sample_is_int16; a.B = B; a.Nmax = Nmax;
+  a.hop = hop; a.nblk = nblk; a.absmax = absmax;
+  if (hipMemsetAsync(absmax, 0, (size_t)B * 4, stream) != hipSuccess) return OS2S_ERR_LAUNCH;
+  OS2S_LAUNCH(absmax_kernel, dim3(ceil_div(nblk * B, 8) * 8), dim3(256), 0, stream, a);
+  return OS2S_OK;
+}
 
 static int logmel_nblk(int Tmax, int Tpad) { return os2s::ceil_div(Tpad > Tmax ? Tpad : Tmax, os2s::kFB); }
 
@@ -557,8 +387,8 @@ extern "C" int os2s_logmel(os2s_stream_t stream_, const void* signal, const int3
   a.seed = seed; a.absmax = absmax; a.raw = raw; a.partial = partial; a.Tmax = Tmax; a.nblk = nblk;
   const int units = ceil_div(nblk * B, 8) * 8;
   if (fixed_gain <= 0.f) {
-    if (hipMemsetAsync(absmax, 0, (size_t)B * 4, stream) != hipSuccess) return OS2S_ERR_LAUNCH;
-    OS2S_LAUNCH(absmax_kernel, dim3(units), dim3(256), 0, stream, a);
+    const int rc = launch_absmax(stream, signal, n_samples, sample_is_int16, B, Nmax, hop, nblk, absmax);
+    if (rc != OS2S_OK) return rc;
   }
   const size_t smem = (size_t)(4 * (2 * 576 + 2 * 260) + kFB * hop + 768) * 4;
   static std::once_flag once;
@@ -573,78 +403,4 @@ extern "C" int os2s_logmel(os2s_stream_t stream_, const void* signal, const int3
   OS2S_LAUNCH(logmel_normalize_kernel, dim3(units), dim3(256), 0, stream, raw, stats, n_samples, Nmax, hop,
               Tmax, Tpad, nblk, B, n_mels, out_bf16, out_f32, out_len);
   return OS2S_OK;
-}
-
-// ---- 'mfcc' and 'spectrogram' of the librosa backend (spec_frames_kernel) -----------------------------------------
-extern "C" size_t os2s_librosa_features_workspace_bytes(int B, int Tmax, int F) {
-  // fp64 plane | max |x| per utterance | mean, 1 / std per utterance and feature
-  return (size_t)B * Tmax * F * 8 + ((size_t)B * 4 + 255) / 256 * 256 + (size_t)B * 2 * F * 8 + 256;
-}
-
-static int librosa_features(hipStream_t stream, const void* signal, const int32_t* n_samples, int sample_is_int16,
-                            int B, long long Nmax, int n_fft, int win_length, int hop, int F, int mfcc,
-                            const double* window, const double* dct, float preemph, float dither,
-                            unsigned long long seed, float fixed_gain, int norm_per_feature,
-                            const double* features_mean, const double* features_std, int Tmax, int Tpad,
-                            uint16_t* out_bf16, float* out_f32, int32_t* out_len, void* workspace,
-                            size_t workspace_bytes) {
-  OS2S_REQUIRE(signal && n_samples && window && out_bf16 && out_len && workspace && (dct || !mfcc));
-  OS2S_REQUIRE(B >= 1 && Nmax >= 1 && hop >= 1 && Tmax >= 1 && Tpad >= Tmax && F >= 1);
-  OS2S_REQUIRE(n_fft >= 16 && win_length >= 1 && win_length <= n_fft);
-  const int nbins = n_fft / 2 + 1;
-  const size_t smem = ((size_t)3 * n_fft + nbins) * sizeof(double);
-  if (F > kSpecMaxF || smem > 48 * 1024) return OS2S_ERR_UNSUPPORTED;
-  if (workspace_bytes < os2s_librosa_features_workspace_bytes(B, Tmax, F)) return OS2S_ERR_WORKSPACE;
-  char* w = (char*)workspace;
-  double* plane = (double*)w;
-  w += (size_t)B * Tmax * F * 8;
-  float* absmax = (float*)w;
-  w += ((size_t)B * 4 + 255) / 256 * 256;
-  double* stats = (double*)w;
-  if (fixed_gain <= 0.f) {
-    // the log-mel path's max |x| pass over the same (utterance, block of 32 frames) units
-    LogmelArgs a = {};
-    a.signal = signal; a.n_samples = n_samples; a.sample_is_int16 = sample_is_int16; a.B = B; a.Nmax = Nmax;
-    a.hop = hop; a.absmax = absmax; a.nblk = ceil_div(Tmax, kFB);
-    if (hipMemsetAsync(absmax, 0, (size_t)B * 4, stream) != hipSuccess) return OS2S_ERR_LAUNCH;
-    OS2S_LAUNCH(absmax_kernel, dim3(ceil_div(a.nblk * B, 8) * 8), dim3(256), 0, stream, a);
-  }
-  SpecArgs s;
-  s.signal = signal; s.n_samples = n_samples; s.sample_is_int16 = sample_is_int16; s.B = B; s.Nmax = Nmax;
-  s.n_fft = n_fft; s.win_length = win_length; s.hop = hop; s.F = F; s.mfcc = mfcc; s.window = window; s.dct = dct;
-  s.preemph = preemph; s.dither = dither; s.fixed_gain = fixed_gain; s.seed = seed; s.absmax = absmax;
-  s.plane = plane; s.Tmax = Tmax;
-  OS2S_LAUNCH(spec_frames_kernel, dim3(Tmax, B), dim3(256), smem, stream, s);
-  OS2S_LAUNCH(spec_stats_kernel, dim3(B), dim3(256), 0, stream, plane, n_samples, Nmax, hop, Tmax, F,
-              norm_per_feature, features_mean, features_std, stats);
-  OS2S_LAUNCH(spec_normalize_kernel, dim3(64, B), dim3(256), 0, stream, plane, stats, n_samples, Nmax, hop, Tmax,
-              Tpad, F, out_bf16, out_f32, out_len);
-  return OS2S_OK;
-}
-
-extern "C" int os2s_librosa_mfcc(os2s_stream_t stream, const void* signal, const int32_t* n_samples,
-                                 int sample_is_int16, int B, long long Nmax, int n_fft, int win_length, int hop,
-                                 int n_mfcc, const double* window, const double* dct, float preemph, float dither,
-                                 unsigned long long seed, float fixed_gain, int norm_per_feature,
-                                 const double* features_mean, const double* features_std, int Tmax, int Tpad,
-                                 uint16_t* out_bf16, float* out_f32, int32_t* out_len, void* workspace,
-                                 size_t workspace_bytes) {
-  OS2S_REQUIRE(n_mfcc <= n_fft / 2 + 1);
-  return librosa_features((hipStream_t)stream, signal, n_samples, sample_is_int16, B, Nmax, n_fft, win_length, hop,
-                          n_mfcc, 1, window, dct, preemph, dither, seed, fixed_gain, norm_per_feature, features_mean,
-                          features_std, Tmax, Tpad, out_bf16, out_f32, out_len, workspace, workspace_bytes);
-}
-
-extern "C" int os2s_librosa_spectrogram(os2s_stream_t stream, const void* signal, const int32_t* n_samples,
-                                        int sample_is_int16, int B, long long Nmax, int n_win, int hop,
-                                        int num_features, const double* window, float dither,
-                                        unsigned long long seed, float fixed_gain, int norm_per_feature,
-                                        const double* features_mean, const double* features_std, int Tmax,
-                                        int Tpad, uint16_t* out_bf16, float* out_f32, int32_t* out_len,
-                                        void* workspace, size_t workspace_bytes) {
-  OS2S_REQUIRE(num_features <= n_win / 2 + 1);      // the reference's assertion (speech_utils.py:377-378)
-  return librosa_features((hipStream_t)stream, signal, n_samples, sample_is_int16, B, Nmax, n_win, n_win, hop,
-                          num_features, 0, window, nullptr, 0.f, dither, seed, fixed_gain, norm_per_feature,
-                          features_mean, features_std, Tmax, Tpad, out_bf16, out_f32, out_len, workspace,
-                          workspace_bytes);
 }

@@ -10,7 +10,7 @@
 // to reach a multiple of pad_to (-300 dB rows) DO enter mean and std, as in the reference.
 // n_win = 320 is not a power of two: direct real DFT in fp32 with the twiddles in LDS, one
 // workgroup per frame, one thread per bin (a data-layer op: ~51 k MAC per frame).
-#include "os2s_common.hpp"
+#include "speech_frontend.hpp"
 
 namespace os2s {
 
@@ -22,15 +22,26 @@ __global__ __launch_bounds__(256) void psf_absmax_kernel(const void* __restrict_
   const int b = blockIdx.x;
   const int n = (int)min((long long)n_samples[b], sig_stride);   // never past the row (as logmel.hip)
   float m = 0.f;
-  for (int i = threadIdx.x; i < n; i += 256) {
-    const float v = is_i16 ? (float)reinterpret_cast<const int16_t*>(signal)[(long long)b * sig_stride + i]
-                           : reinterpret_cast<const float*>(signal)[(long long)b * sig_stride + i];
-    m = fmaxf(m, fabsf(v));
-  }
+  for (int i = threadIdx.x; i < n; i += 256)
+    m = fmaxf(m, fabsf(load_sample(signal, is_i16, (long long)b * sig_stride + i)));
   m = wave_max(m);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
   __syncthreads();
   if (threadIdx.x == 0) gain[b] = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3])) + 1e-5f;
+}
+
+// s16 of the header: sample `index` over d = max|x| + 1e-5, times 32767, astype(np.int16) (toward zero)
+__device__ __forceinline__ float psf_s16(const void* signal, int is_i16, long long index, float d) {
+  return truncf((load_sample(signal, is_i16, index) / d) * 32767.0f);
+}
+
+// What both frame kernels open with: frame 0 publishes the utterance's frame count (pad_to rounding included), and
+// a frame past that count writes zero partials and is done (false).
+__device__ __forceinline__ bool psf_frame_begin(const PsfFrames& fc, int b, int t, int32_t* frames_out, double* slot) {
+  if (t == 0 && threadIdx.x == 0) frames_out[b] = fc.padded;
+  if (t < fc.padded) return true;
+  if (threadIdx.x == 0) slot[0] = slot[1] = 0.0;
+  return false;
 }
 
 // frames_out[b] = frames of utterance b incl. the pad_to rounding; plane[b, t, :] = lps; per-frame
@@ -46,58 +57,29 @@ __global__ __launch_bounds__(256) void psf_logpowspec_kernel(
   __shared__ double red[2][4];
   const int b = blockIdx.y, t = blockIdx.x, tid = threadIdx.x;
   const int n = (int)min((long long)n_samples[b], sig_stride);   // never past the row
-  int frames = n <= n_win ? 1 : 1 + (n - n_win + n_step - 1) / n_step;
-  if (pad_to > 0 && frames % pad_to) frames += pad_to - frames % pad_to;
-  if (t == 0 && tid == 0) frames_out[b] = frames;
-  if (t >= frames) {
-    if (tid == 0) { partial[((long long)b * T + t) * 2] = 0.0; partial[((long long)b * T + t) * 2 + 1] = 0.0; }
-    return;
-  }
+  double* const slot = partial + ((long long)b * T + t) * 2;
+  if (!psf_frame_begin(psf_frame_count(n, n_win, n_step, pad_to), b, t, frames_out, slot)) return;
   const float d = denom[b];
   for (int i = tid; i < n_win; i += 256) {
     const long long j = (long long)t * n_step + i;
-    float v = 0.f;
-    if (j < n) {
-      const float raw = is_i16 ? (float)reinterpret_cast<const int16_t*>(signal)[(long long)b * sig_stride + j]
-                               : reinterpret_cast<const float*>(signal)[(long long)b * sig_stride + j];
-      v = truncf((raw / d) * 32767.0f);                       // astype(np.int16): toward zero
-    }
+    const float v = j < n ? psf_s16(signal, is_i16, (long long)b * sig_stride + j, d) : 0.f;
     // np.hanning(M)[i] = 0.5 - 0.5 cos(2 pi i / (M - 1))
     const float w = 0.5f - 0.5f * cospif(2.0f * (float)i / (float)(n_win - 1));
     x[i] = v * w;
-    float s, c;
-    sincospif(2.0f * (float)i / (float)n_win, &s, &c);
-    cs[i] = c;
-    sn[i] = s;
   }
+  fill_twiddles(cs, sn, n_win);
   __syncthreads();
   double s1 = 0.0, s2 = 0.0;
   for (int k = tid; k < F; k += 256) {
-    float re = 0.f, im = 0.f;
-    int idx = 0;
-    for (int i = 0; i < n_win; ++i) {
-      re += x[i] * cs[idx];
-      im -= x[i] * sn[idx];
-      idx += k;
-      if (idx >= n_win) idx -= n_win;
-    }
+    float re, im;
+    dft_bin(x, cs, sn, 0, n_win, k, n_win, re, im);
     const float ps = fmaxf((re * re + im * im) / (float)n_win, 1e-30f);
     const float lps = 10.0f * log10f(ps);
     plane[((long long)b * T + t) * F + k] = lps;
     s1 += (double)lps;
     s2 += (double)lps * (double)lps;
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    s1 += __shfl_xor(s1, o, 64);
-    s2 += __shfl_xor(s2, o, 64);
-  }
-  if ((tid & 63) == 0) { red[0][tid >> 6] = s1; red[1][tid >> 6] = s2; }
-  __syncthreads();
-  if (tid == 0) {
-    partial[((long long)b * T + t) * 2] = (red[0][0] + red[0][1]) + (red[0][2] + red[0][3]);
-    partial[((long long)b * T + t) * 2 + 1] = (red[1][0] + red[1][1]) + (red[1][2] + red[1][3]);
-  }
+  emit_frame_partial(s1, s2, red, slot);
 }
 
 // mean / std over the utterance (fixed summation order), then (x - mean) / std -> bf16 (+ fp32)
@@ -164,49 +146,28 @@ __global__ __launch_bounds__(256) void psf_logfbank_kernel(
   const int b = blockIdx.y, t = blockIdx.x, tid = threadIdx.x;
   const int nbins = nfft / 2 + 1;
   const int n = (int)min((long long)n_samples[b], sig_stride);
-  int frames = n <= n_win ? 1 : 1 + (n - n_win + n_step - 1) / n_step;
-  if (pad_to > 0 && frames % pad_to) frames += pad_to - frames % pad_to;
-  if (t == 0 && tid == 0) frames_out[b] = frames;
-  if (t >= frames) {
-    if (tid == 0) { partial[((long long)b * T + t) * 2] = 0.0; partial[((long long)b * T + t) * 2 + 1] = 0.0; }
-    return;
-  }
+  const PsfFrames fc = psf_frame_count(n, n_win, n_step, pad_to);
+  double* const slot = partial + ((long long)b * T + t) * 2;
+  if (!psf_frame_begin(fc, b, t, frames_out, slot)) return;
   const float d = denom[b];
   auto s16 = [&](long long j) -> float {
-    if (j < 0 || j >= n) return 0.f;
-    const float raw = is_i16 ? (float)reinterpret_cast<const int16_t*>(signal)[(long long)b * sig_stride + j]
-                             : reinterpret_cast<const float*>(signal)[(long long)b * sig_stride + j];
-    return truncf((raw / d) * 32767.0f);                      // astype(np.int16): toward zero
+    return j < 0 || j >= n ? 0.f : psf_s16(signal, is_i16, (long long)b * sig_stride + j, d);
   };
   // the reference pads the SIGNAL (by whole strides, to the pad_to frame count) before psf.logfbank runs its
   // pre-emphasis over it; framesig then zero-pads the pre-emphasised signal to complete the last frame. So
   // y[n] = -0.97 s16[n-1] exists only when that signal padding happened (plen > n), and y[j] = 0 past plen.
-  long long plen = n;
-  {
-    const int length = n <= n_win ? 1 : 1 + (n - n_win + n_step - 1) / n_step;   // 1 + ceil((n - n_win) / n_step)
-    // (python: 1 + int(ceil((n - n_win) / n_step)) is <= 1 for n <= n_win: ceil of a non-positive quotient;
-    // for n < n_win - n_step it is <= 0 — such clips (< 10 ms) do not occur: frames >= 1 is kept)
-    if (pad_to > 0 && length % pad_to) plen = (long long)n + (long long)(pad_to - length % pad_to) * n_step;
-  }
+  // (python: 1 + int(ceil((n - n_win) / n_step)) is <= 1 for n <= n_win: ceil of a non-positive quotient;
+  // for n < n_win - n_step it is <= 0 — such clips (< 10 ms) do not occur: frames >= 1 is kept)
+  const long long plen = (long long)n + (long long)(fc.padded - fc.live) * n_step;
   for (int i = tid; i < n_win; i += 256) {
     const long long j = (long long)t * n_step + i;
     x[i] = j >= plen ? 0.f : (j == 0 ? s16(0) : s16(j) - 0.97f * s16(j - 1));
   }
-  for (int i = tid; i < nfft; i += 256) {
-    float s, c;
-    sincospif(2.0f * (float)i / (float)nfft, &s, &c);
-    cs[i] = c;
-    sn[i] = s;
-  }
+  fill_twiddles(cs, sn, nfft);
   __syncthreads();
   for (int k = tid; k < nbins; k += 256) {
-    float re = 0.f, im = 0.f;
-    int idx = 0;
-    for (int i = 0; i < n_win; ++i) {
-      re += x[i] * cs[idx];
-      im -= x[i] * sn[idx];
-      idx = (idx + k) & (nfft - 1);
-    }
+    float re, im;
+    dft_bin(x, cs, sn, 0, n_win, k, nfft, re, im);
     ps[k] = (re * re + im * im) / (float)nfft;
   }
   __syncthreads();
@@ -235,36 +196,31 @@ __global__ __launch_bounds__(256) void psf_logfbank_kernel(
       s2 += (double)c * (double)c;
     }
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    s1 += __shfl_xor(s1, o, 64);
-    s2 += __shfl_xor(s2, o, 64);
-  }
-  if ((tid & 63) == 0) { red[0][tid >> 6] = s1; red[1][tid >> 6] = s2; }
-  __syncthreads();
-  if (tid == 0) {
-    partial[((long long)b * T + t) * 2] = (red[0][0] + red[0][1]) + (red[0][2] + red[0][3]);
-    partial[((long long)b * T + t) * 2 + 1] = (red[1][0] + red[1][1]) + (red[1][2] + red[1][3]);
-  }
+  emit_frame_partial(s1, s2, red, slot);
 }
 
 }  // namespace os2s
 
 using namespace os2s;
 
-// 'logfbank' of the psf backend (see psf_logfbank_kernel): fb = [nfilt][nfft/2 + 1] fp32 filter table on the
-// device (python_speech_features.get_filterbanks; the host layer builds it). nfft: a power of two >= n_win.
-// Workspace as os2s_psf_spectrogram_workspace_bytes(B, Tpad, nfilt).
-extern "C" int os2s_psf_logfbank(os2s_stream_t stream_, const void* signal, int sample_is_int16,
-                                 const int32_t* n_samples, int B, long long Nmax, int n_win, int n_step,
-                                 int pad_to, int nfilt, int nfft, const float* fb, int Tpad,
-                                 uint16_t* out_bf16, float* out_f32, int32_t* out_len, void* workspace,
-                                 size_t workspace_bytes) {
-  OS2S_REQUIRE(signal && n_samples && fb && out_bf16 && out_len && workspace);
-  OS2S_REQUIRE(B >= 1 && n_win >= 16 && n_step >= 1 && Tpad >= 1 && nfilt >= 1 && nfilt <= 4096);
-  OS2S_REQUIRE(nfft >= n_win && (nfft & (nfft - 1)) == 0);
-  if (workspace_bytes < os2s_psf_spectrogram_workspace_bytes(B, Tpad, nfilt)) return OS2S_ERR_WORKSPACE;
-  const size_t lds = ((size_t)n_win + 2 * (size_t)nfft + nfft / 2 + 1) * sizeof(float);
+extern "C" size_t os2s_psf_spectrogram_workspace_bytes(int B, int T, int F) {
+  return (size_t)B * 4 + (size_t)B * T * F * 4 + (size_t)B * T * 2 * 8 + 64;
+}
+
+// The three feature types of the psf backend share everything but the frame kernel: max |x| -> frames (plane of
+// F features per frame + per-frame partial sums) -> utterance mean / std and store. Workspace: denom | partial | plane.
+enum PsfMode { kPsfSpectrogram, kPsfLogfbank, kPsfMfcc };
+
+static int psf_features(os2s_stream_t stream_, PsfMode mode, const void* signal, int sample_is_int16,
+                        const int32_t* n_samples, int B, long long Nmax, int n_win, int n_step, int pad_to, int F,
+                        int nfilt, int nfft, const float* fb, const float* dctl, int Tpad, uint16_t* out_bf16,
+                        float* out_f32, int32_t* out_len, void* workspace, size_t workspace_bytes) {
+  OS2S_REQUIRE(signal && n_samples && out_bf16 && out_len && workspace);
+  OS2S_REQUIRE(B >= 1 && n_win >= 16 && n_step >= 1 && Tpad >= 1 && F >= 1);
+  if (mode != kPsfSpectrogram) OS2S_REQUIRE(fb && nfilt >= 1 && nfilt <= 4096 && nfft >= n_win && (nfft & (nfft - 1)) == 0);
+  if (workspace_bytes < os2s_psf_spectrogram_workspace_bytes(B, Tpad, F)) return OS2S_ERR_WORKSPACE;
+  const size_t lds = sizeof(float) * (mode == kPsfSpectrogram ? (size_t)3 * n_win
+                                      : (size_t)n_win + 2 * (size_t)nfft + nfft / 2 + 1 + (mode == kPsfMfcc ? nfilt : 0));
   if (lds > 48 * 1024) return OS2S_ERR_UNSUPPORTED;
   hipStream_t stream = (hipStream_t)stream_;
   char* ws = reinterpret_cast<char*>(workspace);
@@ -274,70 +230,53 @@ extern "C" int os2s_psf_logfbank(os2s_stream_t stream_, const void* signal, int 
   off += (size_t)B * Tpad * 2 * 8;
   float* plane = reinterpret_cast<float*>(ws + off);
   OS2S_LAUNCH(psf_absmax_kernel, dim3(B), dim3(256), 0, stream, signal, sample_is_int16, Nmax, n_samples, denom);
-  OS2S_LAUNCH(psf_logfbank_kernel<false>, dim3(Tpad, B), dim3(256), lds, stream, signal, sample_is_int16, Nmax,
-              n_samples, denom, n_win, n_step, pad_to, nfilt, nfft, fb, (const float*)nullptr, 0, Tpad, plane, partial,
-              out_len);
-  OS2S_LAUNCH(psf_normalize_kernel, dim3(64, B), dim3(256), 0, stream, plane, partial, out_len, nfilt, Tpad,
-              out_bf16, out_f32);
+  if (mode == kPsfSpectrogram)
+    OS2S_LAUNCH(psf_logpowspec_kernel, dim3(Tpad, B), dim3(256), lds, stream, signal, sample_is_int16, Nmax,
+                n_samples, denom, n_win, n_step, pad_to, F, Tpad, plane, partial, out_len);
+  else if (mode == kPsfLogfbank)
+    OS2S_LAUNCH(psf_logfbank_kernel<false>, dim3(Tpad, B), dim3(256), lds, stream, signal, sample_is_int16, Nmax,
+                n_samples, denom, n_win, n_step, pad_to, nfilt, nfft, fb, (const float*)nullptr, 0, Tpad, plane,
+                partial, out_len);
+  else
+    OS2S_LAUNCH(psf_logfbank_kernel<true>, dim3(Tpad, B), dim3(256), lds, stream, signal, sample_is_int16, Nmax,
+                n_samples, denom, n_win, n_step, pad_to, nfilt, nfft, fb, dctl, F, Tpad, plane, partial, out_len);
+  OS2S_LAUNCH(psf_normalize_kernel, dim3(64, B), dim3(256), 0, stream, plane, partial, out_len, F, Tpad, out_bf16,
+              out_f32);
   return OS2S_OK;
+}
+
+extern "C" int os2s_psf_spectrogram(os2s_stream_t stream, const void* signal, int sample_is_int16,
+                                    const int32_t* n_samples, int B, long long Nmax, int n_win,
+                                    int n_step, int pad_to, int num_features, int Tpad,
+                                    uint16_t* out_bf16, float* out_f32, int32_t* out_len,
+                                    void* workspace, size_t workspace_bytes) {
+  OS2S_REQUIRE(num_features <= n_win / 2 + 1);   // the reference's assertion (speech_utils.py:501-502)
+  return psf_features(stream, kPsfSpectrogram, signal, sample_is_int16, n_samples, B, Nmax, n_win, n_step, pad_to,
+                      num_features, 0, 0, nullptr, nullptr, Tpad, out_bf16, out_f32, out_len, workspace,
+                      workspace_bytes);
+}
+
+// 'logfbank' of the psf backend (see psf_logfbank_kernel): fb = [nfilt][nfft/2 + 1] fp32 filter table on the
+// device (python_speech_features.get_filterbanks; the host layer builds it). nfft: a power of two >= n_win.
+// Workspace as os2s_psf_spectrogram_workspace_bytes(B, Tpad, nfilt).
+extern "C" int os2s_psf_logfbank(os2s_stream_t stream, const void* signal, int sample_is_int16,
+                                 const int32_t* n_samples, int B, long long Nmax, int n_win, int n_step,
+                                 int pad_to, int nfilt, int nfft, const float* fb, int Tpad,
+                                 uint16_t* out_bf16, float* out_f32, int32_t* out_len, void* workspace,
+                                 size_t workspace_bytes) {
+  return psf_features(stream, kPsfLogfbank, signal, sample_is_int16, n_samples, B, Nmax, n_win, n_step, pad_to, nfilt,
+                      nfilt, nfft, fb, nullptr, Tpad, out_bf16, out_f32, out_len, workspace, workspace_bytes);
 }
 
 // 'mfcc' of the psf backend (psf_logfbank_kernel<true>): fb = [nfilt][nfft/2 + 1] filter table as for
 // os2s_psf_logfbank, dctl = [numcep][nfilt] fp32 DCT-II x lifter table (device; the host layer builds both).
 // Workspace as os2s_psf_spectrogram_workspace_bytes(B, Tpad, numcep): only the cepstra reach memory.
-extern "C" int os2s_psf_mfcc(os2s_stream_t stream_, const void* signal, int sample_is_int16,
+extern "C" int os2s_psf_mfcc(os2s_stream_t stream, const void* signal, int sample_is_int16,
                              const int32_t* n_samples, int B, long long Nmax, int n_win, int n_step, int pad_to,
                              int numcep, int nfilt, int nfft, const float* fb, const float* dctl, int Tpad,
                              uint16_t* out_bf16, float* out_f32, int32_t* out_len, void* workspace,
                              size_t workspace_bytes) {
-  OS2S_REQUIRE(signal && n_samples && fb && dctl && out_bf16 && out_len && workspace);
-  OS2S_REQUIRE(B >= 1 && n_win >= 16 && n_step >= 1 && Tpad >= 1 && nfilt >= 1 && nfilt <= 4096);
-  OS2S_REQUIRE(numcep >= 1 && numcep <= nfilt);
-  OS2S_REQUIRE(nfft >= n_win && (nfft & (nfft - 1)) == 0);
-  if (workspace_bytes < os2s_psf_spectrogram_workspace_bytes(B, Tpad, numcep)) return OS2S_ERR_WORKSPACE;
-  const size_t lds = ((size_t)n_win + 2 * (size_t)nfft + nfft / 2 + 1 + nfilt) * sizeof(float);
-  if (lds > 48 * 1024) return OS2S_ERR_UNSUPPORTED;
-  hipStream_t stream = (hipStream_t)stream_;
-  char* ws = reinterpret_cast<char*>(workspace);
-  float* denom = reinterpret_cast<float*>(ws);
-  size_t off = ((size_t)B * 4 + 63) / 64 * 64;
-  double* partial = reinterpret_cast<double*>(ws + off);
-  off += (size_t)B * Tpad * 2 * 8;
-  float* plane = reinterpret_cast<float*>(ws + off);
-  OS2S_LAUNCH(psf_absmax_kernel, dim3(B), dim3(256), 0, stream, signal, sample_is_int16, Nmax, n_samples, denom);
-  OS2S_LAUNCH(psf_logfbank_kernel<true>, dim3(Tpad, B), dim3(256), lds, stream, signal, sample_is_int16, Nmax,
-              n_samples, denom, n_win, n_step, pad_to, nfilt, nfft, fb, dctl, numcep, Tpad, plane, partial, out_len);
-  OS2S_LAUNCH(psf_normalize_kernel, dim3(64, B), dim3(256), 0, stream, plane, partial, out_len, numcep, Tpad,
-              out_bf16, out_f32);
-  return OS2S_OK;
-}
-
-extern "C" size_t os2s_psf_spectrogram_workspace_bytes(int B, int T, int F) {
-  return (size_t)B * 4 + (size_t)B * T * F * 4 + (size_t)B * T * 2 * 8 + 64;
-}
-
-extern "C" int os2s_psf_spectrogram(os2s_stream_t stream_, const void* signal, int sample_is_int16,
-                                    const int32_t* n_samples, int B, long long Nmax, int n_win,
-                                    int n_step, int pad_to, int num_features, int Tpad,
-                                    uint16_t* out_bf16, float* out_f32, int32_t* out_len,
-                                    void* workspace, size_t workspace_bytes) {
-  OS2S_REQUIRE(signal && n_samples && out_bf16 && out_len && workspace);
-  OS2S_REQUIRE(B >= 1 && n_win >= 16 && n_step >= 1 && Tpad >= 1 && num_features >= 1);
-  OS2S_REQUIRE(num_features <= n_win / 2 + 1);   // the reference's assertion (speech_utils.py:501-502)
-  if (workspace_bytes < os2s_psf_spectrogram_workspace_bytes(B, Tpad, num_features)) return OS2S_ERR_WORKSPACE;
-  if ((size_t)3 * n_win * sizeof(float) > 48 * 1024) return OS2S_ERR_UNSUPPORTED;
-  hipStream_t stream = (hipStream_t)stream_;
-  char* ws = reinterpret_cast<char*>(workspace);
-  float* denom = reinterpret_cast<float*>(ws);
-  size_t off = ((size_t)B * 4 + 63) / 64 * 64;
-  double* partial = reinterpret_cast<double*>(ws + off);
-  off += (size_t)B * Tpad * 2 * 8;
-  float* plane = reinterpret_cast<float*>(ws + off);
-  OS2S_LAUNCH(psf_absmax_kernel, dim3(B), dim3(256), 0, stream, signal, sample_is_int16, Nmax, n_samples, denom);
-  OS2S_LAUNCH(psf_logpowspec_kernel, dim3(Tpad, B), dim3(256), (size_t)3 * n_win * sizeof(float), stream, signal,
-              sample_is_int16, Nmax, n_samples, denom, n_win, n_step, pad_to, num_features, Tpad, plane, partial,
-              out_len);
-  OS2S_LAUNCH(psf_normalize_kernel, dim3(64, B), dim3(256), 0, stream, plane, partial, out_len, num_features,
-              Tpad, out_bf16, out_f32);
-  return OS2S_OK;
+  OS2S_REQUIRE(dctl && numcep <= nfilt);
+  return psf_features(stream, kPsfMfcc, signal, sample_is_int16, n_samples, B, Nmax, n_win, n_step, pad_to, numcep,
+                      nfilt, nfft, fb, dctl, Tpad, out_bf16, out_f32, out_len, workspace, workspace_bytes);
 }

@@ -8,7 +8,7 @@
 // windowed frame and an n_fft-entry twiddle table in LDS, one thread per frequency bin with
 // an incremental (k*n mod N) phase index. It is a data-layer op (once per batch,
 // ~0.5 M complex MACs per frame), bound by VALU, not by HBM: 2 B read + ~2 KB written/frame.
-#include "os2s_common.hpp"
+#include "speech_frontend.hpp"
 
 namespace os2s {
 
@@ -37,26 +37,19 @@ __global__ __launch_bounds__(256) void tts_spectrogram_kernel(
   const float* sig = signal + (long long)b * sig_stride;
   const int start = t * hop - n_fft / 2;
   for (int i = tid; i < n_fft; i += 256) {
+    // Not reflect_index: a clip shorter than n_fft / 2 is reflected a SECOND time here (-j >= n goes on to
+    // 2 (n - 1) + j), where reflect_index stops after one reflection and clamps.
     int j = start + i;          // np.pad(mode='reflect'): ... 2 1 | 0 1 2 ... n-1 | n-2 n-3 ...
     if (j < 0) j = -j;
     if (j >= n) j = 2 * (n - 1) - j;
     j = min(max(j, 0), n - 1);
     x[i] = sig[j] * window[i];
-    float s, c;
-    sincospif(2.0f * (float)i / (float)n_fft, &s, &c);
-    cs[i] = c;
-    sn[i] = s;
   }
+  fill_twiddles(cs, sn, n_fft);
   __syncthreads();
   for (int k = tid; k < nbins; k += 256) {
-    float re = 0.f, im = 0.f;
-    int idx = 0;
-    for (int i = 0; i < n_fft; ++i) {
-      re += x[i] * cs[idx];
-      im -= x[i] * sn[idx];
-      idx += k;
-      if (idx >= n_fft) idx -= n_fft;
-    }
+    float re, im;
+    dft_bin(x, cs, sn, 0, n_fft, k, n_fft, re, im);
     const float p2 = re * re + im * im;
     mag[k] = mag_power == 2 ? p2 : sqrtf(p2);
   }

@@ -2,7 +2,7 @@
 open_seq2seq/data/speech2text/speech_utils.py (get_speech_features :275-319,
 get_speech_features_librosa :322-441, get_speech_features_psf :444-535): one launcher class per
 (backend, input_type), see FRONT_ENDS. The per-sample arithmetic runs on the GPU
-(csrc/logmel.hip, csrc/psf_features.hip); the host only prepares constant tables once:
+(csrc/logmel.hip, csrc/librosa_features.hip, csrc/psf_features.hip); the host only prepares constant tables once:
 the analysis window, the mel filterbank (what the reference precomputes with
 librosa.filters.mel in speech2text.py:167-183) and the DCT matrices of the 'mfcc' paths.
 
@@ -53,99 +53,90 @@ def mel_basis_slaney(sample_freq, n_fft, n_mels, fmin=0.0, fmax=None):
   return w.astype(np.float32)
 
 
-class LogMelFrontEnd(object):
-  """Constant tables + launcher for the 'logfbank' features of a Speech2TextDataLayer
-  configuration (params as in speech_utils.get_speech_features :275-306)."""
+def compact_mel_tables(basis):
+  """A [n_mels, n_bins] mel basis as the kernels read it: per filter the first non-zero bin and the length of its
+  support (int32 [n_mels] each), and the weights of that support, [max length, n_mels] float32, zero padded."""
+  n_mels = basis.shape[0]
+  starts, lens = np.zeros(n_mels, np.int32), np.zeros(n_mels, np.int32)
+  for m in range(n_mels):
+    nz = np.nonzero(basis[m])[0]
+    if len(nz):
+      starts[m], lens[m] = nz[0], nz[-1] - nz[0] + 1
+  wt = np.zeros((max(int(lens.max()), 1), n_mels), np.float32)
+  for m in range(n_mels):
+    wt[:lens[m], m] = basis[m, starts[m]:starts[m] + lens[m]]
+  return starts, lens, wt
+
+
+def psf_frame_count(n, n_win, n_step, pad_to):
+  """Frames of an n-sample utterance on the psf paths, as psf_frame_count of csrc/speech_frontend.hpp:
+  (1 + ceil((n - n_win) / n_step), at least one; that count rounded up to a multiple of pad_to)."""
+  live = 1 if n <= n_win else 1 + -(-(n - n_win) // n_step)
+  rem = live % pad_to if pad_to > 0 else 0
+  return live, (live + pad_to - rem if rem else live)
+
+
+class _FrontEnd(object):
+  """What every launcher shares: the parameters of get_speech_features (speech_utils.py:289-311) that all paths
+  read, the (backend, input_type) check, and the frame counts of a batch. A front end is called as
+  fe(signal [B,Nmax] float32|int16 (device), n_samples int32 [B] (device), max_samples = host max(n_samples), which
+  avoids a device sync and defaults to Nmax) -> (features bf16 [B,Tpad,F], frames int32 [B], fp32 copy or None)."""
+  backend = input_type = None
 
   def __init__(self, params, device):
     self.device = device
-    sr = params.get('sample_freq', 16000)
-    self.sample_freq = sr
-    if params.get('backend', 'psf') != 'librosa' or params.get('input_type') != 'logfbank':
-      raise NotImplementedError("GPU front ends: backend='librosa' + input_type='logfbank' (the Jasper "
-                                "configs), backend='psf' + input_type='spectrogram' (DeepSpeech2) or 'logfbank'")
-    self.n_mels = params['num_audio_features']
-    window_size = params.get('window_size', 20e-3)
-    window_stride = params.get('window_stride', 10e-3)
-    self.win_length = int(sr * window_size)
-    self.hop = int(sr * window_stride)
-    self.n_fft = params.get('num_fft', None) or 2 ** math.ceil(math.log2(window_size * sr))
-    self.dither = params.get('dither', 0.0)
-    self.norm_per_feature = params.get('norm_per_feature', False)
-    self.gain = params.get('gain', None)
-    self.pad_to = params.get('pad_to', 8)
-    wfn = WINDOWS_FNS[params.get('window', 'hanning')]
-    win = wfn(self.win_length) if wfn is not None else np.ones(self.win_length)
-    full = np.zeros(self.n_fft, np.float32)
-    lp = (self.n_fft - self.win_length) // 2
-    full[lp:lp + self.win_length] = win
-    basis = params.get('mel_basis', None)
-    if basis is None:
-      basis = mel_basis_slaney(sr, self.n_fft, self.n_mels, 0, int(sr / 2))
-    self.mel_basis = np.asarray(basis, np.float32)
-    starts, lens = [], []
-    for m in range(self.n_mels):
-      nz = np.nonzero(self.mel_basis[m])[0]
-      starts.append(int(nz[0]) if len(nz) else 0)
-      lens.append(int(nz[-1] - nz[0] + 1) if len(nz) else 0)
-    maxlen = max(max(lens), 1)
-    wt = np.zeros((maxlen, self.n_mels), np.float32)
-    for m in range(self.n_mels):
-      wt[:lens[m], m] = self.mel_basis[m, starts[m]:starts[m] + lens[m]]
-    self.window = torch.from_numpy(full).to(device)
-    self.mel_start = torch.tensor(starts, dtype=torch.int32, device=device)
-    self.mel_len = torch.tensor(lens, dtype=torch.int32, device=device)
-    self.mel_wt = torch.from_numpy(wt).to(device)
-
-  def frames(self, n_samples):
-    return 1 + int(n_samples) // self.hop
-
-  def __call__(self, signal, n_samples, max_samples=None, seed=0, want_f32=False):
-    """signal [B,Nmax] (float32 or int16, device), n_samples int32 [B] (device).
-    max_samples: host int = max(n_samples) (avoids a device sync); defaults to Nmax.
-    Returns (features bf16 [B,Tpad,F], frames int32 [B], fp32 copy or None)."""
-    nmax = int(max_samples) if max_samples is not None else signal.shape[1]
-    tmax = self.frames(nmax)
-    tpad = -(-tmax // self.pad_to) * self.pad_to if self.pad_to > 0 else tmax
-    return capi.logmel(signal, n_samples, self.window, self.mel_start, self.mel_len,
-                       self.mel_wt, hop=self.hop, n_mels=self.n_mels, tmax=tmax, tpad=tpad,
-                       dither=self.dither, seed=seed,
-                       fixed_gain=self.gain if self.gain is not None else -1.0,
-                       norm_per_feature=self.norm_per_feature, want_f32=want_f32,
-                       n_fft=self.n_fft)
-
-
-class PsfSpectrogramFrontEnd(object):
-  """Launcher for the 'spectrogram' features of the python_speech_features backend
-  (get_speech_features_psf, speech_utils.py:444-535; the DeepSpeech2 configs). Same call
-  signature as LogMelFrontEnd; dither / gain / norm_per_feature do not exist on this path."""
-
-  def __init__(self, params, device):
-    self.device = device
-    sr = params.get('sample_freq', 16000)
-    self.sample_freq = sr
-    if params.get('backend', 'psf') != 'psf' or params.get('input_type') != 'spectrogram':
-      raise NotImplementedError("PsfSpectrogramFrontEnd implements backend='psf', input_type='spectrogram'")
+    self.sample_freq = sr = params.get('sample_freq', 16000)
+    if (params.get('backend', 'psf'), params.get('input_type')) != (self.backend, self.input_type):
+      raise NotImplementedError("%s implements backend='%s', input_type='%s'"
+                                % (type(self).__name__, self.backend, self.input_type))
     self.num_features = params['num_audio_features']
     self.win_length = int(sr * params.get('window_size', 20e-3))
     self.hop = int(sr * params.get('window_stride', 10e-3))
     self.pad_to = params.get('pad_to', 8)
+
+  def _shape(self, signal, max_samples):
+    """(tmax, tpad): the frames of the longest utterance, and that count rounded up to pad_to."""
+    tmax = self.frames(int(max_samples) if max_samples is not None else signal.shape[1])
+    return tmax, (-(-tmax // self.pad_to) * self.pad_to if self.pad_to > 0 else tmax)
+
+
+class _PsfFrontEnd(_FrontEnd):
+  """The python_speech_features backend (get_speech_features_psf, speech_utils.py:444-535): frames() includes the
+  pad_to rounding; dither / gain / norm_per_feature do not exist on these paths."""
+  backend = 'psf'
+  nfft = 512          # psf.logfbank / psf.mfcc are called with nfft = 512
+
+  def __init__(self, params, device):
+    super(_PsfFrontEnd, self).__init__(params, device)
     self.gain = None
+    self._tables(device)
+
+  def _filterbank(self, nfilt, device):
+    if self.win_length > self.nfft:
+      raise NotImplementedError("psf.%s truncates frames longer than nfft = 512 (window_size > 32 ms)"
+                                % self.input_type)
+    fb = psf_filterbanks(nfilt, self.nfft, self.sample_freq, 0.0, self.sample_freq / 2.0)
+    self.fb = torch.from_numpy(np.ascontiguousarray(fb, np.float32)).to(device)
+
+  def frames(self, n_samples):
+    return psf_frame_count(int(n_samples), self.win_length, self.hop, self.pad_to)[1]
+
+  def _psf_args(self, signal, max_samples, want_f32):
+    return dict(n_win=self.win_length, n_step=self.hop, pad_to=self.pad_to, tpad=self._shape(signal, max_samples)[1],
+                want_f32=want_f32)
+
+
+class PsfSpectrogramFrontEnd(_PsfFrontEnd):
+  """Launcher for the 'spectrogram' features of the python_speech_features backend (the DeepSpeech2 configs)."""
+  input_type = 'spectrogram'
+
+  def _tables(self, device):
     if self.num_features > self.win_length // 2 + 1:        # speech_utils.py:501-502
       raise AssertionError("num_features for spectrogram should be <= (sample_freq * window_size // 2 + 1)")
 
-  def frames(self, n_samples):
-    n = int(n_samples)
-    f = 1 if n <= self.win_length else 1 + -(-(n - self.win_length) // self.hop)
-    if self.pad_to > 0 and f % self.pad_to:
-      f += self.pad_to - f % self.pad_to
-    return f
-
   def __call__(self, signal, n_samples, max_samples=None, seed=0, want_f32=False):
-    nmax = int(max_samples) if max_samples is not None else signal.shape[1]
-    return capi.psf_spectrogram(signal, n_samples, n_win=self.win_length, n_step=self.hop,
-                                pad_to=self.pad_to, num_features=self.num_features,
-                                tpad=self.frames(nmax), want_f32=want_f32)
+    return capi.psf_spectrogram(signal, n_samples, num_features=self.num_features,
+                                **self._psf_args(signal, max_samples, want_f32))
 
 
 def psf_filterbanks(nfilt, nfft, samplerate, lowfreq=0.0, highfreq=None):
@@ -169,28 +160,14 @@ class PsfLogfbankFrontEnd(PsfSpectrogramFrontEnd):
   """Launcher for the 'logfbank' features of the python_speech_features backend (get_speech_features_psf,
   speech_utils.py:517-535: psf.logfbank with nfft = 512, preemph = 0.97; the toy Wave2Letter / TDNN test
   configurations). Framing and padding as the spectrogram path."""
+  input_type = 'logfbank'
 
-  def __init__(self, params, device):
-    self.device = device
-    sr = params.get('sample_freq', 16000)
-    self.sample_freq = sr
-    if params.get('backend', 'psf') != 'psf' or params.get('input_type') != 'logfbank':
-      raise NotImplementedError("PsfLogfbankFrontEnd implements backend='psf', input_type='logfbank'")
-    self.num_features = params['num_audio_features']
-    self.win_length = int(sr * params.get('window_size', 20e-3))
-    self.hop = int(sr * params.get('window_stride', 10e-3))
-    self.pad_to = params.get('pad_to', 8)
-    self.gain = None
-    self.nfft = 512
-    if self.win_length > self.nfft:
-      raise NotImplementedError("psf.logfbank truncates frames longer than nfft = 512 (window_size > 32 ms)")
-    fb = psf_filterbanks(self.num_features, self.nfft, sr, 0.0, sr / 2.0)
-    self.fb = torch.from_numpy(np.ascontiguousarray(fb, np.float32)).to(device)
+  def _tables(self, device):
+    self._filterbank(self.num_features, device)
 
   def __call__(self, signal, n_samples, max_samples=None, seed=0, want_f32=False):
-    nmax = int(max_samples) if max_samples is not None else signal.shape[1]
-    return capi.psf_logfbank(signal, n_samples, self.fb, n_win=self.win_length, n_step=self.hop,
-                             pad_to=self.pad_to, nfft=self.nfft, tpad=self.frames(nmax), want_f32=want_f32)
+    return capi.psf_logfbank(signal, n_samples, self.fb, nfft=self.nfft,
+                             **self._psf_args(signal, max_samples, want_f32))
 
 
 def dct_ortho_table(n_out, n_in):
@@ -217,62 +194,42 @@ class PsfMfccFrontEnd(PsfLogfbankFrontEnd):
   speech_utils.py:504-515: psf.mfcc with numcep = F, nfilt = 2F, nfft = 512, preemph = 0.97, ceplifter = 2F,
   appendEnergy = False, rectangular window; example_configs/speech2text/lstm_small_1gpu.py). Framing and padding
   as the other psf paths."""
+  input_type = 'mfcc'
 
-  def __init__(self, params, device):
-    self.device = device
-    sr = params.get('sample_freq', 16000)
-    self.sample_freq = sr
-    if params.get('backend', 'psf') != 'psf' or params.get('input_type') != 'mfcc':
-      raise NotImplementedError("PsfMfccFrontEnd implements backend='psf', input_type='mfcc'")
-    self.num_features = params['num_audio_features']
-    self.win_length = int(sr * params.get('window_size', 20e-3))
-    self.hop = int(sr * params.get('window_stride', 10e-3))
-    self.pad_to = params.get('pad_to', 8)
-    self.gain = None
-    self.nfft = 512
-    if self.win_length > self.nfft:
-      raise NotImplementedError("psf.mfcc truncates frames longer than nfft = 512 (window_size > 32 ms)")
+  def _tables(self, device):
     nfilt = 2 * self.num_features
-    fb = psf_filterbanks(nfilt, self.nfft, sr, 0.0, sr / 2.0)
-    self.fb = torch.from_numpy(np.ascontiguousarray(fb, np.float32)).to(device)
+    self._filterbank(nfilt, device)
     dctl = psf_mfcc_table(self.num_features, nfilt, nfilt)
     self.dctl = torch.from_numpy(np.ascontiguousarray(dctl, np.float32)).to(device)
 
   def __call__(self, signal, n_samples, max_samples=None, seed=0, want_f32=False):
-    nmax = int(max_samples) if max_samples is not None else signal.shape[1]
-    return capi.psf_mfcc(signal, n_samples, self.fb, self.dctl, n_win=self.win_length, n_step=self.hop,
-                         pad_to=self.pad_to, nfft=self.nfft, tpad=self.frames(nmax), want_f32=want_f32)
+    return capi.psf_mfcc(signal, n_samples, self.fb, self.dctl, nfft=self.nfft,
+                         **self._psf_args(signal, max_samples, want_f32))
 
 
-class _LibrosaFrontEnd(object):
-  """What the 'mfcc' and 'spectrogram' launchers of the librosa backend share: the parameters of
-  get_speech_features (speech_utils.py:289-311), the frame count of a centred STFT and the padding to pad_to."""
-  input_type = None
+class _LibrosaFrontEnd(_FrontEnd):
+  """The librosa backend (get_speech_features_librosa, speech_utils.py:322-441): a centred STFT (frame count
+  1 + n // hop) with the window_fn(win_length) window zero-padded centred to n_fft, dither, gain, and the
+  normalisation options."""
+  backend = 'librosa'
+  window_dtype = np.float64
 
   def __init__(self, params, device):
-    self.device = device
-    sr = params.get('sample_freq', 16000)
-    self.sample_freq = sr
-    if params.get('backend', 'psf') != 'librosa' or params.get('input_type') != self.input_type:
-      raise NotImplementedError("%s implements backend='librosa', input_type='%s'"
-                                % (type(self).__name__, self.input_type))
-    self.num_features = params['num_audio_features']
-    window_size = params.get('window_size', 20e-3)
-    self.win_length = int(sr * window_size)
-    self.hop = int(sr * params.get('window_stride', 10e-3))
-    self.n_fft = self._transform_length(params, window_size * sr)
+    super(_LibrosaFrontEnd, self).__init__(params, device)
+    self.n_fft = self._transform_length(params, params.get('window_size', 20e-3) * self.sample_freq)
     self.dither = params.get('dither', 0.0)
     self.norm_per_feature = params.get('norm_per_feature', False)
     self.gain = params.get('gain', None)
-    self.pad_to = params.get('pad_to', 8)
     wfn = WINDOWS_FNS[params.get('window', 'hanning')]
-    win = wfn(self.win_length) if wfn is not None else np.ones(self.win_length)
-    full = np.zeros(self.n_fft, np.float64)
+    full = np.zeros(self.n_fft, self.window_dtype)
     lp = (self.n_fft - self.win_length) // 2
-    full[lp:lp + self.win_length] = win
+    full[lp:lp + self.win_length] = wfn(self.win_length) if wfn is not None else np.ones(self.win_length)
     self.window = torch.from_numpy(full).to(device)
     self.features_mean = self._given(params.get('features_mean'))
     self.features_std = self._given(params.get('features_std_dev'))
+
+  def _transform_length(self, params, win):
+    return params.get('num_fft', None) or 2 ** math.ceil(math.log2(win))
 
   def _given(self, value):
     if value is None:
@@ -283,15 +240,36 @@ class _LibrosaFrontEnd(object):
   def frames(self, n_samples):
     return 1 + int(n_samples) // self.hop
 
-  def _shape(self, signal, max_samples):
-    nmax = int(max_samples) if max_samples is not None else signal.shape[1]
-    tmax = self.frames(nmax)
-    return tmax, (-(-tmax // self.pad_to) * self.pad_to if self.pad_to > 0 else tmax)
-
-  def _common(self, seed, want_f32):
-    return dict(hop=self.hop, dither=self.dither, seed=seed,
+  def _common(self, signal, max_samples, seed, want_f32):
+    tmax, tpad = self._shape(signal, max_samples)
+    return dict(hop=self.hop, tmax=tmax, tpad=tpad, dither=self.dither, seed=seed,
                 fixed_gain=self.gain if self.gain is not None else -1.0, norm_per_feature=self.norm_per_feature,
-                features_mean=self.features_mean, features_std=self.features_std, want_f32=want_f32)
+                want_f32=want_f32)
+
+  def _stats(self):
+    return dict(features_mean=self.features_mean, features_std=self.features_std)
+
+
+class LogMelFrontEnd(_LibrosaFrontEnd):
+  """Constant tables + launcher for the 'logfbank' features of the librosa backend (the Jasper configs; params as
+  in speech_utils.get_speech_features :275-306): the FFT path of csrc/logmel.hip, which reads a float32 window and
+  the compact tables of the mel basis (params['mel_basis'], or librosa.filters.mel's)."""
+  input_type = 'logfbank'
+  window_dtype = np.float32
+
+  def __init__(self, params, device):
+    super(LogMelFrontEnd, self).__init__(params, device)
+    self.n_mels = self.num_features
+    basis = params.get('mel_basis', None)
+    if basis is None:
+      basis = mel_basis_slaney(self.sample_freq, self.n_fft, self.n_mels, 0, int(self.sample_freq / 2))
+    self.mel_basis = np.asarray(basis, np.float32)
+    self.mel_start, self.mel_len, self.mel_wt = (torch.from_numpy(t).to(device)
+                                                 for t in compact_mel_tables(self.mel_basis))
+
+  def __call__(self, signal, n_samples, max_samples=None, seed=0, want_f32=False):
+    return capi.logmel(signal, n_samples, self.window, self.mel_start, self.mel_len, self.mel_wt,
+                       n_mels=self.n_mels, n_fft=self.n_fft, **self._common(signal, max_samples, seed, want_f32))
 
 
 class LibrosaMfccFrontEnd(_LibrosaFrontEnd):
@@ -302,17 +280,13 @@ class LibrosaMfccFrontEnd(_LibrosaFrontEnd):
   spectrum, with no mel scale and no logarithm. This class reproduces that."""
   input_type = 'mfcc'
 
-  def _transform_length(self, params, win):
-    return params.get('num_fft', None) or 2 ** math.ceil(math.log2(win))
-
   def __init__(self, params, device):
     super(LibrosaMfccFrontEnd, self).__init__(params, device)
     self.dct = torch.from_numpy(dct_ortho_table(self.num_features, self.n_fft // 2 + 1)).to(device)
 
   def __call__(self, signal, n_samples, max_samples=None, seed=0, want_f32=False):
-    tmax, tpad = self._shape(signal, max_samples)
-    return capi.librosa_mfcc(signal, n_samples, self.window, self.dct, win_length=self.win_length, tmax=tmax,
-                             tpad=tpad, **self._common(seed, want_f32))
+    return capi.librosa_mfcc(signal, n_samples, self.window, self.dct, win_length=self.win_length,
+                             **self._common(signal, max_samples, seed, want_f32), **self._stats())
 
 
 class LibrosaSpectrogramFrontEnd(_LibrosaFrontEnd):
@@ -329,9 +303,8 @@ class LibrosaSpectrogramFrontEnd(_LibrosaFrontEnd):
       raise AssertionError("num_features for spectrogram should be <= (sample_freq * window_size // 2 + 1)")
 
   def __call__(self, signal, n_samples, max_samples=None, seed=0, want_f32=False):
-    tmax, tpad = self._shape(signal, max_samples)
-    return capi.librosa_spectrogram(signal, n_samples, self.window, num_features=self.num_features, tmax=tmax,
-                                    tpad=tpad, **self._common(seed, want_f32))
+    return capi.librosa_spectrogram(signal, n_samples, self.window, num_features=self.num_features,
+                                    **self._common(signal, max_samples, seed, want_f32), **self._stats())
 
 
 FRONT_ENDS = {

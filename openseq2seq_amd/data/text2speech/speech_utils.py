@@ -15,7 +15,7 @@ import numpy as np
 import torch
 
 from ... import capi
-from ..speech2text.speech_utils import mel_basis_slaney
+from ..speech2text.speech_utils import compact_mel_tables, mel_basis_slaney
 
 
 def mel_basis_htk(sample_freq, n_fft, n_mels, fmin=0.0, fmax=None):
@@ -80,17 +80,8 @@ class TTSFeatureFrontEnd(object):
       if mel_basis is None:
         mel_basis = (mel_basis_htk if mel_type == "htk" else mel_basis_slaney)(sample_freq, n_fft, self.n_mels)
       self.mel_basis = np.asarray(mel_basis, np.float32)
-      starts, lens = [], []
-      for m in range(self.n_mels):
-        nz = np.nonzero(self.mel_basis[m])[0]
-        starts.append(int(nz[0]) if len(nz) else 0)
-        lens.append(int(nz[-1] - nz[0] + 1) if len(nz) else 0)
-      wt = np.zeros((max(max(lens), 1), self.n_mels), np.float32)
-      for m in range(self.n_mels):
-        wt[:lens[m], m] = self.mel_basis[m, starts[m]:starts[m] + lens[m]]
-      self.mel_start = torch.tensor(starts, dtype=torch.int32, device=device)
-      self.mel_len = torch.tensor(lens, dtype=torch.int32, device=device)
-      self.mel_wt = torch.from_numpy(wt).to(device)
+      self.mel_start, self.mel_len, self.mel_wt = (torch.from_numpy(t).to(device)
+                                                   for t in compact_mel_tables(self.mel_basis))
 
   def frames(self, n_samples):
     return 1 + int(n_samples) // self.hop
