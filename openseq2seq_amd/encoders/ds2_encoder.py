@@ -53,6 +53,13 @@ class Conv2dBN(object):
     self.cin_f, self.cout_f = f_in * c_in, self.Fo * c_out
     if self.cin_f % 8 or self.cout_f % 8:
       raise NotImplementedError("F*C must be a multiple of 8")
+    # The BatchNorm kernels take channel counts that are multiples of 8. A narrower layer runs them on the
+    # [rows / m, m * Cout] view (m neighbouring frequency bins side by side, m * Cout % 8 == 0; Fo % m == 0
+    # follows from Fo * Cout % 8 == 0) and folds the m copies of every channel in the [parts, 2, C] partials
+    # (a sum over a few hundred floats; every pass over the rows stays on the BatchNorm kernels). m == 1 for
+    # Cout % 8 == 0: those layers launch exactly what they did without the fold.
+    self._bn_fold = 8 // math.gcd(c_out, 8)
+    assert self.Fo % self._bn_fold == 0
     self._wexp = self._wexpT = None
     self._desc = torch.frombuffer(bytearray(struct.pack(
         "<qqiiii", 0, 0, KT, self.cout_f, self.cin_f, 0)), dtype=torch.uint8).to(dev).view(1, 32)
@@ -79,19 +86,26 @@ class Conv2dBN(object):
     else:
       tout, pl = capi.valid_padding(Tin, self.KT, self.sT, 1)
     y = capi.conv1d_fwd(x.data, self._wexp, stride=self.sT, pad_left=pl, tout=tout)
-    C = self.Cout
-    rows = B * tout * self.Fo
+    m, Co = self._bn_fold, self.Cout
+    C = Co * m                          # the BatchNorm kernels' view: [rows, C]
+    count = B * tout * self.Fo          # positions per channel
+    rows = count // m
+    if m == 1:
+      rep = fold = lambda t: t
+    else:
+      rep = lambda t: t.repeat(m)                                        # [Co] -> [C]
+      fold = lambda p: p.view(p.shape[0], 2, m, Co).sum(2)               # [parts, 2, C] -> [parts, 2, Co]
     dev = y.device
-    sc, sh = torch.empty(C, device=dev), torch.empty(C, device=dev)
+    sc, sh = torch.empty(Co, device=dev), torch.empty(Co, device=dev)
     mean = rstd = part = None
     if training:
-      part = capi.bn_stats(y.view(rows, C))
-      mean, rstd = torch.empty(C, device=dev), torch.empty(C, device=dev)
-    capi.bn_finalize(part, rows, self.gamma.master, self.beta.master, self.eps, self.momentum,
+      part = fold(capi.bn_stats(y.view(rows, C)))
+      mean, rstd = torch.empty(Co, device=dev), torch.empty(Co, device=dev)
+    capi.bn_finalize(part, count, self.gamma.master, self.beta.master, self.eps, self.momentum,
                      training, self.moving_mean, self.moving_var, mean, rstd, sc, sh)
     out = torch.empty_like(y)
     act = act_id(activation_fn)
-    capi.bn_act_fwd([y.view(1, rows, C)], [sc], [sh], out.view(1, rows, C), None, act, 1.0, 0)
+    capi.bn_act_fwd([y.view(1, rows, C)], [rep(sc)], [rep(sh)], out.view(1, rows, C), None, act, 1.0, 0)
     res = Act(out, None)
     if not (training and tape is not None):
       return res
@@ -102,12 +116,13 @@ class Conv2dBN(object):
       assert dout is not None
       dz = torch.empty_like(out)
       partial = torch.empty((capi.bn_act_bwd_num_parts(rows), 2, C), dtype=torch.float32, device=dev)
+      mean_v, rstd_v = rep(mean), rep(rstd)
       capi.bn_act_bwd_reduce(dout.view(1, rows, C), out.view(1, rows, C), [y.view(1, rows, C)],
-                             [mean], [rstd], dz.view(1, rows, C), partial, None, act, 1.0, 0)
-      c1, c2 = torch.empty(C, device=dev), torch.empty(C, device=dev)
-      capi.bn_bwd_finalize(partial, 1, rows, L.gamma.grad, L.beta.grad, True, c1, c2)
+                             [mean_v], [rstd_v], dz.view(1, rows, C), partial, None, act, 1.0, 0)
+      c1, c2 = torch.empty(Co, device=dev), torch.empty(Co, device=dev)
+      capi.bn_bwd_finalize(fold(partial), 1, count, L.gamma.grad, L.beta.grad, True, c1, c2)
       dy = torch.empty_like(y)
-      capi.bn_bwd_apply(dz.view(rows, C), y.view(rows, C), L.gamma.master, mean, rstd, c1, c2,
+      capi.bn_bwd_apply(dz.view(rows, C), y.view(rows, C), rep(L.gamma.master), mean_v, rstd_v, rep(c1), rep(c2),
                         dy.view(rows, C))
       dwexp = capi.conv1d_wgrad(x.data, dy, L.KT, stride=L.sT, pad_left=pl)
       capi.conv2d_toeplitz_reduce(dwexp, L.Fi, L.Fo, L.sF, L.padF, L.kernel.grad)

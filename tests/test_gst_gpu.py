@@ -2,7 +2,8 @@
 fp32 oracle: conv2d stack (stride 2 in time AND frequency, incl. the transposed-convolution
 data gradient), TF GRUCell summary with ragged lengths, Dense+tanh, token attention; output
 and all parameter gradients. bf16 activations: output rel-L2 <= 4e-2, gradients cosine >=
-0.98 and rel-L2 <= 0.2."""
+0.98 and rel-L2 <= 0.2.
+Per-kernel accuracy is pinned in tests/test_gst_kernels_gpu.py and tests/test_conv2d_toeplitz_gpu.py."""
 import pytest
 import torch
 
