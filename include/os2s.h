@@ -933,11 +933,13 @@ int os2s_rnn_layer_bwd_multi(os2s_stream_t stream, int cell, int ndir,
  *   ctx:   raw contexts, row (b,t) at ctx + b*ctx_bs + t*ctx_ts (bf16)
  * so os2s_attn_decoder_fwd may be called for any step range [t_begin, t_end): the whole
  * teacher-forced sequence at once, or one step at a time for greedy / free-running decoding.
- * tgt_len (or NULL): steps t >= tgt_len[b] leave sample b untouched (impute_finished).
+ * tgt_len (or NULL): steps t >= tgt_len[b] leave sample b untouched (impute_finished), but for
+ * cum_seq, whose row t+1 then repeats row t.
  * Dropout masks come from the library's counter hash: attention-input dropout indexes the
  * logical [B, T+1, M] tensor (row t+1 = attention_t), output dropout [B, T, H] per layer.
  * Limits: H % 8 == 0, M % 8 == 0, U % 128 == 0 and <= 512; location-sensitive mode:
- * U == 128, loc_k <= 32.
+ * U == 128, loc_k <= 32. Luong with U != H has no query layer to bridge the two widths:
+ * OS2S_ERR_UNSUPPORTED.
  * ---------------------------------------------------------------------- */
 typedef struct os2s_attn_decoder {
   int B, T, S, L, H, M, U;

@@ -208,11 +208,19 @@ __device__ __forceinline__ void attn_pre2(const AdAttn& p, const AttnLds& l, int
   x1 = bfhi(kv) + l.q[u + 1] + l.bs[u + 1];
 }
 
+// finished sample (t >= tgt_len[b]) in location mode: the cumulative alignments carry over, row t + 1 =
+// row t (the state of impute_finished); every other buffer of the step stays as the caller zeroed it
+__device__ __forceinline__ void attn_carry_cum(const AdAttn& p, int b) {
+  if (p.mode != 2) return;
+  float* cum = p.cum_seq + ((long long)b * (p.T + 1) + p.t) * p.S;
+  for (int sp = threadIdx.x; sp < p.S; sp += blockDim.x) cum[p.S + sp] = cum[sp];
+}
+
 // ------------------------------------------------------------------ attention forward
 __global__ __launch_bounds__(kAttnThreads) void ad_attn_fwd_kernel(AdAttn p) {
   extern __shared__ float lds_raw[];
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  if (p.tgt_len && p.t >= p.tgt_len[b]) return;
+  if (p.tgt_len && p.t >= p.tgt_len[b]) { attn_carry_cum(p, b); return; }
   const int H = p.H, M = p.M, U = p.U, S = p.S, K = p.loc_k;
   const AttnLds l = attn_lds_carve(lds_raw, H, U, S, p.mode, K);
   const int slen = min(max(p.src_len[b], 0), S);
@@ -940,7 +948,10 @@ __global__ __launch_bounds__(kAttnThreads) void ad_loc_scores_kernel(AdAttn p, A
 __global__ __launch_bounds__(256) void ad_loc_context_kernel(AdAttn p, AdLoc x, int ncg, int nsp) {
   extern __shared__ float lds_raw[];
   const int cpart = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
-  if (p.tgt_len && p.t >= p.tgt_len[b]) return;
+  if (p.tgt_len && p.t >= p.tgt_len[b]) {
+    if (cpart == 0) attn_carry_cum(p, b);
+    return;
+  }
   const int M = p.M, S = p.S;
   float* e = lds_raw;                  // [S]
   float* red = e + S;                  // [8]
@@ -1928,16 +1939,6 @@ __global__ __launch_bounds__(256) void ad_dkeys_kernel(const bf16_t* __restrict_
   *reinterpret_cast<f32x4*>(o + 4) = f32x4{a[4], a[5], a[6], a[7]};
 }
 
-// out[n] += sum_b acc[b, n]
-__global__ void ad_reduce_rows_kernel(const float* __restrict__ acc, int B, long long N,
-                                      float* __restrict__ out) {
-  const long long n = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (n >= N) return;
-  float s = 0.f;
-  for (int b = 0; b < B; ++b) s += acc[(long long)b * N + n];
-  out[n] += s;
-}
-
 // gradient of the score vector parameters from d(normalised v) partials [B,U]
 __global__ __launch_bounds__(256) void ad_score_vec_grads_kernel(const float* __restrict__ dnv_acc,
                                                                  int B, int U, int mode,
@@ -2003,7 +2004,7 @@ int os2s::ad_check(const os2s_attn_decoder_t* d) {
   OS2S_REQUIRE(d && d->B >= 1 && d->T >= 1 && d->S >= 1 && (d->L == 1 || d->L == 2));
   OS2S_REQUIRE(d->H % 8 == 0 && d->M % 8 == 0 && d->U % 128 == 0 && d->U <= 512);
   OS2S_REQUIRE(d->score_mode >= 0 && d->score_mode <= 3);
-  if (d->score_mode == 3) OS2S_REQUIRE(d->U == d->H);     // Luong: the query IS the cell output
+  if (d->score_mode == 3 && d->U != d->H) return OS2S_ERR_UNSUPPORTED;     // Luong: the query IS the cell output
   OS2S_REQUIRE(d->t_begin >= 0 && d->t_begin <= d->t_end && d->t_end <= d->T);
   OS2S_REQUIRE(d->wcat[0] && d->wq && d->v && d->keys && d->values && d->src_len && d->gx0);
   OS2S_REQUIRE(d->cat[0] && d->c_seq[0] && d->align_seq && d->q_seq && d->y_top && d->ctx);

@@ -73,7 +73,7 @@ def masked_softmax(score, mask):
 
 def attention_decoder(p, gx0, memory, src_len, tgt_len=None, attn_in_mask=None, out_masks=None,
                       forget_bias=1.0, mode="bahdanau_norm", keys_override=None,
-                      values_override=None):
+                      values_override=None, store=None):
   """Runs T steps. p: dict of parameters
       wcat: list of L tensors, wcat[0] [4H, M+H] (columns: attention, h), wcat[l>0] [4H, 2H]
       bias: list of L tensors [4H] or None (layer 0's bias is part of gx0)
@@ -85,7 +85,12 @@ def attention_decoder(p, gx0, memory, src_len, tgt_len=None, attn_in_mask=None, 
     out_masks: list of L [B,T,H] masks on each cell's OUTPUT (state h stays undropped).
     tgt_len: steps >= tgt_len[b] leave the state untouched and output zeros
       (TrainingHelper + impute_finished=True); None: every sample runs all T steps.
+    store: optional callable applied where the device loop stores bf16 in the forward pass (each
+      layer's new h before it becomes the next step's recurrent input, each layer's output after
+      output dropout, the context); None: identity.
     Returns dict(y [B,T,H] top cell outputs, ctx [B,T,M], align [B,T,S])."""
+  if store is None:
+    store = lambda t: t
   B, T, _ = gx0.shape
   L = len(p["wcat"])
   H = p["wq"].shape[1]
@@ -114,9 +119,9 @@ def attention_decoder(p, gx0, memory, src_len, tgt_len=None, attn_in_mask=None, 
         hn, cn = lstm_cell(torch.cat([a_in, h[0]], -1), c[0], p["wcat"][0], gx0[:, t], forget_bias)
       else:
         hn, cn = lstm_cell(torch.cat([x, h[l]], -1), c[l], p["wcat"][l], p["bias"][l], forget_bias)
-      nh.append(hn)
+      nh.append(store(hn))
       nc.append(cn)
-      x = hn if out_masks is None else hn * out_masks[l][:, t]
+      x = store(hn if out_masks is None else hn * out_masks[l][:, t])
     q = x @ p["wq"].t()
     if mode == "location":
       loc = location_features(cum, p["conv_w"], p["conv_b"], p["dense_w"])
@@ -133,7 +138,7 @@ def attention_decoder(p, gx0, memory, src_len, tgt_len=None, attn_in_mask=None, 
     else:
       score = bahdanau_score(q, keys, p["v"])
     al = masked_softmax(score, mask)
-    ctx = (al[:, :, None] * values).sum(1)
+    ctx = store((al[:, :, None] * values).sum(1))
     if live is not None:
       for l in range(L):
         h[l] = live * nh[l] + (1 - live) * h[l]
