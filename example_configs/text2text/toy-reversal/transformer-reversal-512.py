@@ -1,8 +1,8 @@
 # pylint: skip-file
 """The reference's tiny Transformer on the toy reversal task
-(example_configs/text2text/toy-reversal/nmt-reversal-TT.py) with d_model raised from 128 to 512
-(8 heads x 64): the HIP LayerNorm / attention kernels are built for the Transformer-base / -big
-widths (hidden 512 / 1024, head dim 64). Everything else — 2+2 layers, LazyAdam +
+(example_configs/text2text/toy-reversal/nmt-reversal-TT.py, in this directory with its own values)
+with d_model raised from 128 to 512 (8 heads x 64): the toy task on the tuned LayerNorm / attention
+kernels of the Transformer-base / -big widths (hidden 512 / 1024, head dim 64). Everything else — 2+2 layers, LazyAdam +
 transformer_policy with 200 warm-up steps, beam 5 / alpha 1.0 / extra_decode_length 2, label
 smoothing default — is the reference's TT config, except learning_rate 1.0 -> 0.3: the policy's
 peak rate scales as d_model^-0.5 only, and 1.0 (tuned for d_model 128) leaves the 4x wider

@@ -634,7 +634,8 @@ int os2s_embed_fwd(os2s_stream_t stream, const int32_t* ids, const int32_t* pos,
 int os2s_embed_bwd(os2s_stream_t stream, const int32_t* ids, const uint16_t* dout, int V,
                    int D, long long N, float emb_scale, float keep_prob,
                    unsigned long long seed, float* dtable, int plain_lookup);
-/* LayerNormalization "layernorm_L2" (parts/transformer/common.py:41-68), D in {512, 1024} */
+/* LayerNormalization "layernorm_L2" (parts/transformer/common.py:41-68): D % 8 == 0, 8 <= D <= 4096
+ * (512 and 1024 are the tuned instantiations, every other width a row kernel with a runtime column loop) */
 int os2s_layernorm_fwd(os2s_stream_t stream, const uint16_t* x, const float* gamma,
                        const float* beta, float eps, long long N, int D, uint16_t* y,
                        float* mean, float* rstd);
@@ -645,7 +646,7 @@ int os2s_layernorm_bwd(os2s_stream_t stream, const uint16_t* dy, const uint16_t*
                        const float* gamma, const float* mean, const float* rstd,
                        const uint16_t* dres, long long N, int D, uint16_t* dx,
                        float* partial);
-/* LayerNormalization "layernorm_L1" (parts/transformer/common.py:69-80), D in {512, 1024}:
+/* LayerNormalization "layernorm_L1" (parts/transformer/common.py:69-80), D % 8 == 0, 8 <= D <= 4096 (as layernorm_L2):
  * y = c / (mean|c| + eps) * gamma + beta with c = x - mean(x); saves mean and rinv = 1 / (mean|c| + eps) per row */
 int os2s_layernorm_l1_fwd(os2s_stream_t stream, const uint16_t* x, const float* gamma,
                           const float* beta, float eps, long long N, int D, uint16_t* y,
@@ -694,7 +695,9 @@ int os2s_add_bf16(os2s_stream_t stream, const uint16_t* a, const uint16_t* b, lo
  * channels [h*dh, (h+1)*dh) of each row (split_heads/combine_heads are indexing only).
  * bias = padding mask (absent keys in the packed layout) and, if causal, the decoder's
  * lower-triangular band (utils.py:57-79). lse [Nq, H] is saved for the backward, which
- * recomputes the probabilities. dh == 64. Training (backward, attention dropout) is
+ * recomputes the probabilities. dh in {8, 16, 32, 64, 128} (64 is the tuned kernel family, the other four share
+ * one family templated on the head dim; anything else: OS2S_ERR_UNSUPPORTED). The dropout mask is element
+ * ((b*H + h)*64 + q)*64 + key whatever dh. Training (backward, attention dropout) is
  * implemented for max_len <= 64 (the length-filtered training sets of the configs); the
  * forward without dropout takes any max_len (eval / infer batches): one wave per 64-query
  * tile walks the key tiles with an online softmax. OS2S_ERR_UNSUPPORTED otherwise. */
@@ -824,7 +827,7 @@ int os2s_gemm_skinny(os2s_stream_t stream, const uint16_t* x, long long ldx, con
  * ancestry[n, step] = n, and attends over positions 0..step of beam n's history, position j
  * living in cache row ancestry[n, j] ([N, Tmax] int32, permuted by the beam search instead
  * of the caches). If status_dev != NULL the step is read from status_dev[1] (device-side
- * loop index). dh == 64. */
+ * loop index). dh in {8, 16, 32, 64, 128}, anything else: OS2S_ERR_UNSUPPORTED. */
 int os2s_decode_self_attention(os2s_stream_t stream, const uint16_t* q, long long ldq,
                                const uint16_t* knew, const uint16_t* vnew, long long ldnew,
                                uint16_t* kcache, uint16_t* vcache, int32_t* ancestry, int N,
@@ -832,7 +835,7 @@ int os2s_decode_self_attention(os2s_stream_t stream, const uint16_t* q, long lon
                                float scale, uint16_t* o, long long ldo);
 /* Encoder-decoder attention for one query per beam row over the PACKED encoder keys/values
  * [N_src, ldkv] projected once per sentence; beam row n attends sentence n / beam
- * (tokens cu_k[b] .. cu_k[b+1]). */
+ * (tokens cu_k[b] .. cu_k[b+1]). dh as for os2s_decode_self_attention. */
 int os2s_decode_cross_attention(os2s_stream_t stream, const uint16_t* q, long long ldq,
                                 const uint16_t* k, const uint16_t* v, long long ldkv,
                                 const int32_t* cu_k, int beam, int N, int H, int dh,

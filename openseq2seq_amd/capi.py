@@ -1202,11 +1202,21 @@ def add_bf16(a, b, out=None):
   return out
 
 
-def attention_fwd(q, k, v, cu_q, cu_k, H, max_len, causal, scale, keep_prob=1.0, seed=0):
-  """q [Nq, >=H*64] / k, v [Nk, ...] bf16 row-major views (row stride = .stride(0));
-  returns (o [Nq, H*64], lse [Nq, H])."""
+ATTENTION_HEAD_DIMS = (8, 16, 32, 64, 128)
+
+
+def _check_head_dim(dh):
+  if dh not in ATTENTION_HEAD_DIMS:
+    raise NotImplementedError("the HIP attention kernels are built for head dims %s, not %d"
+                              % (", ".join(str(d) for d in ATTENTION_HEAD_DIMS), dh))
+  return int(dh)
+
+
+def attention_fwd(q, k, v, cu_q, cu_k, H, max_len, causal, scale, keep_prob=1.0, seed=0, dh=64):
+  """q [Nq, >=H*dh] / k, v [Nk, ...] bf16 row-major views (row stride = .stride(0));
+  returns (o [Nq, H*dh], lse [Nq, H]). dh: one of ATTENTION_HEAD_DIMS."""
   Nq = q.shape[0]
-  dh = 64
+  dh = _check_head_dim(dh)
   B = cu_q.numel() - 1
   o = torch.empty((Nq, H * dh), dtype=torch.bfloat16, device=q.device)
   lse = torch.empty((Nq, H), dtype=torch.float32, device=q.device)
@@ -1218,12 +1228,13 @@ def attention_fwd(q, k, v, cu_q, cu_k, H, max_len, causal, scale, keep_prob=1.0,
 
 
 def attention_bwd(q, k, v, d_o, lse, dq, dk, dv, cu_q, cu_k, H, max_len, causal, scale,
-                  keep_prob=1.0, seed=0):
+                  keep_prob=1.0, seed=0, dh=64):
+  dh = _check_head_dim(dh)
   B = cu_q.numel() - 1
   _lib.C.os2s_attention_bwd(_stream(), c_void_p(q.data_ptr()), c_void_p(k.data_ptr()), c_void_p(v.data_ptr()),
                             _ptr(d_o, torch.bfloat16), _ptr(lse, torch.float32), c_void_p(dq.data_ptr()),
                             c_void_p(dk.data_ptr()), c_void_p(dv.data_ptr()), _ptr(cu_q, torch.int32),
-                            _ptr(cu_k, torch.int32), B, H, 64, int(max_len), q.stride(0), k.stride(0),
+                            _ptr(cu_k, torch.int32), B, H, dh, int(max_len), q.stride(0), k.stride(0),
                             v.stride(0), d_o.stride(0), dq.stride(0), dk.stride(0), dv.stride(0), int(causal),
                             float(scale), float(keep_prob), int(seed) & (2**64 - 1))
 
@@ -1361,12 +1372,13 @@ def gather_rows(src, idx, enable=None, out=None):
 def decode_self_attention(q, knew, vnew, kcache, vcache, ancestry, H, step, scale, status=None):
   """q/knew/vnew: bf16 [N, D] column slices of one row-major buffer; caches [N, Tmax, D]."""
   N, D = q.shape
+  dh = _check_head_dim(D // H)
   Tmax = kcache.shape[1]
   o = torch.empty((N, D), dtype=torch.bfloat16, device=q.device)
   assert knew.stride(0) == vnew.stride(0) and q.stride(1) == 1 and knew.stride(1) == 1
   _lib.C.os2s_decode_self_attention(_stream(), c_void_p(q.data_ptr()), q.stride(0), c_void_p(knew.data_ptr()),
                                     c_void_p(vnew.data_ptr()), knew.stride(0), _ptr(kcache, torch.bfloat16),
-                                    _ptr(vcache, torch.bfloat16), _ptr(ancestry, torch.int32), N, H, D // H, Tmax,
+                                    _ptr(vcache, torch.bfloat16), _ptr(ancestry, torch.int32), N, H, dh, Tmax,
                                     int(step), _ptr(status, allow_none=True), float(scale), _ptr(o), D)
   return o
 
@@ -1374,11 +1386,12 @@ def decode_self_attention(q, knew, vnew, kcache, vcache, ancestry, H, step, scal
 def decode_cross_attention(q, k, v, cu_k, beam, H, max_len, scale):
   """q bf16 [N, D]; k, v: column slices [N_src, D] of the packed encoder projections."""
   N, D = q.shape
+  dh = _check_head_dim(D // H)
   o = torch.empty((N, D), dtype=torch.bfloat16, device=q.device)
   assert k.stride(0) == v.stride(0) and k.stride(1) == 1 and q.stride(1) == 1
   _lib.C.os2s_decode_cross_attention(_stream(), c_void_p(q.data_ptr()), q.stride(0), c_void_p(k.data_ptr()),
                                      c_void_p(v.data_ptr()), k.stride(0), _ptr(cu_k, torch.int32), int(beam), N, H,
-                                     D // H, int(max_len), float(scale), _ptr(o), D)
+                                     dh, int(max_len), float(scale), _ptr(o), D)
   return o
 
 

@@ -656,12 +656,17 @@ __global__ __launch_bounds__(kBwdThreads) void attn_bwd_kernel(AttnArgs p) {
 
 }  // namespace os2s
 
+#include "attention_dh.hpp"      // the same three kernels for head dims 8, 16, 32 and 128
+
 using namespace os2s;
+
+// dh == 64 launches the tuned kernels above; 8, 16, 32 and 128 the family of attention_dh.hpp
+static bool attn_dh_ok(int dh) { return dh == kDh || dh == 8 || dh == 16 || dh == 32 || dh == 128; }
 
 static int attn_check(const int32_t* cu_q, const int32_t* cu_k, int B, int H, int dh, int max_len) {
   if (!cu_q || !cu_k || B < 1 || H < 1) return OS2S_ERR_INVALID_ARG;
   if ((long long)B * H >= (1ll << 30)) return OS2S_ERR_INVALID_ARG;
-  if (dh != kDh || max_len > kL) return OS2S_ERR_UNSUPPORTED;
+  if (!attn_dh_ok(dh) || max_len > kL) return OS2S_ERR_UNSUPPORTED;
   return OS2S_OK;
 }
 
@@ -683,6 +688,10 @@ extern "C" int os2s_attention_fwd(os2s_stream_t stream, const uint16_t* q, const
   a.q = q; a.k = k; a.v = v; a.o = o; a.lse = lse; a.cu_q = cu_q; a.cu_k = cu_k; a.B = B; a.H = H;
   a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.ldo = ldo; a.causal = causal; a.scale = scale;
   a.keep_prob = keep_prob; a.seed = seed;
+  if (dh != kDh) {
+    OS2S_REQUIRE(ldq >= dh && ldk >= dh && ldv >= dh && ldo >= dh);
+    return attn_fwd_dh((hipStream_t)stream, a, dh, max_len);
+  }
   const size_t smem = (size_t)kFwdWaves * 16384;
   if (max_len > kL) {      // multi-tile forward (inference); no attention dropout on this path
     if (keep_prob < 1.f) return OS2S_ERR_UNSUPPORTED;
@@ -727,6 +736,11 @@ extern "C" int os2s_attention_bwd(os2s_stream_t stream, const uint16_t* q, const
   a.B = B; a.H = H; a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.causal = causal; a.scale = scale;
   a.keep_prob = keep_prob; a.seed = seed; a.d_o = d_o; a.dq = dq; a.dk = dk; a.dv = dv;
   a.lddo = lddo; a.lddq = lddq; a.lddk = lddk; a.lddv = lddv;
+  if (dh != kDh) {
+    OS2S_REQUIRE(ldq >= dh && ldk >= dh && ldv >= dh && lddo >= dh && lddq >= dh && lddk >= dh && lddv >= dh);
+    OS2S_REQUIRE(lddq < kMaxLd && lddk < kMaxLd && lddv < kMaxLd);
+    return attn_bwd_dh((hipStream_t)stream, a, dh);
+  }
   const size_t smem = (size_t)kBwdLds;      // 40 KB: under the default dynamic limit
   if (keep_prob < 1.f)
     OS2S_LAUNCH(attn_bwd_kernel<true>, dim3((unsigned)((long long)B * H)), dim3(kBwdThreads), smem, (hipStream_t)stream, a);

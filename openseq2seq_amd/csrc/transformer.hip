@@ -14,6 +14,7 @@
 #include <cstdlib>
 #include "os2s_common.hpp"
 #include "ln_rows.hpp"
+#include "ln_any.hpp"
 
 namespace os2s {
 
@@ -635,6 +636,9 @@ extern "C" int os2s_layernorm_fwd(os2s_stream_t stream, const uint16_t* x, const
   } else if (D == 512) {
     OS2S_LAUNCH(layernorm_fwd_kernel<1>, grid, dim3(256), 0, (hipStream_t)stream, x, gamma, beta, eps,
                 N, y, mean, rstd);
+  } else if (ln_any_width_ok(D)) {      // every other width: the row kernel with a runtime column loop
+    OS2S_LAUNCH(layernorm_any_fwd_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, x, gamma, beta, eps,
+                N, D, y, mean, rstd);
   } else {
     return OS2S_ERR_UNSUPPORTED;
   }
@@ -661,6 +665,9 @@ extern "C" int os2s_layernorm_bwd(os2s_stream_t stream, const uint16_t* dy, cons
   } else if (D == 512) {
     OS2S_LAUNCH(layernorm_bwd_kernel<1>, grid, dim3(64 * kLnWaves), 0, (hipStream_t)stream, dy, x, gamma, mean,
                 rstd, dres, N, kLnRowsPerBlock, dx, partial);
+  } else if (ln_any_width_ok(D)) {
+    OS2S_LAUNCH(layernorm_any_bwd_kernel<false>, grid, dim3(512), 0, (hipStream_t)stream, dy, x, gamma, mean,
+                rstd, dres, N, D, kLnRowsPerBlock, dx, partial);
   } else {
     return OS2S_ERR_UNSUPPORTED;
   }

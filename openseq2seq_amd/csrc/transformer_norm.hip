@@ -11,6 +11,7 @@
 //     affine apply and the two backward passes (one reduction, one apply that adds the residual gradient).
 #include "os2s_common.hpp"
 #include "ln_rows.hpp"
+#include "ln_any.hpp"
 
 namespace os2s {
 
@@ -334,6 +335,9 @@ extern "C" int os2s_layernorm_l1_fwd(os2s_stream_t stream, const uint16_t* x, co
   } else if (D == 512) {
     OS2S_LAUNCH(layernorm_l1_fwd_kernel<1>, grid, dim3(256), 0, (hipStream_t)stream, x, gamma, beta, eps,
                 N, y, mean, rinv);
+  } else if (ln_any_width_ok(D)) {      // every other width: the row kernel with a runtime column loop
+    OS2S_LAUNCH(layernorm_any_fwd_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, x, gamma, beta, eps,
+                N, D, y, mean, rinv);
   } else {
     return OS2S_ERR_UNSUPPORTED;
   }
@@ -355,6 +359,9 @@ extern "C" int os2s_layernorm_l1_bwd(os2s_stream_t stream, const uint16_t* dy, c
   } else if (D == 512) {
     OS2S_LAUNCH(layernorm_l1_bwd_kernel<1>, grid, dim3(64 * kL1Waves), 0, (hipStream_t)stream, dy, x, gamma, mean,
                 rinv, dres, N, kL1RowsPerBlock, dx, partial);
+  } else if (ln_any_width_ok(D)) {
+    OS2S_LAUNCH(layernorm_any_bwd_kernel<true>, grid, dim3(512), 0, (hipStream_t)stream, dy, x, gamma, mean,
+                rinv, dres, N, D, kL1RowsPerBlock, dx, partial);
   } else {
     return OS2S_ERR_UNSUPPORTED;
   }

@@ -102,7 +102,8 @@ class TransformerDecoder(Decoder):
       x = lyr["ffn"].forward(y, tape, seeds, relu_keep, post_keep, residual=x)
     out = self.output_normalization.forward(x, tape)
     logits = emb.linear(out, tape)
-    return {"logits": logits.data, "logits_act": logits, "packed_target": pt,
+    # vocab_size: the logical vocabulary — logits has emb.Vpad >= emb.V columns (L.SharedEmbedding)
+    return {"logits": logits.data, "logits_act": logits, "packed_target": pt, "vocab_size": emb.V,
             "outputs": None, "final_state": None, "final_sequence_lengths": None}
 
   # ---- inference: beam search (transformer_decoder.py:232-326) --------------------------------

@@ -2,7 +2,9 @@
 PaddedCrossEntropyLossWithSmoothing — open_seq2seq/losses/sequence_loss.py:233-309 on the
 fused HIP kernel: soft targets (1-s at the label, s/(V-1) elsewhere), minus the smoothing
 entropy constant, weights = (label != 0), sum / sum(weights). In the packed layout every
-row is a non-pad target position, so sum(weights) = number of rows."""
+row is a non-pad target position, so sum(weights) = number of rows. V is the decoder's logical
+vocabulary ("vocab_size" of its output): logits columns past it are device padding and enter
+neither the softmax nor the smoothing."""
 from __future__ import absolute_import, division, print_function
 
 from .loss import Loss
@@ -29,7 +31,7 @@ class PaddedCrossEntropyLossWithSmoothing(Loss):
     want_grad = la is not None and input_dict.get("want_grad", True)
     _, mean, dl = capi.xent_smooth(logits, labels, self._label_smoothing,
                                    grad_scale_dev=input_dict.get("loss_scale_dev"),
-                                   want_grad=want_grad)
+                                   want_grad=want_grad, v_valid=dec.get("vocab_size"))
     if want_grad:
       la.grad = dl
       la.grad_init = True

@@ -131,6 +131,10 @@ class Text2Text(EncoderDecoderModel):
     from ..utils.metrics import corpus_bleu
     dl = self.get_data_layer()
     hyps, refs = [], []
+    if max_batches is None and dl.params.get('repeat', False):
+      # an evaluation is ONE pass over the files (the reference runs size / batch steps, utils/funcs.py:293-340),
+      # also under "repeat": True, which the reference's toy configs set because they evaluate many times
+      max_batches = -(-len(dl.load()) // dl.params['batch_size'])
     for n, batch in enumerate(dl.iterate_batches(device or self._device, drop_remainder=False)):
       if max_batches is not None and n >= max_batches:
         break

@@ -212,9 +212,13 @@ class MultiHeadAttention(object):
 
   def __init__(self, store, name, hidden, num_heads, self_attention, kv=None, l2=0.0):
     self.D, self.H, self.self_att = hidden, num_heads, self_attention
-    self.scale = (hidden // num_heads) ** -0.5
-    if hidden // num_heads != 64:
-      raise NotImplementedError("HIP attention kernel is built for head dim 64")
+    if hidden % num_heads:
+      raise ValueError("hidden size %d is not a multiple of num_heads %d" % (hidden, num_heads))
+    self.dh = hidden // num_heads
+    self.scale = self.dh ** -0.5
+    if self.dh not in capi.ATTENTION_HEAD_DIMS:
+      raise NotImplementedError("the HIP attention kernels are built for head dims %s, not %d (hidden %d / %d heads)"
+                                % (", ".join(str(d) for d in capi.ATTENTION_HEAD_DIMS), self.dh, hidden, num_heads))
     if self_attention:
       self.qkv = Dense(store, name + "/qkv", hidden, 3 * hidden, False, l2=l2)
     else:
@@ -243,7 +247,7 @@ class MultiHeadAttention(object):
       qv, kv_, vv = q.data, kv.data[:, :D], kv.data[:, D:]
     seed = seeds.next()
     o, lse = capi.attention_fwd(qv, kv_, vv, cu_q, cu_k, H, max_len, causal, self.scale,
-                                att_keep, seed)
+                                att_keep, seed, dh=self.dh)
     oa = Act(o)
     if tape is not None:
       att = self
@@ -254,20 +258,20 @@ class MultiHeadAttention(object):
         if att.self_att:
           g = torch.empty_like(qkv.data)
           capi.attention_bwd(qv, kv_, vv, d_o, lse, g[:, :D], g[:, D:2 * D], g[:, 2 * D:], cu_q,
-                             cu_k, H, max_len, causal, att.scale, att_keep, seed)
+                             cu_k, H, max_len, causal, att.scale, att_keep, seed, dh=att.dh)
           qkv.grad = g
         elif kv_all is not None:
           # this layer's columns of the fused gradient; FusedCrossKV's closure runs after every layer's
           gq = torch.empty_like(q.data)
           gkv = kv_all.grad_buffer()[:, lidx * 2 * D:(lidx + 1) * 2 * D]
           capi.attention_bwd(qv, kv_, vv, d_o, lse, gq, gkv[:, :D], gkv[:, D:], cu_q, cu_k, H,
-                             max_len, causal, att.scale, att_keep, seed)
+                             max_len, causal, att.scale, att_keep, seed, dh=att.dh)
           q.grad = gq
         else:
           gq = torch.empty_like(q.data)
           gkv = torch.empty_like(kv.data)
           capi.attention_bwd(qv, kv_, vv, d_o, lse, gq, gkv[:, :D], gkv[:, D:], cu_q, cu_k, H,
-                             max_len, causal, att.scale, att_keep, seed)
+                             max_len, causal, att.scale, att_keep, seed, dh=att.dh)
           q.grad, kv.grad = gq, gkv
         oa.grad = None
 
@@ -358,24 +362,33 @@ class FeedForward(object):
 
 class SharedEmbedding(object):
   """EmbeddingSharedWeights (embedding_layer.py:26-105): one [V, D] matrix used for the
-  input embeddings of both stacks and, transposed, for the pre-softmax projection."""
+  input embeddings of both stacks and, transposed, for the pre-softmax projection.
+
+  pad_vocab_to_eight (the reference's pad_embeddings_2_eight) rounds V itself up: the extra rows are real, trained
+  vocabulary, as in the reference. Any other V that is no multiple of 8 keeps its logical size — the variable is
+  [V, D] in checkpoints (logical_out) and V is what the loss, the beam search and an argmax see (`V`) — while the
+  device table has Vpad = V rounded up to 8 rows (the GEMMs' and the loss kernel's 16-byte vectors). The padding
+  rows are zero and stay zero: no id selects them and their logit columns carry no probability and no gradient
+  (os2s_xent_smooth V_valid), so their weight gradient is exactly zero."""
 
   def __init__(self, store, name, vocab_size, hidden, pad_vocab_to_eight=False):
     if pad_vocab_to_eight and vocab_size % 8:
       vocab_size += 8 - vocab_size % 8
-    if vocab_size % 8:
-      raise NotImplementedError("vocab size must be a multiple of 8 (use pad_vocab_to_eight)")
     self.V, self.D = vocab_size, hidden
+    self.Vpad = -(-vocab_size // 8) * 8
+    V = vocab_size
 
     def init(shape):   # random_normal_initializer(0, hidden**-0.5)
-      return torch.randn(shape) * hidden ** -0.5
+      w = torch.randn(shape) * hidden ** -0.5
+      w[:, V:, :] = 0.0          # vocabulary padding rows
+      return w
 
-    self.weights = store.add(name + "/embedding_and_softmax/weights", (1, vocab_size, hidden),
-                             init, kind="conv")
+    self.weights = store.add(name + "/embedding_and_softmax/weights", (1, self.Vpad, hidden),
+                             init, kind="conv", logical_out=V if self.Vpad != V else None)
 
   @property
   def table(self):
-    return self.weights.w16.view(self.V, self.D)
+    return self.weights.w16.view(self.Vpad, self.D)
 
   def embed(self, ids, pos, tape, keep, seed, final_use=False):
     """final_use: True for the FIRST use in forward order (= the last closure of the
@@ -390,7 +403,7 @@ class SharedEmbedding(object):
           # table — the softmax weight gradient and both embedding scatters — sit on that ONE stream,
           # in order: the scatter's atomics must not interleave with the GEMM's read-modify-write)
           with on_side_stream(out.grad.device, ids, out.grad):
-            capi.embed_bwd(ids, out.grad, emb.weights.grad.view(emb.V, emb.D), emb.D ** 0.5, keep,
+            capi.embed_bwd(ids, out.grad, emb.weights.grad.view(emb.Vpad, emb.D), emb.D ** 0.5, keep,
                            seed)
         out.grad = None
 
@@ -398,7 +411,7 @@ class SharedEmbedding(object):
     return out
 
   def linear(self, x, tape):
-    """logits = x E^T  (bf16 [N, V])."""
+    """logits = x E^T  (bf16 [N, Vpad]; columns >= V are the zero padding rows' and count nowhere)."""
     if tape is None and x.data.shape[0] <= dense.SKINNY_MAX_ROWS and SKINNY_LOGITS:
       return Act(capi.gemm_skinny(x.data, self.table))
     out = Act(capi.gemm(x.data, self.table))
@@ -410,8 +423,8 @@ class SharedEmbedding(object):
         assert dy is not None
         g = x.grad_buffer()
         with on_side_stream(dy.device, x.data, dy):
-          capi.gemm_wgrad(x.data, dy, emb.weights.grad.view(emb.V, emb.D), accumulate=True)
-        capi.gemm(dy, emb.weights.wt16.view(emb.D, emb.V), out=g, accumulate=x.grad_init)
+          capi.gemm_wgrad(x.data, dy, emb.weights.grad.view(emb.Vpad, emb.D), accumulate=True)
+        capi.gemm(dy, emb.weights.wt16.view(emb.D, emb.Vpad), out=g, accumulate=x.grad_init)
         x.grad_init = True
         out.grad = None
 
