@@ -695,15 +695,9 @@ extern "C" int os2s_attention_fwd(os2s_stream_t stream, const uint16_t* q, const
   const size_t smem = (size_t)kFwdWaves * 16384;
   if (max_len > kL) {      // multi-tile forward (inference); no attention dropout on this path
     if (keep_prob < 1.f) return OS2S_ERR_UNSUPPORTED;
-    static bool attr_long = false;
-    if (!attr_long) {
-      if (hipFuncSetAttribute((const void*)attn_fwd_long_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)smem) != hipSuccess) return OS2S_ERR_LAUNCH;
-      attr_long = true;
-    }
     const int q_tiles = (max_len + kL - 1) / kL;
-    OS2S_LAUNCH(attn_fwd_long_kernel, dim3(ceil_div((long long)B * H * q_tiles, kFwdWaves)),
-                dim3(kFwdWaves * 64), smem, (hipStream_t)stream, a, q_tiles);
+    OS2S_LAUNCH_LDS(attn_fwd_long_kernel, dim3(ceil_div((long long)B * H * q_tiles, kFwdWaves)),
+                    dim3(kFwdWaves * 64), smem, (hipStream_t)stream, a, q_tiles);
     return OS2S_OK;
   }
   const size_t smem1 = (size_t)kFwdWaves * 8192;     // one V^T image per wave

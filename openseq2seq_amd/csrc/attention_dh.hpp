@@ -545,15 +545,6 @@ __global__ __launch_bounds__(kBwdThreads) void attn_bwd_dh_kernel(AttnArgs p) {
 // ---- host side -------------------------------------------------------------------------------------
 namespace os2s {
 
-// hipFuncSetAttribute once per kernel: launches above the default 64 KB of dynamic LDS (and the ones at it)
-static int attn_raise_lds(const void* fn, size_t smem, bool& done) {
-  if (smem < 48 * 1024 || done) return OS2S_OK;
-  if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess)
-    return OS2S_ERR_LAUNCH;
-  done = true;
-  return OS2S_OK;
-}
-
 template <int DH>
 static int attn_fwd_dh_launch(hipStream_t st, const AttnArgs& a, int max_len) {
   using HD = HeadDim<DH>;
@@ -561,26 +552,17 @@ static int attn_fwd_dh_launch(hipStream_t st, const AttnArgs& a, int max_len) {
   if (max_len > kL) {      // multi-tile forward (inference); no attention dropout on this path
     if (a.keep_prob < 1.f) return OS2S_ERR_UNSUPPORTED;
     const size_t smem = (size_t)kFwdWaves * (1 + HD::kImgs) * 8192;       // 64 KB, 96 KB at DH = 128
-    static bool attr = false;
-    const int rc = attn_raise_lds((const void*)attn_fwd_long_dh_kernel<DH>, smem, attr);
-    if (rc != OS2S_OK) return rc;
     const int q_tiles = (max_len + kL - 1) / kL;
-    OS2S_LAUNCH(attn_fwd_long_dh_kernel<DH>, dim3(ceil_div((long long)B * H * q_tiles, kFwdWaves)),
-                dim3(kFwdWaves * 64), smem, st, a, q_tiles);
+    OS2S_LAUNCH_LDS(attn_fwd_long_dh_kernel<DH>, dim3(ceil_div((long long)B * H * q_tiles, kFwdWaves)),
+                    dim3(kFwdWaves * 64), smem, st, a, q_tiles);
     return OS2S_OK;
   }
   const size_t smem = (size_t)kFwdWaves * HD::kImgs * 8192;               // 32 KB, 64 KB at DH = 128
   const dim3 grid(ceil_div((long long)B * H, kFwdWaves)), block(kFwdWaves * 64);
   if (a.keep_prob < 1.f) {
-    static bool attr = false;
-    const int rc = attn_raise_lds((const void*)attn_fwd_dh_kernel<DH, true>, smem, attr);
-    if (rc != OS2S_OK) return rc;
-    OS2S_LAUNCH((attn_fwd_dh_kernel<DH, true>), grid, block, smem, st, a);
+    OS2S_LAUNCH_LDS((attn_fwd_dh_kernel<DH, true>), grid, block, smem, st, a);
   } else {
-    static bool attr = false;
-    const int rc = attn_raise_lds((const void*)attn_fwd_dh_kernel<DH, false>, smem, attr);
-    if (rc != OS2S_OK) return rc;
-    OS2S_LAUNCH((attn_fwd_dh_kernel<DH, false>), grid, block, smem, st, a);
+    OS2S_LAUNCH_LDS((attn_fwd_dh_kernel<DH, false>), grid, block, smem, st, a);
   }
   return OS2S_OK;
 }
@@ -590,15 +572,9 @@ static int attn_bwd_dh_launch(hipStream_t st, const AttnArgs& a) {
   const size_t smem = (size_t)attn_bwd_dh_lds<DH>();                      // 56 KB, 80 KB at DH = 128
   const dim3 grid((unsigned)((long long)a.B * a.H)), block(kBwdThreads);
   if (a.keep_prob < 1.f) {
-    static bool attr = false;
-    const int rc = attn_raise_lds((const void*)attn_bwd_dh_kernel<DH, true>, smem, attr);
-    if (rc != OS2S_OK) return rc;
-    OS2S_LAUNCH((attn_bwd_dh_kernel<DH, true>), grid, block, smem, st, a);
+    OS2S_LAUNCH_LDS((attn_bwd_dh_kernel<DH, true>), grid, block, smem, st, a);
   } else {
-    static bool attr = false;
-    const int rc = attn_raise_lds((const void*)attn_bwd_dh_kernel<DH, false>, smem, attr);
-    if (rc != OS2S_OK) return rc;
-    OS2S_LAUNCH((attn_bwd_dh_kernel<DH, false>), grid, block, smem, st, a);
+    OS2S_LAUNCH_LDS((attn_bwd_dh_kernel<DH, false>), grid, block, smem, st, a);
   }
   return OS2S_OK;
 }

@@ -1499,14 +1499,7 @@ static bool ad_fast_score_bwd(const os2s_attn_decoder_t* d) {
 static int ad_launch_fast_score_bwd(hipStream_t stream, const AdAttn& at, const AdLoc& lx,
                                     const os2s_attn_decoder_t* d) {
   const size_t lds = ad_score_bwd_mfma_lds_floats(d->S) * sizeof(float);
-  static size_t attr_for = 0;
-  if (lds > 64 * 1024 && lds > attr_for) {
-    if (hipFuncSetAttribute((const void*)ad_loc_score_bwd_mfma_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)lds) != hipSuccess)
-      return OS2S_ERR_LAUNCH;
-    attr_for = lds;
-  }
-  OS2S_LAUNCH(ad_loc_score_bwd_mfma_kernel, dim3(kLocParts, d->B), dim3(kAttnThreads), lds, stream, at, lx);
+  OS2S_LAUNCH_LDS(ad_loc_score_bwd_mfma_kernel, dim3(kLocParts, d->B), dim3(kAttnThreads), lds, stream, at, lx);
   return OS2S_OK;
 }
 
@@ -2047,9 +2040,6 @@ extern "C" int os2s_attn_decoder_fwd(os2s_stream_t stream_, const os2s_attn_deco
   if (rc != OS2S_OK) return rc;
   hipStream_t stream = (hipStream_t)stream_;
   const size_t lds = attn_lds_bytes(d, false);
-  if (lds > 64 * 1024 &&
-      hipFuncSetAttribute((const void*)ad_attn_fwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-    return OS2S_ERR_LAUNCH;
   const int B = d->B, T = d->T, H = d->H, M = d->M, L = d->L;
   AdAttn at;
   ad_fill_attn(d, at);
@@ -2102,7 +2092,7 @@ extern "C" int os2s_attn_decoder_fwd(os2s_stream_t stream_, const os2s_attn_deco
       }
       OS2S_LAUNCH(ad_loc_context_kernel, dim3(ctx_parts, B), dim3(256), lds_c, stream, at, lx, ncg, nsp);
     } else {
-      OS2S_LAUNCH(ad_attn_fwd_kernel, dim3(B), dim3(kAttnThreads), lds, stream, at);
+      OS2S_LAUNCH_LDS(ad_attn_fwd_kernel, dim3(B), dim3(kAttnThreads), lds, stream, at);
     }
   }
   return OS2S_OK;
@@ -2147,9 +2137,6 @@ extern "C" int os2s_attn_decoder_bwd(os2s_stream_t stream_, const os2s_attn_deco
   OS2S_REQUIRE(d->t_begin == 0 && d->t_end == d->T);
   hipStream_t stream = (hipStream_t)stream_;
   const size_t lds = attn_lds_bytes(d, true);
-  if (lds > 64 * 1024 &&
-      hipFuncSetAttribute(d->score_mode == 2 ? (const void*)ad_attn_bwd_kernel<true> : (const void*)ad_attn_bwd_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-    return OS2S_ERR_LAUNCH;
   const int B = d->B, T = d->T, H = d->H, M = d->M, L = d->L, U = d->U, S = d->S;
   const int K = d->loc_k, F = d->loc_f;
   if (hipMemsetAsync(workspace, 0, os2s_attn_decoder_bwd_workspace_bytes(d), stream) != hipSuccess) return OS2S_ERR_LAUNCH;
@@ -2181,9 +2168,6 @@ extern "C" int os2s_attn_decoder_bwd(os2s_stream_t stream_, const os2s_attn_deco
   int* const da_ticket = reinterpret_cast<int*>(ws); ws += nda;
   const size_t lds_da = ((size_t)M + ceil_div(S, kLocCtxParts)) * sizeof(float);
   const size_t lds_sb = loc_bwd_lds_floats(S, K) * sizeof(float);
-  if (split && lds_sb > 64 * 1024 &&
-      hipFuncSetAttribute((const void*)ad_loc_score_bwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_sb) != hipSuccess)
-    return OS2S_ERR_LAUNCH;
   // gate gradients of finished steps are zero; dkeys accumulates
   for (int l = 0; l < L; ++l)
     if (hipMemsetAsync(gr->dg[l], 0, (size_t)B * T * 4 * H * 2, stream) != hipSuccess) return OS2S_ERR_LAUNCH;
@@ -2221,10 +2205,10 @@ extern "C" int os2s_attn_decoder_bwd(os2s_stream_t stream_, const os2s_attn_deco
         const int r2 = ad_launch_fast_score_bwd(stream, at, lx, d);
         if (r2 != OS2S_OK) return r2;
       } else {
-        OS2S_LAUNCH(ad_loc_score_bwd_kernel, dim3(kLocParts, B), dim3(kAttnThreads), lds_sb, stream, at, lx);
+        OS2S_LAUNCH_LDS(ad_loc_score_bwd_kernel, dim3(kLocParts, B), dim3(kAttnThreads), lds_sb, stream, at, lx);
       }
-    } else if (d->score_mode == 2) { OS2S_LAUNCH(ad_attn_bwd_kernel<true>, dim3(B), dim3(kAttnThreads), lds, stream, at); }
-    else { OS2S_LAUNCH(ad_attn_bwd_kernel<false>, dim3(B), dim3(kAttnThreads), lds, stream, at); }
+    } else if (d->score_mode == 2) { OS2S_LAUNCH_LDS(ad_attn_bwd_kernel<true>, dim3(B), dim3(kAttnThreads), lds, stream, at); }
+    else { OS2S_LAUNCH_LDS(ad_attn_bwd_kernel<false>, dim3(B), dim3(kAttnThreads), lds, stream, at); }
     for (int l = L - 1; l >= 0; --l) {
       AdCellBwd c;
       c.B = B; c.T = T; c.H = H; c.t = t; c.last = last; c.forget_bias = d->forget_bias; c.lens = d->tgt_len;

@@ -1041,11 +1041,9 @@ static int launch_conv(hipStream_t stream, ConvArgs& a) {
   size_t epi_bytes = conv_epilogue_lds_bytes<BM, BN, NWIN, NTHR>();
   size_t smem = main_bytes > epi_bytes ? main_bytes : epi_bytes;
   if (smem > 160 * 1024) return OS2S_ERR_UNSUPPORTED;
-  static const hipError_t attr_rc = opt_in_lds_160k({(const void*)conv1d_igemm_kernel<BM, BN, WM, WN, NWIN, XSINGLE>});
-  if (attr_rc != hipSuccess) return OS2S_ERR_LAUNCH;
   const int grid = a.MT8 * 8 * a.NT;
-  OS2S_LAUNCH((conv1d_igemm_kernel<BM, BN, WM, WN, NWIN, XSINGLE>), dim3(grid), dim3(NTHR), smem,
-              stream, a);
+  OS2S_LAUNCH_LDS((conv1d_igemm_kernel<BM, BN, WM, WN, NWIN, XSINGLE>), dim3(grid), dim3(NTHR), smem,
+                  stream, a);
   return OS2S_OK;
 }
 
@@ -1114,11 +1112,7 @@ static int launch_conv_pp(hipStream_t stream, ConvArgs& a, void* workspace, size
   a.pp_tile = tile;
   a.pp_c256 = g_pp_cost[0]; a.pp_c2 = g_pp_cost[1]; a.pp_c3 = g_pp_cost[2]; a.pp_dgrad_pen = g_pp_cost[3];
   a.pp_prio = g_pp_prio;
-  static const hipError_t attr_rc = opt_in_lds_160k({
-      (const void*)conv1d_pp_kernel<false>, (const void*)conv1d_pp_kernel<true>,
-      (const void*)conv1d_ppn_kernel<false>, (const void*)conv1d_ppn_kernel<true>});
-  if (attr_rc != hipSuccess) return OS2S_ERR_LAUNCH;
-  a.ncu = split_ncu();
+  a.ncu = device_cus();
   const SplitWorkspace ws = split_carve(workspace, workspace_bytes, a.ncu);
   a.ws_cnt = ws.tickets; a.ws_slabs = ws.slabs; a.ws_nslabs = ws.nslabs;
   // a forward launch whose lengths the host knows (no mask at all, or the caller's host copy): the tile
@@ -1141,17 +1135,17 @@ static int launch_conv_pp(hipStream_t stream, ConvArgs& a, void* workspace, size
   if (tile <= 0) {
     const int grid = ceil_div(a.MT, NWIN) * a.NT + a.ws_nslabs + nzero;
     if (dbg) {
-      OS2S_LAUNCH(conv1d_pp_kernel<true>, dim3(grid), dim3(NTHR), smem, stream, a);
+      OS2S_LAUNCH_LDS(conv1d_pp_kernel<true>, dim3(grid), dim3(NTHR), smem, stream, a);
     } else {
-      OS2S_LAUNCH(conv1d_pp_kernel<false>, dim3(grid), dim3(NTHR), smem, stream, a);
+      OS2S_LAUNCH_LDS(conv1d_pp_kernel<false>, dim3(grid), dim3(NTHR), smem, stream, a);
     }
   }
   if (tile != 0 && (a.pp_ok2 || a.pp_ok3)) {
     const int grid = ceil_div(a.MT, 2) * ceil_div(a.Cout, 128) + nzero;
     if (dbg_n) {
-      OS2S_LAUNCH(conv1d_ppn_kernel<true>, dim3(grid), dim3(NTHR), smem_n, stream, a);
+      OS2S_LAUNCH_LDS(conv1d_ppn_kernel<true>, dim3(grid), dim3(NTHR), smem_n, stream, a);
     } else {
-      OS2S_LAUNCH(conv1d_ppn_kernel<false>, dim3(grid), dim3(NTHR), smem_n, stream, a);
+      OS2S_LAUNCH_LDS(conv1d_ppn_kernel<false>, dim3(grid), dim3(NTHR), smem_n, stream, a);
     }
   }
   return OS2S_OK;
@@ -1410,10 +1404,8 @@ static int conv1x1_fwd_grouped_impl(os2s_stream_t stream, const os2s_conv_group_
   constexpr size_t kOP = BN * 2 + 16;
   const size_t epi_bytes = conv_epilogue_lds_bytes<BM, BN, 1, 256>();
   const size_t smem = main_bytes > epi_bytes ? main_bytes : epi_bytes;
-  static const hipError_t attr_rc = opt_in_lds_160k({(const void*)conv1d_igemm_grouped_kernel<128, 128, 2, 2>});
-  if (attr_rc != hipSuccess) return OS2S_ERR_LAUNCH;
-  OS2S_LAUNCH((conv1d_igemm_grouped_kernel<128, 128, 2, 2>), dim3(tiles), dim3(256), smem,
-              (hipStream_t)stream, a, gt);
+  OS2S_LAUNCH_LDS((conv1d_igemm_grouped_kernel<128, 128, 2, 2>), dim3(tiles), dim3(256), smem,
+                  (hipStream_t)stream, a, gt);
   return OS2S_OK;
 }
 

@@ -1202,7 +1202,7 @@ static void wgrad_tap_quad_geometry(os2s::WgradArgs& a, int xbuf_bytes) {
 // (the split factor is decided on the device from the live length of the batch) — whole units, or up to 16 pieces
 // of each unit of the tail.
 static int wgrad_split_grid(os2s::WgradArgs& a, int units, void* workspace, size_t workspace_bytes) {
-  a.ncu = os2s::split_ncu();
+  a.ncu = os2s::device_cus();
   const os2s::SplitWorkspace ws = os2s::split_carve(workspace, workspace_bytes, a.ncu);
   a.ws_cnt = ws.tickets; a.ws_slabs = ws.slabs; a.ws_nslabs = ws.nslabs;
   return units + os2s::split_tail_pieces(units, a.ncu, ws.nslabs);
@@ -1232,10 +1232,8 @@ static os2s::WgradGroupTable wgrad_group_table(const os2s_wgrad_group_t* groups,
 static int launch_wgrad1x1_pp(hipStream_t stream, os2s::WgradArgs a, const os2s::WgradGroupTable& gt, int units,
                               void* workspace, size_t workspace_bytes) {
   using namespace os2s;
-  static const hipError_t attr_rc = opt_in_lds_160k({(const void*)conv1d_wgrad1x1_pp_kernel});
-  if (attr_rc != hipSuccess) return OS2S_ERR_LAUNCH;
   const int grid = wgrad_split_grid(a, units, workspace, workspace_bytes);
-  OS2S_LAUNCH(conv1d_wgrad1x1_pp_kernel, dim3(grid), dim3(512), (size_t)160 * 1024, stream, a, gt);
+  OS2S_LAUNCH_LDS(conv1d_wgrad1x1_pp_kernel, dim3(grid), dim3(512), (size_t)160 * 1024, stream, a, gt);
   return OS2S_OK;
 }
 
@@ -1287,28 +1285,19 @@ static int conv1d_wgrad_impl_g(os2s_stream_t stream, const uint16_t* x, long lon
     wgrad_tap_quad_geometry(a, kSwXBuf);
     const size_t smem = (size_t)kSwRing * (kSwYBuf + kSwXBuf) + a.steptab_bytes;
     if (smem <= 160 * 1024) {
-      static const hipError_t attr_rc = opt_in_lds_160k({
-          (const void*)conv1d_wgrad_sw_kernel<0>,
-#ifdef OS2S_SW_ABLATE
-          (const void*)conv1d_wgrad_sw_kernel<1>, (const void*)conv1d_wgrad_sw_kernel<2>,
-          (const void*)conv1d_wgrad_sw_kernel<4>, (const void*)conv1d_wgrad_sw_kernel<8>,
-          (const void*)conv1d_wgrad_sw_kernel<3>, (const void*)conv1d_wgrad_sw_kernel<5>,
-#endif
-      });
-      if (attr_rc != hipSuccess) return OS2S_ERR_LAUNCH;
       const int grid = wgrad_split_grid(a, pp_units, workspace, workspace_bytes);
 #ifdef OS2S_SW_ABLATE      // measurement build only (tools/sw_ablate.py): the stream with one ingredient removed
       switch (g_wgrad_sw_ablate) {
-        case 1: OS2S_LAUNCH(conv1d_wgrad_sw_kernel<1>, dim3(grid), dim3(256), smem, (hipStream_t)stream, a); return OS2S_OK;
-        case 2: OS2S_LAUNCH(conv1d_wgrad_sw_kernel<2>, dim3(grid), dim3(256), smem, (hipStream_t)stream, a); return OS2S_OK;
-        case 3: OS2S_LAUNCH(conv1d_wgrad_sw_kernel<3>, dim3(grid), dim3(256), smem, (hipStream_t)stream, a); return OS2S_OK;
-        case 4: OS2S_LAUNCH(conv1d_wgrad_sw_kernel<4>, dim3(grid), dim3(256), smem, (hipStream_t)stream, a); return OS2S_OK;
-        case 5: OS2S_LAUNCH(conv1d_wgrad_sw_kernel<5>, dim3(grid), dim3(256), smem, (hipStream_t)stream, a); return OS2S_OK;
-        case 8: OS2S_LAUNCH(conv1d_wgrad_sw_kernel<8>, dim3(grid), dim3(256), smem, (hipStream_t)stream, a); return OS2S_OK;
+        case 1: OS2S_LAUNCH_LDS(conv1d_wgrad_sw_kernel<1>, dim3(grid), dim3(256), smem, (hipStream_t)stream, a); return OS2S_OK;
+        case 2: OS2S_LAUNCH_LDS(conv1d_wgrad_sw_kernel<2>, dim3(grid), dim3(256), smem, (hipStream_t)stream, a); return OS2S_OK;
+        case 3: OS2S_LAUNCH_LDS(conv1d_wgrad_sw_kernel<3>, dim3(grid), dim3(256), smem, (hipStream_t)stream, a); return OS2S_OK;
+        case 4: OS2S_LAUNCH_LDS(conv1d_wgrad_sw_kernel<4>, dim3(grid), dim3(256), smem, (hipStream_t)stream, a); return OS2S_OK;
+        case 5: OS2S_LAUNCH_LDS(conv1d_wgrad_sw_kernel<5>, dim3(grid), dim3(256), smem, (hipStream_t)stream, a); return OS2S_OK;
+        case 8: OS2S_LAUNCH_LDS(conv1d_wgrad_sw_kernel<8>, dim3(grid), dim3(256), smem, (hipStream_t)stream, a); return OS2S_OK;
         default: break;
       }
 #endif
-      OS2S_LAUNCH(conv1d_wgrad_sw_kernel<0>, dim3(grid), dim3(256), smem, (hipStream_t)stream, a);
+      OS2S_LAUNCH_LDS(conv1d_wgrad_sw_kernel<0>, dim3(grid), dim3(256), smem, (hipStream_t)stream, a);
       return OS2S_OK;
     }
   }
@@ -1317,14 +1306,11 @@ static int conv1d_wgrad_impl_g(os2s_stream_t stream, const uint16_t* x, long lon
     wgrad_tap_quad_geometry(a, 24 * 1024);              // 3 DMA rounds of 8 waves x 1 KB
     const size_t smem = (size_t)2 * 64 * 256 + (size_t)3 * a.xbuf_bytes + a.steptab_bytes + (a.dbg ? 2 * 48 * 10 * 8 : 0);
     if (smem <= 160 * 1024) {
-      static const hipError_t attr_rc = opt_in_lds_160k({(const void*)conv1d_wgrad_pp_kernel<false>,
-                                                         (const void*)conv1d_wgrad_pp_kernel<true>});
-      if (attr_rc != hipSuccess) return OS2S_ERR_LAUNCH;
       const int grid = wgrad_split_grid(a, a.NG * pp_units, workspace, workspace_bytes);
       if (a.dbg) {
-        OS2S_LAUNCH(conv1d_wgrad_pp_kernel<true>, dim3(grid), dim3(512), smem, (hipStream_t)stream, a);
+        OS2S_LAUNCH_LDS(conv1d_wgrad_pp_kernel<true>, dim3(grid), dim3(512), smem, (hipStream_t)stream, a);
       } else {
-        OS2S_LAUNCH(conv1d_wgrad_pp_kernel<false>, dim3(grid), dim3(512), smem, (hipStream_t)stream, a);
+        OS2S_LAUNCH_LDS(conv1d_wgrad_pp_kernel<false>, dim3(grid), dim3(512), smem, (hipStream_t)stream, a);
       }
       return OS2S_OK;
     }
@@ -1385,22 +1371,18 @@ static int conv1d_wgrad_impl_g(os2s_stream_t stream, const uint16_t* x, long lon
   a.xrows_pad = ceil_div(a.xrows, 4) * 4;
   const size_t smem = (size_t)2 * 64 * 2 * COT + (size_t)2 * a.xrows_pad * 256;
   if (smem > 160 * 1024) return OS2S_ERR_UNSUPPORTED;
-  static const hipError_t attr_rc = opt_in_lds_160k({
-      (const void*)conv1d_wgrad_kernel<2, 128>, (const void*)conv1d_wgrad_kernel<2, 256>,
-      (const void*)conv1d_wgrad_kernel<1, 128>, (const void*)conv1d_wgrad_kernel<1, 256>});
-  if (attr_rc != hipSuccess) return OS2S_ERR_LAUNCH;
   const int nunits = a.NCO * a.NCI * a.NSPLIT;
   const int grid = ceil_div(nunits, 8) * 8 * a.NTP;
   if (wide) {
     if (TAPS == 1)
-      OS2S_LAUNCH((conv1d_wgrad_kernel<1, 256>), dim3(grid), dim3(512), smem, (hipStream_t)stream, a);
+      OS2S_LAUNCH_LDS((conv1d_wgrad_kernel<1, 256>), dim3(grid), dim3(512), smem, (hipStream_t)stream, a);
     else
-      OS2S_LAUNCH((conv1d_wgrad_kernel<2, 256>), dim3(grid), dim3(512), smem, (hipStream_t)stream, a);
+      OS2S_LAUNCH_LDS((conv1d_wgrad_kernel<2, 256>), dim3(grid), dim3(512), smem, (hipStream_t)stream, a);
   } else {
     if (TAPS == 1)
-      OS2S_LAUNCH((conv1d_wgrad_kernel<1, 128>), dim3(grid), dim3(256), smem, (hipStream_t)stream, a);
+      OS2S_LAUNCH_LDS((conv1d_wgrad_kernel<1, 128>), dim3(grid), dim3(256), smem, (hipStream_t)stream, a);
     else
-      OS2S_LAUNCH((conv1d_wgrad_kernel<2, 128>), dim3(grid), dim3(256), smem, (hipStream_t)stream, a);
+      OS2S_LAUNCH_LDS((conv1d_wgrad_kernel<2, 128>), dim3(grid), dim3(256), smem, (hipStream_t)stream, a);
   }
   if (a.part) {
     const int blocks = ceil_div(dw_elems, 256) < 2048 ? ceil_div(dw_elems, 256) : 2048;
@@ -1491,9 +1473,7 @@ extern "C" int os2s_conv1x1_wgrad_grouped(os2s_stream_t stream, const os2s_wgrad
   a.use_atomic = 1;
   const WgradGroupTable gt = wgrad_group_table(groups, ngroups, 128, a.NSPLIT);
   const size_t smem = (size_t)2 * 64 * 2 * 128 + (size_t)2 * a.xrows_pad * 256;
-  static const hipError_t attr_rc = opt_in_lds_160k({(const void*)conv1d_wgrad_grouped_kernel});
-  if (attr_rc != hipSuccess) return OS2S_ERR_LAUNCH;
-  OS2S_LAUNCH(conv1d_wgrad_grouped_kernel, dim3(gt.total_units), dim3(256), smem, (hipStream_t)stream, a, gt);
+  OS2S_LAUNCH_LDS(conv1d_wgrad_grouped_kernel, dim3(gt.total_units), dim3(256), smem, (hipStream_t)stream, a, gt);
   return OS2S_OK;
 }
 

@@ -934,43 +934,26 @@ extern "C" int os2s_depthwise_conv1d_fwd(os2s_stream_t stream, const uint16_t* x
     const DmGeom g = dm_geom(K);
     const size_t ldsm = (size_t)kDmCh * g.plane_bytes + (size_t)8 * 2 * g.wt * sizeof(bf16_t);
     if (ldsm <= 160 * 1024) {
-      static bool attrm = false;
-      if (!attrm) {
-        if (hipFuncSetAttribute((const void*)depthwise_mfma_fwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-          return OS2S_ERR_LAUNCH;
-        attrm = true;
-      }
       a.tile0 = g_dw_ablate;
       dim3 gridm(B * ceil_div(Tout, 32 * g.nseg), ceil_div(C, kDmCh));
-      OS2S_LAUNCH(depthwise_mfma_fwd_kernel, gridm, dim3(512), ldsm, (hipStream_t)stream, a);
+      OS2S_LAUNCH_LDS(depthwise_mfma_fwd_kernel, gridm, dim3(512), ldsm, (hipStream_t)stream, a);
       return OS2S_OK;
     }
   }
   if (stride == 1 && (dil == 1 || dil == 2 || dil == 4) && g_dw_variant != 0) {
     const size_t lds16 = (((size_t)(kD16BT + (K - 1) * dil) * kD16Pitch + 15) & ~(size_t)15) + (size_t)K * kDwBC * sizeof(float);
     if (lds16 <= 160 * 1024) {             // <= 80 KB: two workgroups per CU (every dilation-1 QuartzNet layer)
-      static bool attr16 = false;
-      if (!attr16) {
-        if (hipFuncSetAttribute((const void*)depthwise_fwd16_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
-            hipFuncSetAttribute((const void*)depthwise_fwd16_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
-            hipFuncSetAttribute((const void*)depthwise_fwd16_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-          return OS2S_ERR_LAUNCH;
-        attr16 = true;
-      }
       dim3 grid16(B * ceil_div(Tout, kD16BT), ceil_div(C, kDwBC));
-      if (dil == 1) { OS2S_LAUNCH(depthwise_fwd16_kernel<1>, grid16, dim3(256), lds16, (hipStream_t)stream, a); }
-      else if (dil == 2) { OS2S_LAUNCH(depthwise_fwd16_kernel<2>, grid16, dim3(256), lds16, (hipStream_t)stream, a); }
-      else { OS2S_LAUNCH(depthwise_fwd16_kernel<4>, grid16, dim3(256), lds16, (hipStream_t)stream, a); }
+      if (dil == 1) { OS2S_LAUNCH_LDS(depthwise_fwd16_kernel<1>, grid16, dim3(256), lds16, (hipStream_t)stream, a); }
+      else if (dil == 2) { OS2S_LAUNCH_LDS(depthwise_fwd16_kernel<2>, grid16, dim3(256), lds16, (hipStream_t)stream, a); }
+      else { OS2S_LAUNCH_LDS(depthwise_fwd16_kernel<4>, grid16, dim3(256), lds16, (hipStream_t)stream, a); }
       return OS2S_OK;
     }
   }
   const size_t lds = ((size_t)a.R * kDwP + (size_t)K * kDwBC) * sizeof(float);
   if (lds > 160 * 1024) return OS2S_ERR_UNSUPPORTED;
-  if (lds > 64 * 1024 &&
-      hipFuncSetAttribute((const void*)depthwise_fwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-    return OS2S_ERR_LAUNCH;
   dim3 grid(B * ceil_div(Tout, kDwBT), ceil_div(C, kDwBC));
-  OS2S_LAUNCH(depthwise_fwd_kernel, grid, dim3(256), lds, (hipStream_t)stream, a);
+  OS2S_LAUNCH_LDS(depthwise_fwd_kernel, grid, dim3(256), lds, (hipStream_t)stream, a);
   return OS2S_OK;
 }
 
@@ -998,14 +981,8 @@ extern "C" int os2s_depthwise_dgrad_bnact(os2s_stream_t stream, const uint16_t* 
   const DmGeom g = dm_geom(K);
   const size_t ldsm = (size_t)kDmCh * g.plane_bytes + (size_t)8 * 2 * g.wt * sizeof(bf16_t);
   OS2S_REQUIRE(ldsm <= 160 * 1024 && ldsm >= 512 * 16 * sizeof(float));
-  static bool attrm = false;
-  if (!attrm) {
-    if (hipFuncSetAttribute((const void*)depthwise_mfma_fwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-      return OS2S_ERR_LAUNCH;
-    attrm = true;
-  }
   dim3 gridm(B * ceil_div(Tout, 32 * g.nseg), ceil_div(C, kDmCh));
-  OS2S_LAUNCH(depthwise_mfma_fwd_kernel, gridm, dim3(512), ldsm, (hipStream_t)stream, a);
+  OS2S_LAUNCH_LDS(depthwise_mfma_fwd_kernel, gridm, dim3(512), ldsm, (hipStream_t)stream, a);
   return OS2S_OK;
 }
 
@@ -1020,18 +997,12 @@ extern "C" int os2s_depthwise_conv1d_wgrad(os2s_stream_t stream, const uint16_t*
   // matrix-core kernel: stride 1, dilation 1, 2 <= K <= 96 (depthwise.variant 1 = the register-window kernels only)
   if (stride == 1 && dil == 1 && K >= 2 && K <= 96 && g_dw_variant != 0 && g_dw_variant != 1) {
     const size_t ldsw = (size_t)kDwgCh * (kDwgXPlane + kDwgYPlane);
-    static bool attrw = false;
-    if (!attrw) {
-      if (hipFuncSetAttribute((const void*)depthwise_mfma_wgrad_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-        return OS2S_ERR_LAUNCH;
-      attrw = true;
-    }
     const int ntiles = B * ceil_div(Tout, kDwgTt), ngroups = ceil_div(C, kDwgCh);
     // enough workgroups for two per CU; deterministic mode: ONE per channel block (one add per dw element)
     int gx = os2s_deterministic() ? 1 : ceil_div(512, ngroups);
     gx = gx < 1 ? 1 : (gx > ntiles ? ntiles : gx);
     a.tile0 = g_dw_ablate;
-    OS2S_LAUNCH(depthwise_mfma_wgrad_kernel, dim3(gx, ngroups), dim3(512), ldsw, (hipStream_t)stream, a);
+    OS2S_LAUNCH_LDS(depthwise_mfma_wgrad_kernel, dim3(gx, ngroups), dim3(512), ldsw, (hipStream_t)stream, a);
     return OS2S_OK;
   }
   if (stride == 1 && (dil == 1 || dil == 2 || dil == 4) && g_dw_variant != 0) {
@@ -1043,37 +1014,26 @@ extern "C" int os2s_depthwise_conv1d_wgrad(os2s_stream_t stream, const uint16_t*
     const size_t redb = (size_t)(nseg > 0 ? nseg : 1) * ncell * 64 * sizeof(float);
     const size_t lds16 = tiles > redb ? tiles : redb;
     if (nseg >= 1 && lds16 <= 160 * 1024) {
-      static bool attr16 = false;
-      if (!attr16) {
-        if (hipFuncSetAttribute((const void*)depthwise_wgrad16_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
-            hipFuncSetAttribute((const void*)depthwise_wgrad16_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
-            hipFuncSetAttribute((const void*)depthwise_wgrad16_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-          return OS2S_ERR_LAUNCH;
-        attr16 = true;
-      }
       const int ntiles = B * ceil_div(Tout, kD16BT);
       // deterministic mode: ONE workgroup per channel block walks every tile (one add per dw element)
       dim3 grid16(os2s_deterministic() ? 1 : (ntiles < 64 ? ntiles : 64), ceil_div(C, kDwBC));
-      if (dil == 1) { OS2S_LAUNCH(depthwise_wgrad16_kernel<1>, grid16, dim3(256), lds16, (hipStream_t)stream, a, ngrp, nseg); }
-      else if (dil == 2) { OS2S_LAUNCH(depthwise_wgrad16_kernel<2>, grid16, dim3(256), lds16, (hipStream_t)stream, a, ngrp, nseg); }
-      else { OS2S_LAUNCH(depthwise_wgrad16_kernel<4>, grid16, dim3(256), lds16, (hipStream_t)stream, a, ngrp, nseg); }
+      if (dil == 1) { OS2S_LAUNCH_LDS(depthwise_wgrad16_kernel<1>, grid16, dim3(256), lds16, (hipStream_t)stream, a, ngrp, nseg); }
+      else if (dil == 2) { OS2S_LAUNCH_LDS(depthwise_wgrad16_kernel<2>, grid16, dim3(256), lds16, (hipStream_t)stream, a, ngrp, nseg); }
+      else { OS2S_LAUNCH_LDS(depthwise_wgrad16_kernel<4>, grid16, dim3(256), lds16, (hipStream_t)stream, a, ngrp, nseg); }
       return OS2S_OK;
     }
   }
   const size_t lds = ((size_t)a.R + kDwBT) * kDwP * sizeof(float);
   if (lds > 160 * 1024) return OS2S_ERR_UNSUPPORTED;
-  if (lds > 64 * 1024 &&
-      hipFuncSetAttribute((const void*)depthwise_wgrad_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-    return OS2S_ERR_LAUNCH;
   dim3 grid(B * ceil_div(Tout, kDwBT), ceil_div(C, kDwBC));
   if (os2s_deterministic()) {     // one (sample, time tile) per launch: the adds of a dw element arrive in tile order
     const int ntiles = (int)grid.x;
     grid.x = 1;
     for (a.tile0 = 0; a.tile0 < ntiles; ++a.tile0)
-      OS2S_LAUNCH(depthwise_wgrad_kernel, grid, dim3(256), lds, (hipStream_t)stream, a);
+      OS2S_LAUNCH_LDS(depthwise_wgrad_kernel, grid, dim3(256), lds, (hipStream_t)stream, a);
     return OS2S_OK;
   }
-  OS2S_LAUNCH(depthwise_wgrad_kernel, grid, dim3(256), lds, (hipStream_t)stream, a);
+  OS2S_LAUNCH_LDS(depthwise_wgrad_kernel, grid, dim3(256), lds, (hipStream_t)stream, a);
   return OS2S_OK;
 }
 

@@ -566,12 +566,10 @@ int launch_conv1x1_pp(hipStream_t stream, ConvArgs a, ConvGroupTable gt) {
   a.mtiles_per_b = ceil_div(a.Tout, 128);
   a.MT = a.B * a.mtiles_per_b;
   a.R = 128; a.Rpad = 128;
-  static const hipError_t attr_rc = opt_in_lds_160k({(const void*)conv1x1_pp_kernel});
-  if (attr_rc != hipSuccess) return OS2S_ERR_LAUNCH;
   const int pmax = ceil_div(a.MT, 2);
   const int nzero = a.out_len ? 0 : ceil_div(a.MT, kGppZeroWin) * gt.ngroups;
   const size_t smem = (size_t)5 * 256 * 128;            // A ring of 3 + W ring of 2 (> epilogue staging)
-  OS2S_LAUNCH(conv1x1_pp_kernel, dim3(pmax * nt + nzero), dim3(512), smem, stream, a, gt);
+  OS2S_LAUNCH_LDS(conv1x1_pp_kernel, dim3(pmax * nt + nzero), dim3(512), smem, stream, a, gt);
   return OS2S_OK;
 }
 
@@ -620,9 +618,7 @@ static int gemm_nt_impl(os2s_stream_t stream, const uint16_t* A, long long lda, 
   const size_t main_bytes = (size_t)5 * 256 * 128;    // A ring of 3 + W ring of 2 = 160 KB
   const size_t epi_bytes = conv_epilogue_lds_bytes<128, 256, 2, 512>();
   const size_t smem = main_bytes > epi_bytes ? main_bytes : epi_bytes;
-  static const hipError_t attr_rc = opt_in_lds_160k({(const void*)gemm_pp_kernel});
-  if (attr_rc != hipSuccess) return OS2S_ERR_LAUNCH;
-  const int ncu = a.ncu = split_ncu();
+  const int ncu = a.ncu = device_cus();
   // ---- the 160-row tile (gemm_pp_cols_kernel<5>): when the 256-row tiling is ONE round that leaves more than 40 % of
   // the CUs without a tile and 160-row tiles still fit one round; per-window statistics keep the 128-row windows
   {
@@ -631,12 +627,10 @@ static int gemm_nt_impl(os2s_stream_t stream, const uint16_t* A, long long lda, 
     // (not for launches of a few tiles — nothing to gain — and not while a test forces the tail split of the 256-row tile)
     const bool fits = !stats && u160 <= ncu && u256 * 10 <= ncu * 6 && u160 > u256 && u256 >= 32 && g_gemm_split <= 0;
     if (g_gemm_tile == 160 ? (!stats && u160 <= 4 * ncu) : (g_gemm_tile == 0 && fits)) {
-      static const hipError_t rc5 = opt_in_lds_160k({(const void*)gemm_pp_cols_kernel<5>});
-      if (rc5 != hipSuccess) return OS2S_ERR_LAUNCH;
       const size_t main5 = (size_t)3 * 160 * 128 + (size_t)3 * 256 * 128;
       const size_t epi5 = conv_epilogue_lds_bytes<160, 256, 1, 512>();
-      OS2S_LAUNCH(gemm_pp_cols_kernel<5>, dim3(ceil_div(u160, 8) * 8), dim3(512), main5 > epi5 ? main5 : epi5,
-                  (hipStream_t)stream, a, mb160);
+      OS2S_LAUNCH_LDS(gemm_pp_cols_kernel<5>, dim3(ceil_div(u160, 8) * 8), dim3(512), main5 > epi5 ? main5 : epi5,
+                      (hipStream_t)stream, a, mb160);
       return OS2S_OK;
     }
   }
@@ -661,7 +655,7 @@ static int gemm_nt_impl(os2s_stream_t stream, const uint16_t* A, long long lda, 
   }
   const int nfull = f > 1 ? U - r : U;
   const int grid = nfull + (f > 1 ? r * f : 0);
-  OS2S_LAUNCH(gemm_pp_kernel, dim3(grid), dim3(512), smem, (hipStream_t)stream, a, gm, rem > 0 ? rem : 1, nfull, f);
+  OS2S_LAUNCH_LDS(gemm_pp_kernel, dim3(grid), dim3(512), smem, (hipStream_t)stream, a, gm, rem > 0 ? rem : 1, nfull, f);
   return OS2S_OK;
 }
 

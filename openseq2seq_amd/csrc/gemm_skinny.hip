@@ -224,41 +224,20 @@ extern "C" int os2s_gemm_skinny(os2s_stream_t stream, const uint16_t* x, long lo
   if (force) variant = force[0] == 'r' ? 0 : (force[0] == 'w' ? 3 : (force[1] == '6' ? 2 : 1));
   if (variant == 3) {     // wide: 128 (n) x 256 (m) per workgroup, no K-split — least L2 traffic
     using C = LdsCfg<4, 8, 64, 4, 1>;
-    static bool attr_set = false;
-    if (!attr_set) {
-      if (hipFuncSetAttribute((const void*)gemm_skinny_lds_kernel<4, 8, 64, 4, 1>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, C::kSmem) != hipSuccess)
-        return OS2S_ERR_LAUNCH;
-      attr_set = true;
-    }
-    OS2S_LAUNCH((gemm_skinny_lds_kernel<4, 8, 64, 4, 1>), dim3((N + 127) / 128, (M + 255) / 256),
-                dim3(512), C::kSmem, (hipStream_t)stream, a);
+    OS2S_LAUNCH_LDS((gemm_skinny_lds_kernel<4, 8, 64, 4, 1>), dim3((N + 127) / 128, (M + 255) / 256),
+                    dim3(512), C::kSmem, (hipStream_t)stream, a);
     return OS2S_OK;
   }
   if (variant == 2) {
     using C = LdsCfg<2, 2, 256>;
-    static bool attr_set = false;
-    if (!attr_set) {
-      if (hipFuncSetAttribute((const void*)gemm_skinny_lds_kernel<2, 2, 256>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, C::kSmem) != hipSuccess)
-        return OS2S_ERR_LAUNCH;
-      attr_set = true;
-    }
-    OS2S_LAUNCH((gemm_skinny_lds_kernel<2, 2, 256>), dim3((N + 63) / 64, (M + 63) / 64), dim3(512),
-                C::kSmem, (hipStream_t)stream, a);
+    OS2S_LAUNCH_LDS((gemm_skinny_lds_kernel<2, 2, 256>), dim3((N + 63) / 64, (M + 63) / 64), dim3(512),
+                    C::kSmem, (hipStream_t)stream, a);
     return OS2S_OK;
   }
   if (variant == 1) {
     using C = LdsCfg<1, 1, 512>;
-    static bool attr_set = false;
-    if (!attr_set) {
-      if (hipFuncSetAttribute((const void*)gemm_skinny_lds_kernel<1, 1, 512>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, C::kSmem) != hipSuccess)
-        return OS2S_ERR_LAUNCH;
-      attr_set = true;
-    }
-    OS2S_LAUNCH((gemm_skinny_lds_kernel<1, 1, 512>), dim3((N + 31) / 32, (M + 31) / 32), dim3(512),
-                C::kSmem, (hipStream_t)stream, a);
+    OS2S_LAUNCH_LDS((gemm_skinny_lds_kernel<1, 1, 512>), dim3((N + 31) / 32, (M + 31) / 32), dim3(512),
+                    C::kSmem, (hipStream_t)stream, a);
     return OS2S_OK;
   }
   OS2S_LAUNCH(gemm_skinny_kernel, dim3((N + 31) / 32, (M + 31) / 32), dim3(64 * kSkWaves), 0,

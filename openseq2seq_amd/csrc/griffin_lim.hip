@@ -276,11 +276,6 @@ extern "C" int os2s_griffin_lim(os2s_stream_t stream_, const float* mag, const i
   const int lds_row = analysis_lds_row(hop);
   const size_t lds = (size_t)(kFrameTile + 3) * lds_row * sizeof(float);
   OS2S_REQUIRE(lds <= 160 * 1024);
-  if (lds > 64 * 1024) {
-    (void)hipGetLastError();
-    if (hipFuncSetAttribute((const void*)gl_analysis_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-      return OS2S_ERR_LAUNCH;
-  }
   const int ft = os2s::ceil_div(T_max, kFrameTile);
   // synthesis geometry: kept hop blocks 2 .. T_max
   const int wtiles = os2s::ceil_div(T_max - 1, kFrameTile) * (hopP / 32);
@@ -291,8 +286,8 @@ extern "C" int os2s_griffin_lim(os2s_stream_t stream_, const float* mag, const i
     float* dst = ((n_iters - i) & 1) ? sig2 : out;
     float* src = ((n_iters - i) & 1) ? out : sig2;
     if (i > 0)
-      OS2S_LAUNCH(gl_analysis_kernel, dim3(ft, groups, B), dim3(64 * waves), lds, stream, (const float*)src, sig_stride,
-                  lengths, basis_analysis, (const float*)Mt, Yt, T_max, n_fft, K, Kp, lds_row);
+      OS2S_LAUNCH_LDS(gl_analysis_kernel, dim3(ft, groups, B), dim3(64 * waves), lds, stream, (const float*)src, sig_stride,
+                      lengths, basis_analysis, (const float*)Mt, Yt, T_max, n_fft, K, Kp, lds_row);
     OS2S_LAUNCH(gl_synthesis_kernel, sgrid, dim3(256), 0, stream, (const float*)Yt, lengths, basis_synthesis, inv_wss,
                 dst, sig_stride, T_max, n_fft, Kp, hopP, i == 0 ? flags : (int32_t*)nullptr);
   }

@@ -18,7 +18,6 @@
 //   3. per-utterance, per-feature mean / std (two-pass, fp64 accumulators) +
 //      normalise + bf16 store into the zero-padded [B, Tpad, F] batch.
 #include "speech_frontend.hpp"
-#include <mutex>
 
 namespace os2s {
 
@@ -391,13 +390,8 @@ extern "C" int os2s_logmel(os2s_stream_t stream_, const void* signal, const int3
     if (rc != OS2S_OK) return rc;
   }
   const size_t smem = (size_t)(4 * (2 * 576 + 2 * 260) + kFB * hop + 768) * 4;
-  static std::once_flag once;
-  static hipError_t attr_rc = hipSuccess;
-  std::call_once(once, [] {
-    attr_rc = hipFuncSetAttribute((const void*)logmel_frames_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  });
-  if (attr_rc != hipSuccess || smem > 160 * 1024) return OS2S_ERR_LAUNCH;
-  OS2S_LAUNCH(logmel_frames_kernel, dim3(units), dim3(256), smem, stream, a);
+  if (smem > 160 * 1024) return OS2S_ERR_LAUNCH;
+  OS2S_LAUNCH_LDS(logmel_frames_kernel, dim3(units), dim3(256), smem, stream, a);
   OS2S_LAUNCH(logmel_stats_kernel, dim3(B), dim3(64), 0, stream, partial, n_samples, Nmax, hop, Tmax, nblk, n_mels,
               norm_per_feature, stats);
   OS2S_LAUNCH(logmel_normalize_kernel, dim3(units), dim3(256), 0, stream, raw, stats, n_samples, Nmax, hop,

@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <atomic>
+
 #include "../../include/os2s.h"
 
 // hipGetLastError() is sticky per thread and also reports benign errors left
@@ -20,6 +22,29 @@
   } while (0)
 
 extern "C" void os2s_record_hip_error(int hip_error, const char* where);
+
+// THE launch form of a kernel whose dynamic LDS can reach the default limit of 64 KB: OS2S_LAUNCH, after making
+// sure that this kernel has been opted in (up to the 160 KB of a gfx950 CU) on the CURRENT device; the attribute
+// belongs to a (function, device) pair. One flag word per expansion site, and so per template instance, one bit
+// per device: a launch of 64 KB or more costs hipGetDevice and an atomic load. A failure is recorded and returned,
+// never latched: the next call tries again. Two host threads may both set the attribute; that is harmless, and
+// so is the opt-in of a launch exactly at the limit. Launches below 64 KB go straight through, so a site may use
+// this form whatever its size.
+// OS2S_LAUNCH_LDS_MAX names the limit to opt in to, for a kernel whose static LDS leaves less than 160 KB.
+#define OS2S_LAUNCH_LDS_MAX(lds_max, kernel, grid, block, smem, stream, ...)                \
+  do {                                                                                      \
+    if ((size_t)(smem) >= os2s::kLdsDefault) {                                              \
+      static std::atomic<uint32_t> opted__{0};                                              \
+      const hipError_t a__ = os2s::lds_opt_in(opted__, (const void*)kernel, (int)(lds_max)); \
+      if (a__ != hipSuccess) {                                                              \
+        os2s_record_hip_error((int)a__, #kernel);                                           \
+        return OS2S_ERR_LAUNCH;                                                             \
+      }                                                                                     \
+    }                                                                                       \
+    OS2S_LAUNCH(kernel, grid, block, smem, stream, __VA_ARGS__);                            \
+  } while (0)
+#define OS2S_LAUNCH_LDS(kernel, grid, block, smem, stream, ...) \
+  OS2S_LAUNCH_LDS_MAX(os2s::kLdsMax, kernel, grid, block, smem, stream, __VA_ARGS__)
 
 #define OS2S_REQUIRE(cond) \
   do {                     \
@@ -39,6 +64,31 @@ typedef void (*StampSetter)(void* stamps, int mode);
 struct StampReg { StampReg(const char* name, StampSetter fn); };
 
 constexpr int kWave = 64;
+
+// ---- per-device host state (device indices 0 .. 31 are cached; beyond that the runtime is asked every time) ----
+constexpr size_t kLdsDefault = 64 * 1024;   // LDS a kernel may use without an opt-in (static + dynamic)
+constexpr int kLdsMax = 160 * 1024;         // LDS of a gfx950 CU
+
+// Behind OS2S_LAUNCH_LDS: `opted` has bit d set once `fn` may use `lds_max` bytes of dynamic LDS on device d.
+inline hipError_t lds_opt_in(std::atomic<uint32_t>& opted, const void* fn, int lds_max) {
+  int dev = -1;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 32) dev = -1;
+  if (dev >= 0 && ((opted.load(std::memory_order_acquire) >> dev) & 1u)) return hipSuccess;
+  const hipError_t rc = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max);
+  if (rc == hipSuccess && dev >= 0) opted.fetch_or(1u << dev, std::memory_order_release);
+  return rc;
+}
+
+// CUs of the current device; `unknown` (256: an MI355X) when the runtime cannot be asked.
+inline int device_cus(int unknown = 256) {
+  static std::atomic<int> cus[32];   // zero-initialised: 0 = not asked yet
+  int dev = -1, n = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0) return unknown;
+  if (dev < 32 && (n = cus[dev].load(std::memory_order_relaxed)) > 0) return n;
+  if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) return unknown;
+  if (dev < 32) cus[dev].store(n, std::memory_order_relaxed);
+  return n;
+}
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;

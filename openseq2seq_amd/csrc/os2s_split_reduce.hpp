@@ -14,11 +14,10 @@
 //     assumed about which workgroups are co-resident.
 // The ticket is reset to zero by the reducer: the workspace's ticket area is zero before and
 // after every launch.
-// The host side of such a launch is at the end of this file: the CU count, the workspace carve (tickets, slabs),
-// the pieces a grid adds for its tail and the 160 KB LDS opt-in, shared by every launcher of these kernels.
+// The host side of such a launch is at the end of this file: the workspace carve (tickets, slabs) and the pieces a
+// grid adds for its tail, shared by every launcher of these kernels. The CU count is device_cus() and the launch
+// itself OS2S_LAUNCH_LDS (os2s_common.hpp), which opts the kernel into its LDS on the current device.
 #pragma once
-#include <initializer_list>
-
 #include "os2s_common.hpp"
 
 namespace os2s {
@@ -157,17 +156,6 @@ __host__ __device__ __forceinline__ int split_factor(int r, int G, float round_u
 
 // ---- host side of a launch with split units -----------------------------------------------------------------------
 
-// CUs of the device that was current at the first launch (256 when it cannot be asked); one latch per process.
-inline int split_ncu() {
-  static const int ncu = [] {
-    int dev = 0, n = 0;
-    const bool ok = hipGetDevice(&dev) == hipSuccess &&
-                    hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0;
-    return ok ? n : 256;
-  }();
-  return ncu;
-}
-
 // The caller's workspace as the kernels see it: [kSplitTicketBytes of int32 tickets][nslabs partial tiles], at most
 // 3 per CU. All null / 0 (the launch then splits nothing) without a workspace or with room for fewer than two slabs.
 struct SplitWorkspace {
@@ -188,16 +176,6 @@ inline SplitWorkspace split_carve(void* workspace, size_t workspace_bytes, int n
 inline int split_tail_pieces(int units, int ncu, int nslabs) {
   const int r = units % ncu;
   return nslabs < 16 * r ? nslabs : 16 * r;
-}
-
-// Opts the kernels into 160 KB of dynamic LDS; the first error, or hipSuccess. Once per call site:
-//   static const hipError_t attr_rc = opt_in_lds_160k({(const void*)kernel, ...});
-inline hipError_t opt_in_lds_160k(std::initializer_list<const void*> kernels) {
-  for (const void* k : kernels) {
-    const hipError_t rc = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (rc != hipSuccess) return rc;
-  }
-  return hipSuccess;
 }
 
 }  // namespace os2s

@@ -574,6 +574,13 @@ extern "C" size_t os2s_gru_xcd_workspace_bytes(int B, int H) {
   return (size_t)2 * 32 * gpc * 16 + 256;
 }
 
+// The persistent kernels carry 256 B of static LDS next to their dynamic LDS, so the opt-in leaves room for it. No
+// __shared__ declaration in this file makes them: the number is what the compiler writes into the code object
+// (.group_segment_fixed_size of gru_xcd_bwd_kernel and of the four gru_xcd_fwd_kernel instances) and has to be
+// read again there after a compiler change. The largest dynamic size the two *_supported() functions admit,
+// 163 466 B, must stay at or below this value, or the largest shapes fail at launch.
+constexpr int kXcdLdsOptIn = kLdsMax - 256;
+
 static size_t gru_xcd_lds_bytes(int B, int H) {
   const int BP = B <= 16 ? 16 : 32, upc = (H + kXcdCus - 1) / kXcdCus, NK = (H + 31) / 32;
   const int RT = 3 * upc <= 80 ? 5 : 6;
@@ -587,11 +594,7 @@ bool gru_xcd_supported(int B, int T, int H, int ndir) {
   const int BP = B <= 16 ? 16 : 32, upc = (H + kXcdCus - 1) / kXcdCus;
   if (3 * upc > kXcdRTMax * 16 || T > 65000 || kXcdCus * ((upc * BP + 6) / 7) >= 65536) return false;
   if (gru_xcd_lds_bytes(B, H) > 160 * 1024) return false;   // (B = 32 with H = 1024: the partial sums do not fit)
-  int dev = 0, n = 0;
-  if (hipGetDevice(&dev) != hipSuccess ||
-      hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n != 256)
-    return false;                                        // 8 XCDs x 32 CUs: the placement the kernel checks
-  return true;
+  return device_cus(0) == 256;                           // 8 XCDs x 32 CUs: the placement the kernel checks
 }
 
 // ---- sticky abort word -------------------------------------------------------------------------------
@@ -676,15 +679,11 @@ int launch_gru_xcd_fwd(hipStream_t stream, int ndir, const os2s_rnn_dir_fwd_t* d
   const int RT = 3 * upc <= 80 ? 5 : 6;
   const size_t lds = gru_xcd_lds_bytes(B, H);
   if (lds > 160 * 1024) return OS2S_ERR_UNSUPPORTED;
-  const void* fn = BP == 16 ? (RT == 5 ? (const void*)gru_xcd_fwd_kernel<1, 5> : (const void*)gru_xcd_fwd_kernel<1, 6>)
-                            : (RT == 5 ? (const void*)gru_xcd_fwd_kernel<2, 5> : (const void*)gru_xcd_fwd_kernel<2, 6>);
-  if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-    return OS2S_ERR_LAUNCH;
   const dim3 grid(8 * kXcdCus), blk(kXcdThreads);
-  if (BP == 16 && RT == 5) { OS2S_LAUNCH((gru_xcd_fwd_kernel<1, 5>), grid, blk, lds, stream, a); }
-  else if (BP == 16) { OS2S_LAUNCH((gru_xcd_fwd_kernel<1, 6>), grid, blk, lds, stream, a); }
-  else if (RT == 5) { OS2S_LAUNCH((gru_xcd_fwd_kernel<2, 5>), grid, blk, lds, stream, a); }
-  else { OS2S_LAUNCH((gru_xcd_fwd_kernel<2, 6>), grid, blk, lds, stream, a); }
+  if (BP == 16 && RT == 5) { OS2S_LAUNCH_LDS_MAX(kXcdLdsOptIn, (gru_xcd_fwd_kernel<1, 5>), grid, blk, lds, stream, a); }
+  else if (BP == 16) { OS2S_LAUNCH_LDS_MAX(kXcdLdsOptIn, (gru_xcd_fwd_kernel<1, 6>), grid, blk, lds, stream, a); }
+  else if (RT == 5) { OS2S_LAUNCH_LDS_MAX(kXcdLdsOptIn, (gru_xcd_fwd_kernel<2, 5>), grid, blk, lds, stream, a); }
+  else { OS2S_LAUNCH_LDS_MAX(kXcdLdsOptIn, (gru_xcd_fwd_kernel<2, 6>), grid, blk, lds, stream, a); }
   if (int rc = gru_xcd_latch(stream, flags)) return rc;
 #ifdef OS2S_GRU_XCD_TIMERS
   {
@@ -735,8 +734,6 @@ int launch_gru_xcd_bwd(hipStream_t stream, int ndir, const os2s_rnn_dir_bwd_t* d
   if (ndir == 1) a.d[1] = a.d[0];
   if (hipMemsetAsync(flags, 0, 64, stream) != hipSuccess) return OS2S_ERR_LAUNCH;
   const size_t lds = gru_xcd_bwd_lds_bytes(H);
-  if (hipFuncSetAttribute((const void*)gru_xcd_bwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-    return OS2S_ERR_LAUNCH;
-  OS2S_LAUNCH(gru_xcd_bwd_kernel, dim3(8 * kXcdCus), dim3(kXcdThreads), lds, stream, a);
+  OS2S_LAUNCH_LDS_MAX(kXcdLdsOptIn, gru_xcd_bwd_kernel, dim3(8 * kXcdCus), dim3(kXcdThreads), lds, stream, a);
   return gru_xcd_latch(stream, flags);
 }
