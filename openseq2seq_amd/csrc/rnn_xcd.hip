@@ -147,6 +147,9 @@ __global__ __launch_bounds__(kXcdThreads) void gru_xcd_fwd_kernel(GruXcdArgs a) 
     hst[b + BP * u] = (u < nu && b < B) ? p.h32[(long long)b * H + u0 + u] : 0.f;
   }
   for (int i = tid; i < gpc * 7 + 1; i += kXcdThreads) hpub[i] = 0;
+  // the whole h image: step 0 multiplies all NK * 32 columns of all BP rows, and the zero weight fragments
+  // of the columns past H do not silence a NaN / Inf the previous kernel left in LDS (HS % 16 == 0)
+  for (int i = tid; i < BP * HS / 16; i += kXcdThreads) reinterpret_cast<u32x4*>(h_l)[i] = u32x4{0u, 0u, 0u, 0u};
   const unsigned gpc_inv = (unsigned)((0x100000000ull + gpc - 1) / gpc);   // gi / gpc = umulhi(gi, gpc_inv), gi < 2^16
   __syncthreads();
   // h_{-1}: every workgroup reads the whole initial state (plain loads: nobody has written it)
