@@ -522,7 +522,9 @@ __global__ __launch_bounds__(256) void bn_act_bwd_reduce_kernel(BnBwdReduceArgs 
             const float th = ov[e] * p.keep_prob;  // tanh(z) of a kept element
             dact = 1.f - th * th;
           }
-          dzv[e] = dv[e] * gsc * dact;
+          // a select, not the bare product: dout < 0 times a zero factor is -0, and dz is +0 wherever no
+          // gradient passes (dropped elements, act' = 0), as it is in the rows past out_len[b]
+          dzv[e] = (gsc != 0.f && dact != 0.f) ? dv[e] * gsc * dact : 0.f;
         }
         // rows at or past out_len[b] read as zeros above, so dz is zero there
         const u32x4 w = pack8(dzv);
