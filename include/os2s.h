@@ -44,7 +44,8 @@ int os2s_abi_version(void);
 const char* os2s_strerror(int code);
 /* Detail of the last failed kernel launch on this thread (HIP error string). */
 const char* os2s_last_error_detail(void);
-/* Deterministic mode (default: environment OS2S_DETERMINISTIC, else off): a debugging aid. The kernels that
+/* Deterministic mode (the option "deterministic"; default off, or OS2S_DETERMINISTIC as it was when the library
+ * was loaded): a debugging aid. The kernels that
  * accumulate parameter gradients with fp32 atomics from several workgroups (narrow / K = 1 / stride-2 conv
  * and depthwise weight gradients, the embedding gradient, the style-token attention gradient) are
  * launched in a single-contributor geometry instead: slower, bit-identical run to run. */
@@ -163,8 +164,12 @@ int os2s_conv1d_fwd_ws(os2s_stream_t stream, const uint16_t* x, const uint16_t* 
  * state, like the variant hook: set it around the launches of one batch (the encoder does). Returns OS2S_OK. */
 int os2s_conv1d_set_host_lens(const int32_t* lens, int B);
 /* Named test / measurement options — the ONE entry point for every tuning knob and forced-variant switch of
- * the library (nothing in the library reads the environment for them; values are process-wide and only
- * select among launch geometries that are all exact for any data):
+ * the library (values are process-wide and only select among launch geometries that are all exact for any
+ * data). A name followed by [OS2S_...] takes its initial value from that environment variable, read ONCE, when
+ * the library is loaded (atoi of the text unless stated); the library reads the environment nowhere else, and a
+ * later change of the variable has no effect. Options are changed BETWEEN passes: a forward and its backward, and
+ * a size query and the call it sizes, have to see the same values.
+ *   deterministic [OS2S_DETERMINISTIC]: != 0 = deterministic mode (os2s_set_deterministic above), default 0
  *   conv1d.variant: force a convolution tile. -1 (default) = by shape; 0 = 128x128 tile, X window
  *     double-buffered; 3 = 128x128, X window single-buffered when K >= 8 (3 workgroups per CU); 5 = 256x256
  *     lockstep tile; 10 = ping-pong kernels (balanced over live windows), tile chosen on the device from the
@@ -177,7 +182,8 @@ int os2s_conv1d_set_host_lens(const int32_t* lens, int B);
  *   conv1d.pp_dgrad_penalty: factor on the narrow tiles' cost in data-gradient launches (out_len given:
  *     they share the chip with the weight-gradient stream)
  *   conv1d.pp_prio: 1 = the loading wave of a narrow-tile slot runs at s_setprio 2
- *   conv1d.pp_min_cout: narrowest layer (output channels) the ping-pong kernels take (default 320)
+ *   conv1d.pp_min_cout [OS2S_PP_MIN_COUT]: narrowest layer (output channels) the ping-pong kernels take
+ *     (default 320)
  *   conv1x1.variant: the 1x1 launches (os2s_conv1x1_fwd_grouped and K = 1 layers): 0 and 1 = lockstep 128x128
  *     tile; 2 = 256x256 ping-pong tile over the live windows whenever its envelope allows (Cin % 64 == 0,
  *     B <= 64); -1 (default) = the ping-pong tile for a single K = 1 layer of >= conv1d.pp_min_cout output
@@ -195,6 +201,25 @@ int os2s_conv1d_set_host_lens(const int32_t* lens, int B);
  *   conv1d_wgrad.sw_ablate: read only by measurement builds (-DOS2S_SW_ABLATE, tools/sw_ablate.py): the one-wave
  *     stream with an ingredient removed (1 LDS-DMA, 2 barrier, 4 transpose reads, 8 MFMAs; results are wrong then)
  *   conv1d_wgrad.split: > 0 forces the reduction split factor of the ping-pong kernels (-1 = cost model)
+ *   conv1d_wgrad.pp_min_units [OS2S_WGRAD_PP_MIN_UNITS]: fewest (128 output x 128 input channel x 4 tap)
+ *     units of a weight gradient the ping-pong kernel takes by shape (default 8)
+ *   conv1d_wgrad.k1_pp [OS2S_WGRAD1X1_PP]: the K = 1 ping-pong weight-gradient tile: 0 = never, 1 = whenever the
+ *     shape allows, -1 (default) = by shape
+ *   gemm_skinny.variant [OS2S_SKINNY_VARIANT, text "reg" | "l32" | "l64" | "wide"]: os2s_gemm_skinny's kernel:
+ *     0 = reg (register-direct), 1 = l32 (32x32 tiles), 2 = l64 (64x64), 3 = wide (128x256), -1 (default) = by shape
+ *   ctc_loss.wave [OS2S_CTC_WAVE]: 0 = the 256-thread alpha / beta kernel always; != 0 (default 1) = one wave per
+ *     (sample, direction) where the extended label fits (2 Lmax + 1 <= 1024 and V <= 32)
+ *   gru_xcd.fwd [OS2S_GRU_XCD], gru_xcd.bwd [OS2S_GRU_XCD_BWD]: 0 = per-step launches instead of the persistent
+ *     GRU forward / backward kernel (default 1, 1); os2s_gru_xcd_set_mode >= 0 overrides gru_xcd.fwd
+ *   attn_decoder.attn_split [OS2S_ATTN_SPLIT]: 0 = the one-workgroup-per-sample location-attention kernels
+ *   attn_decoder.cell_split [OS2S_CELL_SPLIT]: 0 = the one-workgroup-per-8-units cell backward
+ *   attn_decoder.fast [OS2S_AD_FAST]: 0 = the training pass does not use the small-code cell / score kernels of
+ *     the Tacotron inference loop (defaults 1, 1, 1)
+ *   tacotron_infer.rows [OS2S_TI_ROWS]: gate rows per workgroup of the inference cell kernel, 16 (default) or 32
+ *   tacotron_infer.geom [OS2S_TI_GEOM, text "<waves>x<slots>"]: 100 * waves + chunk slots per wave of the 16-row
+ *     cell kernel (804, 904, 1203, 1103, 1603, 1602, else 8 x 5); 0 (default) = by K
+ *   tacotron_infer.ctx_parts [OS2S_TI_CTX_PARTS]: > 0 = parts the context columns are cut into (default 0 = by B)
+ *   tacotron_infer.debug [OS2S_TI_DEBUG]: debug word handed to the frame-tail kernel (default 0)
  *   gemm_nt.split: f > 0 forces the tail split factor of os2s_gemm_nt*, 0 disables the split, < 0 = cost model
  *   gemm_nt.tile: 0 (default) = by shape, 256 = always the 256 x 256 tile, 160 = the 160-row x 256-column tile
  *     (eight waves over the columns; bit-identical results) whenever it is legal (no per-window statistics)
@@ -207,8 +232,11 @@ int os2s_conv1d_set_host_lens(const int32_t* lens, int B);
  *     per workgroup 8 .. 1024; tools/bench_bn_sweep.py); the reduce tiling also sets what
  *     os2s_bn_act_bwd_num_parts returns
  * Returns 0, or -1 for an unknown name. os2s_option_name(i) enumerates the registered names (NULL past the
- * last one). */
+ * last one). os2s_get_option stores in *value what the launch path reads for `name` right now, whether it came
+ * from the default, the environment at load time, os2s_set_option or an entry point such as
+ * os2s_set_deterministic; returns 0, or -1 for an unknown name or a NULL pointer. */
 int os2s_set_option(const char* name, double value);
+int os2s_get_option(const char* name, double* value);
 const char* os2s_option_name(int index);
 /* Profiling aid (tools/pp_timeline.py, ppn_timeline.py, conv1x1_phases.py): a device buffer the instrumented
  * kernel `kernel` ("conv1d", "conv1d_wgrad") writes per-slot time stamps into (NULL withdraws it); `mode` is
@@ -864,7 +892,8 @@ size_t os2s_rnn_fwd_workspace_bytes(int B, int H);
  * launch (csrc/rnn_xcd.hip: a direction per XCD, weights stationary in registers, the hidden state
  * exchanged through that XCD's L2) instead of one launch per time step; os2s_rnn_fwd_workspace_bytes
  * includes its exchange buffers. os2s_gru_xcd_set_mode: 0 = per-step launches, 1 = persistent kernel,
- * -1 = environment OS2S_GRU_XCD (default on), 2 (test hook) = on, and the next forward launch starts with
+ * -1 = what the option gru_xcd.fwd says (default on; OS2S_GRU_XCD when the library was loaded), 2 (test hook) =
+ * on, and the next forward launch starts with
  * its abort flag set. A launch that gives up (unexpected workgroup placement, a wait that times out) leaves
  * its outputs partially written: its abort code is latched, behind every persistent forward AND backward
  * launch, into a sticky host-visible word no launch clears; os2s_gru_xcd_status() returns it (1 = timeout,

@@ -153,6 +153,14 @@ def set_option(name, value):
     raise Os2sError("os2s_set_option: unknown option %r" % (name,))
 
 
+def get_option(name):
+  """os2s_get_option: the value the launch path reads for a named option."""
+  v = ctypes.c_double()
+  if C.os2s_get_option(name.encode(), ctypes.byref(v)) != 0:
+    raise Os2sError("os2s_get_option: unknown option %r" % (name,))
+  return v.value
+
+
 def option_names():
   out, i = [], 0
   while True:

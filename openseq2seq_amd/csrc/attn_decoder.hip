@@ -24,7 +24,6 @@
 //                   tanh terms; accumulates dkeys, per-sample parameter partials), cell
 //                   backward (two fused transposed GEMMs + gate derivatives).
 #include <algorithm>
-#include <cstdlib>
 #include "attn_decoder_common.hpp"
 #include "rnn_tile.hpp"
 
@@ -1981,10 +1980,15 @@ static size_t attn_lds_bytes(const os2s_attn_decoder_t* d, bool bwd) {
   return attn_lds_floats(d->H, d->M, d->U, d->S, d->score_mode, d->loc_k, bwd) * sizeof(float);
 }
 
-// the split location-attention kernels (OS2S_ATTN_SPLIT=0: the one-workgroup-per-sample kernels)
+// A/B switches: attn_decoder.attn_split = 0: the one-workgroup-per-sample attention kernels; attn_decoder.cell_split
+// = 0: the one-workgroup-per-8-units cell backward. No workspace size depends on either.
+static int g_attn_split = 1, g_cell_split = 1;
+static os2s::OptionReg r_attn_split("attn_decoder.attn_split", &g_attn_split, "OS2S_ATTN_SPLIT");
+static os2s::OptionReg r_cell_split("attn_decoder.cell_split", &g_cell_split, "OS2S_CELL_SPLIT");
+
+// the split location-attention kernels apply
 bool os2s::loc_split(const os2s_attn_decoder_t* d) {
-  static const int mode = [] { const char* e = getenv("OS2S_ATTN_SPLIT"); return e ? atoi(e) : 1; }();
-  return mode != 0 && d->score_mode == 2 && d->U == kLocParts * kLocUnits && d->M % 8 == 0 &&
+  return g_attn_split != 0 && d->score_mode == 2 && d->U == kLocParts * kLocUnits && d->M % 8 == 0 &&
          loc_fwd_lds_floats(d->H, d->S) * sizeof(float) <= 64 * 1024 &&
          loc_bwd_lds_floats(d->S, d->loc_k) * sizeof(float) <= 160 * 1024;
 }
@@ -2112,15 +2116,7 @@ extern "C" size_t os2s_attn_decoder_bwd_workspace_bytes(const os2s_attn_decoder_
   return n * sizeof(float) + 1024;
 }
 
-// OS2S_CELL_SPLIT=0: the one-workgroup-per-8-units cell backward (A/B switch)
-static bool cell_split(const os2s_attn_decoder_t* d) {
-  static int mode = -1;
-  if (mode < 0) {
-    const char* e = getenv("OS2S_CELL_SPLIT");
-    mode = e ? (atoi(e) != 0) : 1;
-  }
-  return mode == 1 && d->U <= 16 * kCbWaves && d->H % 8 == 0;
-}
+static bool cell_split(const os2s_attn_decoder_t* d) { return g_cell_split != 0 && d->U <= 16 * kCbWaves && d->H % 8 == 0; }
 
 extern "C" int os2s_attn_decoder_bwd(os2s_stream_t stream_, const os2s_attn_decoder_t* d,
                                      const os2s_attn_decoder_grads_t* gr, void* workspace,

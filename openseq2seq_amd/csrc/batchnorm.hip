@@ -859,12 +859,12 @@ extern "C" int os2s_bn_act_fwd(os2s_stream_t stream, int J, const uint16_t* cons
 // os2s_bn_act_bwd_num_parts returns.
 static void bn_set_groups(int which, double v) { if (v >= 8 && v <= 256) g_tiling[which][0] = (int)v; }
 static void bn_set_rows(int which, double v) { if (v >= 8 && v <= kMaxTileRows) g_tiling[which][1] = (int)v; }
-static os2s::OptionReg r_bn0g("bn.act_fwd.groups", [](double v) { bn_set_groups(0, v); });
-static os2s::OptionReg r_bn0r("bn.act_fwd.rows", [](double v) { bn_set_rows(0, v); });
-static os2s::OptionReg r_bn1g("bn.act_bwd_reduce.groups", [](double v) { bn_set_groups(1, v); });
-static os2s::OptionReg r_bn1r("bn.act_bwd_reduce.rows", [](double v) { bn_set_rows(1, v); });
-static os2s::OptionReg r_bn2g("bn.bwd_apply.groups", [](double v) { bn_set_groups(2, v); });
-static os2s::OptionReg r_bn2r("bn.bwd_apply.rows", [](double v) { bn_set_rows(2, v); });
+static os2s::OptionReg r_bn0g("bn.act_fwd.groups", [](double v) { bn_set_groups(0, v); }, [] { return (double)g_tiling[0][0]; });
+static os2s::OptionReg r_bn0r("bn.act_fwd.rows", [](double v) { bn_set_rows(0, v); }, [] { return (double)g_tiling[0][1]; });
+static os2s::OptionReg r_bn1g("bn.act_bwd_reduce.groups", [](double v) { bn_set_groups(1, v); }, [] { return (double)g_tiling[1][0]; });
+static os2s::OptionReg r_bn1r("bn.act_bwd_reduce.rows", [](double v) { bn_set_rows(1, v); }, [] { return (double)g_tiling[1][1]; });
+static os2s::OptionReg r_bn2g("bn.bwd_apply.groups", [](double v) { bn_set_groups(2, v); }, [] { return (double)g_tiling[2][0]; });
+static os2s::OptionReg r_bn2r("bn.bwd_apply.rows", [](double v) { bn_set_rows(2, v); }, [] { return (double)g_tiling[2][1]; });
 
 extern "C" int os2s_bn_act_bwd_num_parts(long long rows) {
   return ceil_div(rows, g_tiling[1][1]);

@@ -1163,16 +1163,7 @@ static int launch_conv_pp(hipStream_t stream, ConvArgs& a, void* workspace, size
 //   0 = 128x128, X window double-buffered   3 = 128x128, X window single-buffered when K >= 8
 //   5 = 256x256 lockstep                   10 = ping-pong (tile chosen on the device)
 //   12 / 13 = ping-pong, 2 / 3 windows x 128 columns   14 = ping-pong, 2 windows x 256 columns
-// narrowest layer the ping-pong kernels take (conv1d.pp_min_cout; the environment variable OS2S_PP_MIN_COUT is
-// read ONCE, at the first launch — no per-launch environment or map lookups in the launch path)
-static int g_pp_min_cout = -1;
-static int pp_min_cout() {
-  if (g_pp_min_cout < 0) {
-    const char* v = getenv("OS2S_PP_MIN_COUT");
-    g_pp_min_cout = v ? atoi(v) : 320;
-  }
-  return g_pp_min_cout;
-}
+static int g_pp_min_cout = 320;   // conv1d.pp_min_cout: narrowest layer the ping-pong kernels take
 static int g_conv_variant = -1;
 static int g_conv_split = -1;
 static unsigned long long* g_conv_dbg = nullptr;
@@ -1187,26 +1178,16 @@ extern "C" int os2s_conv1d_set_host_lens(const int32_t* lens, int B) {
   os2s::g_host_lens_set = true;
   return OS2S_OK;
 }
-// Named options of the convolution launchers (os2s_set_option; nothing here is read per launch):
-//   conv1d.variant            >= 0 forces a tile (list above), -1 = by shape
-//   conv1d.split              > 0 forces the tail split factor of the ping-pong kernel, -1 = cost model
-//   conv1d.pp_cost_256 / .pp_cost_2x128 / .pp_cost_3x128   fitted microseconds per 64-deep step of the three
-//       ping-pong tiles — the constants of the device-side tile choice (tools/bench_conv_shapes.py refits
-//       them); a cost >= 1e6 removes a narrow tile from the candidates
-//   conv1d.pp_dgrad_penalty   factor on the narrow tiles' cost in data-gradient launches (out_len given)
-//   conv1d.pp_prio            1: the loading wave of a narrow-tile slot runs at s_setprio 2
-//   conv1d.pp_min_cout        narrowest layer (output channels) the ping-pong kernels take (default 320)
-//   conv1x1.variant           the 1x1 launches: 0 / 1 = lockstep 128x128 tile, 2 = 256x256 ping-pong tile,
-//                             -1 (default) = ping-pong for a single K = 1 layer of >= pp_min_cout output channels,
-//                             lockstep for the grouped launches
-static os2s::OptionReg r_variant("conv1d.variant", [](double v) { g_conv_variant = (int)v; });
-static os2s::OptionReg r_split("conv1d.split", [](double v) { g_conv_split = (int)v; });
-static os2s::OptionReg r_c256("conv1d.pp_cost_256", [](double v) { os2s::g_pp_cost[0] = (float)v; });
-static os2s::OptionReg r_c2("conv1d.pp_cost_2x128", [](double v) { os2s::g_pp_cost[1] = (float)v; });
-static os2s::OptionReg r_c3("conv1d.pp_cost_3x128", [](double v) { os2s::g_pp_cost[2] = (float)v; });
-static os2s::OptionReg r_pen("conv1d.pp_dgrad_penalty", [](double v) { os2s::g_pp_cost[3] = (float)v; });
-static os2s::OptionReg r_prio("conv1d.pp_prio", [](double v) { os2s::g_pp_prio = (int)v; });
-static os2s::OptionReg r_min("conv1d.pp_min_cout", [](double v) { g_pp_min_cout = (int)v; });
+// Named options of the convolution launchers: include/os2s.h describes each under os2s_set_option (the pp_cost_*
+// constants of the device-side tile choice are refitted by tools/bench_conv_shapes.py)
+static os2s::OptionReg r_variant("conv1d.variant", &g_conv_variant);
+static os2s::OptionReg r_split("conv1d.split", &g_conv_split);
+static os2s::OptionReg r_c256("conv1d.pp_cost_256", &os2s::g_pp_cost[0]);
+static os2s::OptionReg r_c2("conv1d.pp_cost_2x128", &os2s::g_pp_cost[1]);
+static os2s::OptionReg r_c3("conv1d.pp_cost_3x128", &os2s::g_pp_cost[2]);
+static os2s::OptionReg r_pen("conv1d.pp_dgrad_penalty", &os2s::g_pp_cost[3]);
+static os2s::OptionReg r_prio("conv1d.pp_prio", &os2s::g_pp_prio);
+static os2s::OptionReg r_min("conv1d.pp_min_cout", &g_pp_min_cout, "OS2S_PP_MIN_COUT");
 // debug stamps "conv1d" (tools/pp_timeline.py, tools/ppn_timeline.py): device buffer of slot time stamps;
 // mode (256-column tile) = every step streams the weight tile of step 0 (always an L2 hit); narrow
 // tiles: bit 1 = no DMA issue in the loop, bit 2 = no fragment reads in the loop (timing only)
@@ -1216,9 +1197,9 @@ static os2s::StampReg r_stamps("conv1d", [](void* stamps, int mode) {
 });
 
 static int g_conv1x1_variant = -1;
-static os2s::OptionReg r_1x1("conv1x1.variant", [](double v) { g_conv1x1_variant = (int)v; });
+static os2s::OptionReg r_1x1("conv1x1.variant", &g_conv1x1_variant);
 static int g_conv1x1_order = 1;
-static os2s::OptionReg r_1x1o("conv1x1.order", [](double v) { g_conv1x1_order = v != 0.0; });
+static os2s::OptionReg r_1x1o("conv1x1.order", &g_conv1x1_order);
 
 extern "C" int os2s_conv1d_num_mtiles(int B, int Tout) {
   return B * os2s::ceil_div(Tout, os2s::kConvBM);
@@ -1265,7 +1246,7 @@ static int conv1d_fwd_impl(os2s_stream_t stream, const uint16_t* x, const uint16
   if (v < 0) {
     v = K >= 8 ? 3 : 0;
     if (Cout >= 512 && (long long)B * ceil_div(Tout, kConvBM) >= 256) v = 5;
-    if (Cout >= pp_min_cout()) v = 10;
+    if (Cout >= g_pp_min_cout) v = 10;
   }
   // K = 1: the lockstep tile's life is its 4 - 16 steps of exposed load latency (1.1 - 2 us each, one step of
   // prefetch: 33.7 us at 512 -> 512 channels, 26 752 rows); the ping-pong tile's rings hide it (26.3 us; 1024 ->
@@ -1377,7 +1358,7 @@ static int conv1x1_fwd_grouped_impl(os2s_stream_t stream, const os2s_conv_group_
   a.MT8 = ceil_div(a.MT, 8);
   a.NT = 0; a.nchunks = 0;
   a.R = BM; a.Rpad = BM;
-  a.tile_order = g_conv1x1_order;
+  a.tile_order = g_conv1x1_order != 0;
   ConvGroupTable gt;
   gt.ngroups = ngroups;
   int tiles = 0;

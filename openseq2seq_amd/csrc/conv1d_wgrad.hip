@@ -24,9 +24,6 @@
 //   * batch splits, only when a layer is too small to fill the chip otherwise,
 //     store partial dW tiles that one more launch sums in split order (with a
 //     workspace), or are combined with fp32 atomics (without one).
-#include <stdlib.h>
-
-#include <cstdlib>
 #include "os2s_common.hpp"
 #include "os2s_split_reduce.hpp"
 
@@ -1130,17 +1127,13 @@ __global__ __launch_bounds__(512, 2) void conv1d_wgrad1x1_pp_kernel(WgradArgs p,
 
 }  // namespace os2s
 
-static int wgrad_pp_min_units() {   // experiment knob (A/B runs on one box); default 8
-  static const int v = [] { const char* e = getenv("OS2S_WGRAD_PP_MIN_UNITS"); return e ? atoi(e) : 8; }();
-  return v;
-}
+static int g_wgrad_pp_min_units = 8;   // conv1d_wgrad.pp_min_units: experiment knob (A/B runs on one box)
+static int g_wgrad_k1_pp = -1;         // conv1d_wgrad.k1_pp: 0 = never, 1 = whenever the shape allows, -1 = by shape
 // K = 1: the 256 x 256 ping-pong tile needs a long reduction per output tile to pay for its
-// pipeline fill and the split reduction (OS2S_WGRAD1X1_PP: 0 = never, 1 = whenever the shape
-// allows, unset = by shape)
+// pipeline fill and the split reduction
 static bool wgrad1x1_pp_auto(int B, int T, int Cin, int Cout, bool have_ws) {
-  static const int mode = [] { const char* e = getenv("OS2S_WGRAD1X1_PP"); return e ? atoi(e) : -1; }();
-  if (mode == 0) return false;
-  if (mode == 1) return true;
+  if (g_wgrad_k1_pp == 0) return false;
+  if (g_wgrad_k1_pp == 1) return true;
   // measured (tools/bench_dense_shapes.py, 8300 rows): 2048 x 1024 and larger beat the lockstep
   // kernel and hipBLASLt (0.073 vs 0.082 / 0.075 ms; 32768 x 1024: 0.465 vs 1.03 / 0.526 ms); a
   // 1024 x 1024 output is 16 tiles cut 16 ways and loses to the lockstep kernel (0.071 vs 0.054 ms),
@@ -1158,10 +1151,12 @@ static int g_wgrad_dbg_mode = 0;
 // os2s_set_option: conv1d_wgrad.variant (0 = lockstep kernel, 1 = ping-pong, 2 = K = 1 ping-pong, -1 = by shape),
 // conv1d_wgrad.split (> 0 forces the reduction split factor of the ping-pong kernels, -1 = cost model);
 // debug stamps "conv1d_wgrad" (tools/pp_timeline.py): per-slot time stamps of the ping-pong kernel
-static os2s::OptionReg r_wg_variant("conv1d_wgrad.variant", [](double v) { g_wgrad_variant = (int)v; });
-static os2s::OptionReg r_wg_split("conv1d_wgrad.split", [](double v) { g_wgrad_split = (int)v; });
-static os2s::OptionReg r_wg_abl("conv1d_wgrad.sw_ablate", [](double v) { g_wgrad_sw_ablate = (int)v; });
-static os2s::OptionReg r_wg_xcd("conv1d_wgrad.xcd_order", [](double v) { g_wgrad_xcd = v != 0 ? 1 : 0; });
+static os2s::OptionReg r_wg_variant("conv1d_wgrad.variant", &g_wgrad_variant);
+static os2s::OptionReg r_wg_split("conv1d_wgrad.split", &g_wgrad_split);
+static os2s::OptionReg r_wg_abl("conv1d_wgrad.sw_ablate", &g_wgrad_sw_ablate);
+static os2s::OptionReg r_wg_xcd("conv1d_wgrad.xcd_order", &g_wgrad_xcd);
+static os2s::OptionReg r_wg_min("conv1d_wgrad.pp_min_units", &g_wgrad_pp_min_units, "OS2S_WGRAD_PP_MIN_UNITS");
+static os2s::OptionReg r_wg_k1("conv1d_wgrad.k1_pp", &g_wgrad_k1_pp, "OS2S_WGRAD1X1_PP");
 static os2s::StampReg r_wg_stamps("conv1d_wgrad", [](void* stamps, int mode) {
   g_wgrad_dbg = (unsigned long long*)stamps;
   g_wgrad_dbg_mode = mode;
@@ -1181,7 +1176,7 @@ static os2s::WgradArgs wgrad_args(const uint16_t* x, long long x_ld, const uint1
   a.accumulate = accumulate ? 1 : 0;
   a.NTP = 1; a.NSPLIT = 1; a.NG = 1;
   a.xrows = 64; a.xrows_pad = 64;
-  a.ncu = 256; a.force_split = g_wgrad_split; a.xcd_order = g_wgrad_xcd;
+  a.ncu = 256; a.force_split = g_wgrad_split; a.xcd_order = g_wgrad_xcd != 0;
   return a;
 }
 
@@ -1302,7 +1297,7 @@ static int conv1d_wgrad_impl_g(os2s_stream_t stream, const uint16_t* x, long lon
     }
   }
 
-  if (pp_shape && g_wgrad_variant != 0 && (groups || g_wgrad_variant == 1 || pp_units >= wgrad_pp_min_units())) {
+  if (pp_shape && g_wgrad_variant != 0 && (groups || g_wgrad_variant == 1 || pp_units >= g_wgrad_pp_min_units)) {
     wgrad_tap_quad_geometry(a, 24 * 1024);              // 3 DMA rounds of 8 waves x 1 KB
     const size_t smem = (size_t)2 * 64 * 256 + (size_t)3 * a.xbuf_bytes + a.steptab_bytes + (a.dbg ? 2 * 48 * 10 * 8 : 0);
     if (smem <= 160 * 1024) {

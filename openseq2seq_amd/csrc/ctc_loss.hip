@@ -18,7 +18,6 @@
 //      beta_t(s) - logp_t(l'_s) - ll) (a posterior, <= 1) the per-class sums are
 //      a dense one-hot product over the extended label — deterministic, no
 //      atomics:  dlogit[t,v] = softmax_t(v) - sum_{s: l'_s = v} e_s.
-#include <cstdlib>
 #include "os2s_common.hpp"
 
 namespace os2s {
@@ -451,6 +450,9 @@ extern "C" size_t os2s_ctc_loss_workspace_bytes(int T, int B, int V, int Lmax) {
   return n + 256;
 }
 
+static int g_ctc_wave = 1;   // ctc_loss.wave: 0 = always the 256-thread alpha / beta kernel (A/B switch)
+static os2s::OptionReg r_ctc_wave("ctc_loss.wave", &g_ctc_wave, "OS2S_CTC_WAVE");
+
 extern "C" int os2s_ctc_loss(os2s_stream_t stream_, const float* logits,
                              const int32_t* in_len, const int32_t* labels,
                              const int32_t* label_len, int T, int B, int V, int Lmax,
@@ -479,7 +481,7 @@ extern "C" int os2s_ctc_loss(os2s_stream_t stream_, const float* logits,
   const size_t smem_g = (size_t)Smax * 4 * (1 + kGR);
   if (smem_ab > 64 * 1024 || smem_g > 64 * 1024) return OS2S_ERR_UNSUPPORTED;
   // one wave per (sample, direction) when the extended label fits 64 lanes x KS registers
-  static const bool wave_path = !(getenv("OS2S_CTC_WAVE") && atoi(getenv("OS2S_CTC_WAVE")) == 0);
+  const bool wave_path = g_ctc_wave != 0;
   const size_t smem_w = (size_t)2 * kTC * V * 4;
   if (wave_path && V <= 32 && Smax <= 64 * 4) {
     OS2S_LAUNCH(ctc_alpha_beta_wave_kernel<4>, dim3(2 * B), dim3(64), smem_w, stream, logp, labels,

@@ -908,9 +908,9 @@ __global__ __launch_bounds__(256) void pointwise_fold_bwd_kernel(const float* __
 using namespace os2s;
 
 static int g_dw_ablate = 0;     // measurement hook (tools/bench_depthwise.py): parts of the matrix-core kernel switched off
-static os2s::OptionReg r_dw_ablate("depthwise.ablate", [](double v) { g_dw_ablate = (int)v; });
+static os2s::OptionReg r_dw_ablate("depthwise.ablate", &g_dw_ablate);
 static int g_dw_variant = -1;   // test / experiment hook: 0 = the generic kernels only
-static os2s::OptionReg r_dw_variant("depthwise.variant", [](double v) { g_dw_variant = (int)v; });
+static os2s::OptionReg r_dw_variant("depthwise.variant", &g_dw_variant);
 
 static int dw_fill(DwArgs& a, int B, int Tin, int Tout, int C, int K, int stride, int dil, int padL) {
   OS2S_REQUIRE(B >= 1 && Tin >= 1 && Tout >= 1 && C >= 8 && C % 8 == 0 && K >= 1 && stride >= 1 && dil >= 1);

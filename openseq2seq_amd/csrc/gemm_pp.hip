@@ -690,6 +690,6 @@ extern "C" int os2s_gemm_nt(os2s_stream_t stream, const uint16_t* A, long long l
 }
 
 // os2s_set_option("gemm_nt.split", f): > 0 forces the tail split factor, 0 disables the split, < 0 = cost model
-static os2s::OptionReg r_gemm_split("gemm_nt.split", [](double v) { g_gemm_split = (int)v; });
+static os2s::OptionReg r_gemm_split("gemm_nt.split", &g_gemm_split);
 // os2s_set_option("gemm_nt.tile", t): 0 = by shape, 256 = always the 256 x 256 tile, 160 = the 160 x 256 tile whenever legal
-static os2s::OptionReg r_gemm_tile("gemm_nt.tile", [](double v) { g_gemm_tile = (int)v; });
+static os2s::OptionReg r_gemm_tile("gemm_nt.tile", &g_gemm_tile);

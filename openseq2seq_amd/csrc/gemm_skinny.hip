@@ -9,8 +9,6 @@
 // wave issuing all loads of its K-share before its first MFMA (rnn_tile.hpp), so the whole
 // product is ~one round trip + an LDS reduction. Bound: launch + L2 latency (≈5 us), then
 // HBM for W.
-#include <stdlib.h>
-
 #include "os2s_common.hpp"
 #include "rnn_tile.hpp"
 
@@ -204,6 +202,12 @@ __global__ __launch_bounds__(512) void gemm_skinny_lds_kernel(SkinnyArgs p) {
 
 using namespace os2s;
 
+// gemm_skinny.variant: 0 = reg, 1 = l32, 2 = l64, 3 = wide, -1 = by shape (tools / tests); the environment form
+// OS2S_SKINNY_VARIANT is the text "reg" | "l32" | "l64" | "wide"
+static int g_skinny_variant = -1;
+static os2s::OptionReg r_skinny("gemm_skinny.variant", &g_skinny_variant, "OS2S_SKINNY_VARIANT",
+                                [](const char* t) { return t[0] == 'r' ? 0 : (t[0] == 'w' ? 3 : (t[0] && t[1] == '6' ? 2 : 1)); });
+
 extern "C" int os2s_gemm_skinny(os2s_stream_t stream, const uint16_t* x, long long ldx,
                                 const uint16_t* w, long long ldw, const float* bias,
                                 const uint16_t* residual, long long ldr, int M, int N, int K,
@@ -215,13 +219,11 @@ extern "C" int os2s_gemm_skinny(os2s_stream_t stream, const uint16_t* x, long lo
   a.y = y; a.ldy = ldy; a.M = M; a.N = N; a.K = K; a.relu = relu;
   // variant: 128x256 tiles when even those fill the chip (the vocabulary projection), 64x64
   // tiles when they do, else 32x32 tiles (4x the workgroups, each streaming half the bytes);
-  // "reg" = the register-direct kernel. OS2S_SKINNY_VARIANT ("reg" | "l64" | "l32" | "wide")
-  // overrides (tools / tests).
-  static const char* const force = getenv("OS2S_SKINNY_VARIANT");     // read once per process
+  // "reg" = the register-direct kernel. gemm_skinny.variant overrides.
   const long long blocks64 = (long long)((N + 63) / 64) * ((M + 63) / 64);
   int variant = blocks64 >= 192 ? 2 : 1;
   if (M > 128 && (long long)((N + 127) / 128) * ((M + 255) / 256) >= 192) variant = 3;
-  if (force) variant = force[0] == 'r' ? 0 : (force[0] == 'w' ? 3 : (force[1] == '6' ? 2 : 1));
+  if (g_skinny_variant >= 0) variant = g_skinny_variant;
   if (variant == 3) {     // wide: 128 (n) x 256 (m) per workgroup, no K-split — least L2 traffic
     using C = LdsCfg<4, 8, 64, 4, 1>;
     OS2S_LAUNCH_LDS((gemm_skinny_lds_kernel<4, 8, 64, 4, 1>), dim3((N + 127) / 128, (M + 255) / 256),

@@ -33,30 +33,45 @@ extern "C" const char* os2s_last_error_detail(void) { return g_last_err; }
 // (narrow / K = 1 / stride-2 conv weight gradients: no reduction split; depthwise weight gradients: one
 // workgroup per channel block / one tile per launch; embedding gradient: one thread per column chunk
 // walking the tokens in order; style-token attention: one workgroup). Slower; bit-identical run to run.
-static int g_deterministic = -1;
-extern "C" int os2s_deterministic(void) {
-  if (g_deterministic < 0) {
-    const char* e = getenv("OS2S_DETERMINISTIC");
-    g_deterministic = (e && atoi(e) != 0) ? 1 : 0;
-  }
-  return g_deterministic;
-}
+static int g_deterministic = 0;
+static os2s::OptionReg r_deterministic("deterministic", &g_deterministic, "OS2S_DETERMINISTIC");
+extern "C" int os2s_deterministic(void) { return g_deterministic != 0; }
 extern "C" void os2s_set_deterministic(int on) { g_deterministic = on ? 1 : 0; }
 
 // ---- named options: one entry point for every test / measurement knob of the library ----
 namespace {
+struct Option {
+  const char* name; int* i; float* f; os2s::OptionSetter set; os2s::OptionGetter get;
+  void assign(double v) const { if (set) set(v); else if (i) *i = (int)v; else *f = (float)v; }
+  double value() const { return get ? get() : i ? (double)*i : (double)*f; }
+};
 template <typename F> struct Named { const char* name; F fn; };
-std::vector<Named<os2s::OptionSetter>>& option_table() { static std::vector<Named<os2s::OptionSetter>> t; return t; }
+std::vector<Option>& option_table() { static std::vector<Option> t; return t; }
 std::vector<Named<os2s::StampSetter>>& stamp_table() { static std::vector<Named<os2s::StampSetter>> t; return t; }
+const Option* find_option(const char* name) {
+  for (const auto& o : option_table())
+    if (name && strcmp(o.name, name) == 0) return &o;
+  return nullptr;
+}
 }  // namespace
-os2s::OptionReg::OptionReg(const char* name, OptionSetter fn) { option_table().push_back({name, fn}); }
+os2s::OptionReg::OptionReg(const char* name, int* var, const char* env, OptionParser parse) {
+  option_table().push_back({name, var, nullptr, nullptr, nullptr});
+  const char* e = env ? getenv(env) : nullptr;   // the library's one read of the environment
+  if (e) option_table().back().assign(parse ? parse(e) : atoi(e));   // as os2s_set_option would
+}
+os2s::OptionReg::OptionReg(const char* name, float* var) { option_table().push_back({name, nullptr, var, nullptr, nullptr}); }
+os2s::OptionReg::OptionReg(const char* name, OptionSetter s, OptionGetter g) { option_table().push_back({name, nullptr, nullptr, s, g}); }
 os2s::StampReg::StampReg(const char* name, StampSetter fn) { stamp_table().push_back({name, fn}); }
 
 extern "C" int os2s_set_option(const char* name, double value) {
-  if (!name) return -1;
-  for (const auto& o : option_table())
-    if (strcmp(o.name, name) == 0) { o.fn(value); return 0; }
-  return -1;
+  const Option* o = find_option(name);
+  if (o) o->assign(value);
+  return o ? 0 : -1;
+}
+extern "C" int os2s_get_option(const char* name, double* value) {
+  const Option* o = find_option(name);
+  if (o && value) *value = o->value();
+  return o && value ? 0 : -1;
 }
 extern "C" const char* os2s_option_name(int index) {
   const auto& t = option_table();

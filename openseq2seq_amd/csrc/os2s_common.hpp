@@ -54,11 +54,22 @@ extern "C" void os2s_record_hip_error(int hip_error, const char* where);
 namespace os2s {
 
 // Named test / measurement options behind the ONE entry point os2s_set_option (os2s_api.hip). A translation
-// unit registers its knobs next to the state they set: `static OptionReg r("conv1d.variant", [](double v) {...});`
+// unit registers its knobs next to the state they set: `static OptionReg r("conv1d.variant", &g_conv_variant);`
 // (host-side only; the registry lives behind a function-local static so the order in which the translation
-// units are initialised does not matter). Nothing registered here is read from the environment.
+// units are initialised does not matter). A knob is the file-scope variable the launch path reads, registered by
+// address (a setter / getter pair only where setting has a side effect); os2s_get_option returns it. A
+// registration may name an environment variable: it is read ONCE, at registration (static initialisation, when the
+// library is loaded), and stored as os2s_set_option would: atoi of the text, or `parse` of it. That is the
+// library's only getenv. Options are changed BETWEEN passes: a forward and its backward, and a workspace-size query
+// and the call that uses the workspace, have to see the same values.
 typedef void (*OptionSetter)(double value);
-struct OptionReg { OptionReg(const char* name, OptionSetter fn); };
+typedef double (*OptionGetter)();
+typedef int (*OptionParser)(const char* text);
+struct OptionReg {
+  OptionReg(const char* name, int* var, const char* env = nullptr, OptionParser parse = nullptr);
+  OptionReg(const char* name, float* var);
+  OptionReg(const char* name, OptionSetter set, OptionGetter get);
+};
 // debug time-stamp buffers of instrumented kernels (os2s_set_debug_stamps): fn(stamps, mode)
 typedef void (*StampSetter)(void* stamps, int mode);
 struct StampReg { StampReg(const char* name, StampSetter fn); };

@@ -24,7 +24,6 @@
 //     word os2s_gru_xcd_status() returns and the host layer redoes the step on the per-step path
 //     (Model.train_step; launches themselves do not fail on a set word — see "sticky abort word").
 #include <cstdio>
-#include <cstdlib>
 
 #include "os2s_common.hpp"
 
@@ -555,7 +554,10 @@ __global__ __launch_bounds__(kXcdThreads) void gru_xcd_bwd_kernel(GruXcdArgsB a)
 
 using namespace os2s;
 
-static int g_gru_xcd_mode = -1;    // -1 = environment (OS2S_GRU_XCD, default on), 0 = off, 1 = on
+static int g_gru_xcd_fwd = 1, g_gru_xcd_bwd = 1;   // the persistent forward / backward kernels (0 = per-step launches)
+static os2s::OptionReg r_xcd_fwd("gru_xcd.fwd", &g_gru_xcd_fwd, "OS2S_GRU_XCD");
+static os2s::OptionReg r_xcd_bwd("gru_xcd.bwd", &g_gru_xcd_bwd, "OS2S_GRU_XCD_BWD");
+static int g_gru_xcd_mode = -1;    // -1 = what gru_xcd.fwd says, 0 = off, 1 = on
 static int g_gru_xcd_force_abort = 0;
 // 2 (test hook) = on, and the NEXT persistent forward launch starts with its abort flag set: every workgroup
 // leaves at its first wait, the outputs are garbage and the sticky word reports a timeout — what a launch that
@@ -565,11 +567,7 @@ extern "C" void os2s_gru_xcd_set_mode(int m) {
   g_gru_xcd_mode = m == 2 ? 1 : m;
 }
 
-static bool gru_xcd_enabled() {
-  if (g_gru_xcd_mode >= 0) return g_gru_xcd_mode != 0;
-  static const int v = [] { const char* e = getenv("OS2S_GRU_XCD"); return e ? atoi(e) : 1; }();
-  return v != 0;
-}
+static bool gru_xcd_enabled() { return (g_gru_xcd_mode >= 0 ? g_gru_xcd_mode : g_gru_xcd_fwd) != 0; }
 
 // bytes of the exchange buffers + flags per direction (appended to the step path's workspace)
 extern "C" size_t os2s_gru_xcd_workspace_bytes(int B, int H) {
@@ -713,8 +711,7 @@ static size_t gru_xcd_bwd_lds_bytes(int H) {
 }
 
 bool gru_xcd_bwd_supported(int B, int T, int H, int ndir) {
-  static const int on = [] { const char* e = getenv("OS2S_GRU_XCD_BWD"); return e ? atoi(e) : 1; }();
-  if (!on) return false;
+  if (!g_gru_xcd_bwd) return false;
   if (!gru_xcd_supported(B, T, H, ndir) || B > 16) return false;
   const int upc = (H + kXcdCus - 1) / kXcdCus;
   if (upc > 32 || upc * 16 > kXcdThreads || H > 8 * kXcdBT * 16) return false;

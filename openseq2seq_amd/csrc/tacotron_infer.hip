@@ -32,7 +32,6 @@
 // state[1]; every later launch returns at once, so the host may enqueue steps ahead and poll every N steps —
 // the result does not depend on N.
 #include <cstdio>
-#include <cstdlib>
 #include "attn_decoder_common.hpp"
 #include "rnn_tile.hpp"
 
@@ -767,22 +766,23 @@ static int ti_check(const os2s_tacotron_infer_t* x) {
 
 extern "C" int os2s_tacotron_infer_supported(const os2s_tacotron_infer_t* x) { return ti_check(x) == OS2S_OK; }
 
-// units per workgroup: 4 (16 gate rows: H / 4 workgroups) or 8 (32 rows: half the workgroups, half the reads of the
-// state rows); OS2S_TI_ROWS = 16 | 32 and OS2S_TI_WAVES = 8 | 16 override the defaults (experiments)
-static int ti_rows() {
-  static const int v = [] { const char* e = getenv("OS2S_TI_ROWS"); return e ? atoi(e) : 16; }();
-  return v == 32 ? 32 : 16;
-}
+// Experiment switches (no buffer size depends on one). rows: gate rows per workgroup, 16 (4 units: H / 4
+// workgroups) or 32 (8 units: half the workgroups, half the reads of the state rows); geom: 100 * waves + chunk
+// slots per wave of the 16-row kernel, 0 = by K; ctx_parts: > 0 = parts the context columns are cut into; debug:
+// TiTail::dbg; attn_decoder.fast: 0 = the training pass keeps ad_cell_fwd_kernel and ad_loc_scores_kernel
+static int g_ti_rows = 16, g_ti_geom = 0, g_ti_ctx_parts = 0, g_ti_debug = 0, g_ad_fast = 1;
+static os2s::OptionReg r_ti_rows("tacotron_infer.rows", &g_ti_rows, "OS2S_TI_ROWS");
+static os2s::OptionReg r_ti_geom("tacotron_infer.geom", &g_ti_geom, "OS2S_TI_GEOM", [](const char* t) {
+  int a = 0, b = 0; return sscanf(t, "%dx%d", &a, &b) == 2 ? a * 100 + b : 0;
+});
+static os2s::OptionReg r_ti_parts("tacotron_infer.ctx_parts", &g_ti_ctx_parts, "OS2S_TI_CTX_PARTS");
+static os2s::OptionReg r_ti_debug("tacotron_infer.debug", &g_ti_debug, "OS2S_TI_DEBUG");
+static os2s::OptionReg r_ad_fast("attn_decoder.fast", &g_ad_fast, "OS2S_AD_FAST");
 // waves x chunk slots per wave of the 16-row kernel: by default the smallest number of slots that covers K with 8
 // or 9 waves (every slot of requests costs about a microsecond: 8 x 5 -> 8 x 4 measured 9.7 -> 8.7 us on the
-// K = 2048 layer; K = 2304 = 36 chunks takes 9 waves x 4). OS2S_TI_GEOM = "<waves>x<slots>" overrides (experiments).
+// K = 2048 layer; K = 2304 = 36 chunks takes 9 waves x 4). tacotron_infer.geom overrides (experiments).
 static void ti_geom(int K, int* nw, int* cpw) {
-  static const int env = [] {
-    const char* e = getenv("OS2S_TI_GEOM");
-    int a = 0, b = 0;
-    return (e && sscanf(e, "%dx%d", &a, &b) == 2) ? a * 100 + b : 0;
-  }();
-  if (env) { *nw = env / 100; *cpw = env % 100; return; }
+  if (g_ti_geom) { *nw = g_ti_geom / 100; *cpw = g_ti_geom % 100; return; }
   const int nchunks = K >> 6;
   if (nchunks <= 32) { *nw = 8; *cpw = 4; }
   else if (nchunks <= 36) { *nw = 9; *cpw = 4; }
@@ -791,7 +791,7 @@ static void ti_geom(int K, int* nw, int* cpw) {
 
 template <bool FP8, int NT>
 static int ti_launch_lstm_nt(hipStream_t stream, const TiLstm& c) {
-  if (ti_rows() == 32 && c.H % 8 == 0) {
+  if (g_ti_rows == 32 && c.H % 8 == 0) {
     OS2S_LAUNCH((ti_lstm_kernel<FP8, 2, NT, 8, 5>), dim3(ceil_div(c.H, 8)), dim3(512), 0, stream, c);
     return OS2S_OK;
   }
@@ -850,16 +850,15 @@ extern "C" int os2s_tacotron_infer_steps(os2s_stream_t stream_, const os2s_tacot
   lx.dal = nullptr; lx.dcum_part = nullptr;
   // context columns per part: 16-column MFMA tiles, up to two per wave with their operands requested up front.
   // (parts + 1) * B workgroups should not exceed the CUs: two workgroups on one CU measured 12 us for the launch
-  // against 7.6 / 9.1 for the context / frame parts alone. OS2S_TI_CTX_PARTS overrides (experiments).
-  static const int parts_env = [] { const char* e = getenv("OS2S_TI_CTX_PARTS"); return e ? atoi(e) : 0; }();
-  int ctx_parts = parts_env > 0 ? parts_env : (B > 28 ? 4 : kLocCtxParts);
+  // against 7.6 / 9.1 for the context / frame parts alone. tacotron_infer.ctx_parts overrides (experiments).
+  int ctx_parts = g_ti_ctx_parts > 0 ? g_ti_ctx_parts : (B > 28 ? 4 : kLocCtxParts);
   while (ctx_parts > 1 && M % (16 * ctx_parts)) ctx_parts >>= 1;
   const int MQ = M / ctx_parts;
   const size_t lds_s = ti_scores_lds_floats(d->S) * sizeof(float);
   const size_t lds_c = ti_ctx_lds_floats(d->S, P, x->n_mel) * sizeof(float);
   TiTail q;
   q.P = P; q.n_mel = x->n_mel; q.mask_seq = x->mask_decoder_sequence; q.first = 0;
-  { static const int dbg = [] { const char* e = getenv("OS2S_TI_DEBUG"); return e ? atoi(e) : 0; }(); q.dbg = dbg; }
+  q.dbg = g_ti_debug;
   q.keep = x->prenet_keep; q.seed[0] = x->prenet_seed[0]; q.seed[1] = x->prenet_seed[1];
   q.wp1 = (const bf16_t*)x->wp1; q.bp1 = x->bp1; q.wp2 = (const bf16_t*)x->wp2; q.bp2 = x->bp2;
   q.wout_h = (const bf16_t*)x->wout_h; q.pv_t = (const bf16_t*)x->pv_t; q.values_t = (const bf16_t*)x->values_t;
@@ -905,11 +904,10 @@ extern "C" int os2s_tacotron_infer_steps(os2s_stream_t stream_, const os2s_tacot
 // ---- the training pass on the small-code kernels -------------------------------------------------------------
 // os2s_attn_decoder_fwd (location-sensitive mode, no per-sample target lengths, B <= 32) launches ti_lstm_kernel
 // for the cells (+ input projection of the step, saved gates, output dropout) and ti_scores_part for the scores:
-// 13.3 -> ~8.7 us per cell launch and 10.4 -> ~6.5 us per score launch of a Tacotron2 decoder step. OS2S_AD_FAST=0
-// keeps the round-3 kernels.
+// 13.3 -> ~8.7 us per cell launch and 10.4 -> ~6.5 us per score launch of a Tacotron2 decoder step.
+// attn_decoder.fast = 0 keeps the round-3 kernels.
 bool os2s::ad_fast_cells(const os2s_attn_decoder_t* d) {
-  static const int on = [] { const char* e = getenv("OS2S_AD_FAST"); return e ? atoi(e) : 1; }();
-  if (!on || d->tgt_len || d->score_mode != 2 || d->B > 32 || d->H > 1024 || d->H % 64 || d->M % 64 || d->loc_k > 32)
+  if (!g_ad_fast || d->tgt_len || d->score_mode != 2 || d->B > 32 || d->H > 1024 || d->H % 64 || d->M % 64 || d->loc_k > 32)
     return false;
   if (ti_scores_lds_floats(d->S) * sizeof(float) > 64 * 1024) return false;
   for (int l = 0; l < d->L; ++l)

@@ -5,8 +5,8 @@ the comparison of the two.
   python -m tests._attn_decoder_cases CASE
 
 runs one case on cuda:0, applies the assertions of compare() and exits non-zero on a mismatch (the A/B
-switches OS2S_ATTN_SPLIT / OS2S_CELL_SPLIT / OS2S_AD_FAST are read once per process, so each setting needs
-a process of its own). One assertion has an exemption, see second_backward_judged().
+switches OS2S_ATTN_SPLIT / OS2S_CELL_SPLIT / OS2S_AD_FAST are read when the library is loaded, so a setting given
+through the environment needs a process of its own). One assertion has an exemption, see second_backward_judged().
 
 Both sides consume the same bf16-rounded parameters and inputs and the same dropout masks. The oracle
 runs in float64, once plainly (R) and, for the tight forward bound, once with a straight-through bf16
@@ -457,12 +457,14 @@ def run_case(name, device, **kw):
 
 
 def second_backward_judged(name):
-  """False only for a location-mode case in a process started with OS2S_ATTN_SPLIT=0. That setting selects
+  """False only for a location-mode case while the option attn_decoder.attn_split is 0 (a process started with
+  OS2S_ATTN_SPLIT=0, or an os2s_set_option call). That setting selects
   the one-workgroup location backward, ad_attn_bwd_kernel<true>, whose wave groups add the state gradient
   (dcum_l) and the filter gradient (dwk_l) with LDS float atomics: the order of the additions, and with it
   the last bits, vary from run to run. Everything downstream of the two can differ; compare() then logs
   which tensors did. Every other kernel, the other two switches' included, is held to bit identity."""
-  return not (os.environ.get("OS2S_ATTN_SPLIT", "").strip() == "0" and CASES[name][7] == 2)
+  from openseq2seq_amd import _lib
+  return not (_lib.get_option("attn_decoder.attn_split") == 0 and CASES[name][7] == 2)
 
 
 def check_case(name, device, log=print, assert_second=None):

@@ -273,16 +273,27 @@ def test_transformer_beam_search_consistency(cuda, Lmax):
     (256, 1024, 4096, True, False, True), (200, 4096, 1024, True, True, False),
     (5, 40, 72, True, False, True), (64, 2048, 1032, False, False, False)])
 @pytest.mark.parametrize("variant", ["l64", "l32", "reg", "wide"])
-def test_gemm_skinny(cuda, M, N, K, bias, relu, res, variant, monkeypatch):
-  """fp32 reference on the same bf16 inputs; bf16 output rounding: rtol 1e-2, atol 2e-2."""
-  from openseq2seq_amd import capi
-  monkeypatch.setenv("OS2S_SKINNY_VARIANT", variant)
+def test_gemm_skinny(cuda, M, N, K, bias, relu, res, variant):
+  """Every kernel of os2s_gemm_skinny, forced with the option gemm_skinny.variant, at every shape. fp32 reference
+  on the same bf16 inputs; bf16 output rounding: rtol 1e-2, atol 2e-2."""
+  from openseq2seq_amd import _lib, capi
+  forced = {"reg": 0, "l32": 1, "l64": 2, "wide": 3}[variant]
   g = torch.Generator().manual_seed(M + N + K)
   x = (torch.randn(M, K, generator=g)).to(torch.bfloat16).to(cuda)
   w = (torch.randn(N, K, generator=g) / K ** 0.5).to(torch.bfloat16).to(cuda)
   b = torch.randn(N, generator=g).to(cuda) if bias else None
   r = torch.randn(M, N, generator=g).to(torch.bfloat16).to(cuda) if res else None
-  y = capi.gemm_skinny(x, w, bias=b, relu=relu, residual=r)
+  wide = torch.zeros(M, K + 64, dtype=torch.bfloat16, device=cuda)
+  wide[:, 64:] = x
+  _lib.set_option("gemm_skinny.variant", forced)
+  try:
+    assert _lib.get_option("gemm_skinny.variant") == forced
+    y = capi.gemm_skinny(x, w, bias=b, relu=relu, residual=r)
+    # strided input (a column slice of a wider buffer)
+    y2 = capi.gemm_skinny(wide[:, 64:], w, bias=b, relu=relu, residual=r)
+    assert _lib.get_option("gemm_skinny.variant") == forced
+  finally:
+    _lib.set_option("gemm_skinny.variant", -1)
   ref = x.float() @ w.float().t()
   if bias:
     ref = ref + b
@@ -291,8 +302,4 @@ def test_gemm_skinny(cuda, M, N, K, bias, relu, res, variant, monkeypatch):
   if res:
     ref = ref + r.float()
   torch.testing.assert_close(y.float(), ref, rtol=1e-2, atol=2e-2)
-  # strided input (a column slice of a wider buffer)
-  wide = torch.zeros(M, K + 64, dtype=torch.bfloat16, device=cuda)
-  wide[:, 64:] = x
-  y2 = capi.gemm_skinny(wide[:, 64:], w, bias=b, relu=relu, residual=r)
   assert torch.equal(y, y2)

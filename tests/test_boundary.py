@@ -118,15 +118,15 @@ def test_missing_library_fails_loudly(monkeypatch):
 
 
 def test_named_options_are_the_only_knobs():
-  """One entry point for every test / measurement knob (os2s_set_option): each name the tests, tools and
-  bench.py use is registered, each registered name is documented in the header, an unknown name is refused,
+  """One entry point for every test / measurement knob (os2s_set_option, read back by os2s_get_option): each
+  name the tests, tools and bench.py use is registered, each registered name is documented in the header, an unknown name is refused,
   and the library exports no per-knob setter beside it (the product controls os2s_set_deterministic and
   os2s_gru_xcd_set_mode, and the host-length hint, are entry points of their own)."""
   import glob
   import subprocess
   from openseq2seq_amd import _lib
   names = _lib.option_names()
-  assert len(names) == len(set(names)) >= 16
+  assert len(names) == len(set(names)) >= 38
   header = open(os.path.join(REPO, "include", "os2s.h")).read()
   used = set()
   for f in glob.glob(os.path.join(REPO, "tests", "*.py")) + glob.glob(os.path.join(REPO, "tools", "*.py")) + \
@@ -134,8 +134,9 @@ def test_named_options_are_the_only_knobs():
     if os.path.basename(f) == "test_boundary.py":
       continue
     src = open(f).read()
-    used |= set(re.findall(r"set_option\(b?\"([a-z0-9_.]+)\"", src))
-    used |= set(re.findall(r"\"((?:conv1d|conv1x1|conv1d_wgrad|gemm_nt|depthwise)\.[a-z0-9_]+)\"", src))
+    used |= set(re.findall(r"[sg]et_option\(b?\"([a-z0-9_.]+)\"", src))
+    used |= set(re.findall(r"\"((?:conv1d|conv1x1|conv1d_wgrad|gemm_nt|depthwise|gemm_skinny|ctc_loss|gru_xcd|attn_decoder|"
+                           r"tacotron_infer)\.[a-z0-9_]+)\"", src))
   assert used and not (used - set(names)), sorted(used - set(names))
   for n in names:
     assert n in header, n

@@ -27,22 +27,30 @@ def _case(seed, T, B, V, L, peaky=1.0):
                                            (257, 5, 29, 100, 3.0), (840, 4, 29, 400, 1.0),
                                            (33, 3, 40, 1, 1.0), (50, 2, 29, 0, 1.0)])
 def test_ctc_vs_oracle(cuda, T, B, V, L, peaky):
-  from openseq2seq_amd import capi
+  """The two small shapes that the one-wave alpha / beta kernel takes by shape run a second time with the option
+  ctc_loss.wave = 0, on the 256-thread kernel, under the same assertions."""
+  from openseq2seq_amd import _lib, capi
   logits, in_len, labels, label_len = _case(T + B, T, B, V, L, peaky)
   r_loss, r_mean, r_grad = ctc.ctc_loss_torch(logits, in_len, labels, label_len, want_grad=True)
   d = cuda
-  out = capi.ctc_loss(torch.from_numpy(logits).to(d), torch.from_numpy(in_len).to(d),
-                      torch.from_numpy(labels).to(d), torch.from_numpy(label_len).to(d),
-                      grad_scale=1.0, want_grad=True, want_grad_bf16=True,
-                      vpad=((V + 7) // 8) * 8 if V > 32 else 32)
-  torch.cuda.synchronize()
-  torch.testing.assert_close(out["loss_per_sample"].cpu(), r_loss, rtol=1e-3, atol=1e-3)
-  torch.testing.assert_close(out["loss_mean"].cpu()[0], r_mean, rtol=1e-3, atol=1e-3)
-  torch.testing.assert_close(out["dlogits"].cpu(), r_grad, rtol=1e-3, atol=2e-4)
-  g16 = out["dlogits_bf16"].float().cpu()      # [B,T,32]
-  torch.testing.assert_close(g16[:, :, :V], r_grad.permute(1, 0, 2), rtol=1e-2, atol=4e-3)
-  if g16.shape[2] > V:
-    assert float(g16[:, :, V:].abs().max()) == 0.0
+  for wave in (1, 0) if (T, B, V, L) in ((20, 4, 5, 6), (64, 8, 29, 20)) else (1,):
+    _lib.set_option("ctc_loss.wave", wave)
+    try:
+      assert _lib.get_option("ctc_loss.wave") == wave
+      out = capi.ctc_loss(torch.from_numpy(logits).to(d), torch.from_numpy(in_len).to(d),
+                          torch.from_numpy(labels).to(d), torch.from_numpy(label_len).to(d),
+                          grad_scale=1.0, want_grad=True, want_grad_bf16=True,
+                          vpad=((V + 7) // 8) * 8 if V > 32 else 32)
+      torch.cuda.synchronize()
+    finally:
+      _lib.set_option("ctc_loss.wave", 1)
+    torch.testing.assert_close(out["loss_per_sample"].cpu(), r_loss, rtol=1e-3, atol=1e-3)
+    torch.testing.assert_close(out["loss_mean"].cpu()[0], r_mean, rtol=1e-3, atol=1e-3)
+    torch.testing.assert_close(out["dlogits"].cpu(), r_grad, rtol=1e-3, atol=2e-4)
+    g16 = out["dlogits_bf16"].float().cpu()      # [B,T,32]
+    torch.testing.assert_close(g16[:, :, :V], r_grad.permute(1, 0, 2), rtol=1e-2, atol=4e-3)
+    if g16.shape[2] > V:
+      assert float(g16[:, :, V:].abs().max()) == 0.0
 
 
 def test_ctc_small_numpy_pin(cuda):

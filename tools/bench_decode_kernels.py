@@ -10,7 +10,7 @@ _sys.path.insert(0, _os.path.join(_os.path.dirname(_os.path.abspath(__file__)), 
 import lt_backend  # noqa: E402  (hipBLASLt comparison harness, tools only)
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from openseq2seq_amd import capi  # noqa: E402
+from openseq2seq_amd import _lib, capi  # noqa: E402
 
 
 def timeit(fn, reps=20, warm=3):
@@ -42,15 +42,11 @@ def main():
                             "ffn-in 4096x1024": (F, D, x), "ffn-out 1024x4096": (D, F, xf),
                             "logits 32768x1024": (V, D, x)}.items():
     w = bf(n, k)
-    os.environ["OS2S_SKINNY_VARIANT"] = "reg"
-    t = timeit(lambda: capi.gemm_skinny(inp, w))
-    os.environ["OS2S_SKINNY_VARIANT"] = "l64"
-    t1 = timeit(lambda: capi.gemm_skinny(inp, w))
-    os.environ["OS2S_SKINNY_VARIANT"] = "l32"
-    t3 = timeit(lambda: capi.gemm_skinny(inp, w))
-    os.environ["OS2S_SKINNY_VARIANT"] = "wide"
-    t4 = timeit(lambda: capi.gemm_skinny(inp, w))
-    del os.environ["OS2S_SKINNY_VARIANT"]
+    try:     # gemm_skinny.variant: 0 = reg, 2 = l64, 1 = l32, 3 = wide, -1 = by shape
+      t, t1, t3, t4 = [(_lib.set_option("gemm_skinny.variant", v), timeit(lambda: capi.gemm_skinny(inp, w)))[1]
+                       for v in (0, 2, 1, 3)]
+    finally:
+      _lib.set_option("gemm_skinny.variant", -1)
     t5 = timeit(lambda: capi.gemm_skinny(inp, w))
     t2 = timeit(lambda: lt_backend.matmul_lt(inp, w, b_is_t=True))
     print("gemm %-18s reg %6.1f  lds64 %6.1f  lds32 %6.1f  wide %6.1f  auto %6.1f  hipBLASLt %6.1f us  (W %.1f MB)"

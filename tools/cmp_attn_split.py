@@ -1,5 +1,5 @@
 """A/B of the location-attention kernels at bench-like shapes: run with OS2S_ATTN_SPLIT=0 and =1
-(the switch is read once per process), each run dumps its outputs; `cmp` compares the two dumps.
+(read when the library is loaded; the option attn_decoder.attn_split), each run dumps its outputs; `cmp` compares the two dumps.
 usage: cmp_attn_split.py run <out.pt> | cmp <a.pt> <b.pt>"""
 import math, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -14,7 +14,7 @@ if sys.argv[1] == "cmp":
                                                           "  <-- " if rel > 2e-2 else ""))
   sys.exit(0)
 
-from openseq2seq_amd import capi
+from openseq2seq_amd import _lib, capi
 dev = torch.device("cuda:0")
 B, T, S, L, H, M, U, mode, K, F = 32, 120, 200, 2, 1024, 1024, 128, 2, 32, 32
 g = torch.Generator().manual_seed(0)
@@ -47,4 +47,4 @@ torch.cuda.synchronize()
 dump = dict(y_top=dec.y_top, ctx=dec.ctx, align=dec.align_seq, cum=dec.cum_seq, dg0=out["dg"][0], dg1=out["dg"][1],
             dmem=out["dmem"], dkeys=out["dkeys"], dq=out["dq_seq"], dv=dv, dconv_w=dcw, dconv_b=dcb, ddense_w=ddw)
 torch.save({k: v.detach().float().cpu() for k, v in dump.items()}, sys.argv[2])
-print("saved", sys.argv[2], "split =", os.environ.get("OS2S_ATTN_SPLIT", "1"))
+print("saved", sys.argv[2], "split = %d" % _lib.get_option("attn_decoder.attn_split"))

@@ -14,4 +14,5 @@ for i in range(int(sys.argv[1]) if len(sys.argv) > 1 else 12):
   loss = model.train_step(batch)
   st = model.train_op.read_state()
   out.append("%.3f(s%g,k%d)" % (float(loss.cpu()[0]), st["loss_scale"], st["num_skipped"]))
-print("split=%s fp8=%s:" % (os.environ.get("OS2S_ATTN_SPLIT", "1"), fp8), " ".join(out))
+from openseq2seq_amd import _lib
+print("split=%d fp8=%s:" % (_lib.get_option("attn_decoder.attn_split"), fp8), " ".join(out))
