@@ -935,6 +935,31 @@ int os2s_rnn_layer_fwd_multi(os2s_stream_t stream, int cell, int ndir,
 int os2s_rnn_layer_bwd_multi(os2s_stream_t stream, int cell, int ndir,
                              const os2s_rnn_dir_bwd_t* dirs, const int32_t* lens, int B, int T,
                              int H, float forget_bias, void* workspace, size_t workspace_bytes);
+/* The same two calls with zoneout on the cell state (parts/rnns/zoneout.py:39-68; cell 2 = tf LSTMCell on the
+ * launch-per-step kernels only, cells 0 and 1: OS2S_ERR_UNSUPPORTED). y keeps the cell's OUTPUT, the new h;
+ * the state the next step reads and c_seq hold the zoned values, and the zoned h' is also saved to h_seq[d]
+ * (bf16 [B, T, H] per direction, zero past the lengths), the sequence the caller forms dWh from (shifted by
+ * one step in processing order) in place of y. mode 0: off; 1 (training): state' = m ? new : old per element,
+ * m ~ Bernoulli(1 - prob) from the counter hash with keep = 1 - prob over the direction's logical [B, T, H]
+ * tensor, indexed by the true time index t also in the reverse direction, seed_h[d] for h and seed_c[d] for
+ * c; 2 (eval / infer): state' = prob old + (1 - prob) new. Past a sample's length the state passes through
+ * as before. Backward: mode 1 only (mode 2: OS2S_ERR_UNSUPPORTED); the part of the state gradient that a
+ * mask sends past the cell rides in the workspace's dh / dc carries, and the unzoned c_new that tanh saw is
+ * c_seq[t] where m_c kept it, else recomputed from the saved gates and the previous c'. h_seq is not read
+ * by the backward call. */
+typedef struct os2s_rnn_zoneout {
+  float prob; int mode;
+  unsigned long long seed_h[2]; unsigned long long seed_c[2];
+  uint16_t* h_seq[2];
+} os2s_rnn_zoneout_t;
+int os2s_rnn_layer_fwd_zoneout(os2s_stream_t stream, int cell, int ndir,
+                               const os2s_rnn_dir_fwd_t* dirs, const os2s_rnn_zoneout_t* zo,
+                               const int32_t* lens, int B, int T, int H, float forget_bias,
+                               void* workspace, size_t workspace_bytes);
+int os2s_rnn_layer_bwd_zoneout(os2s_stream_t stream, int cell, int ndir,
+                               const os2s_rnn_dir_bwd_t* dirs, const os2s_rnn_zoneout_t* zo,
+                               const int32_t* lens, int B, int T, int H, float forget_bias,
+                               void* workspace, size_t workspace_bytes);
 
 /* ------------------------------------------------------------------------
  * Attention-RNN decoder loop: the AttentionWrapper cell that tf.contrib.seq2seq.dynamic_decode
@@ -972,6 +997,23 @@ int os2s_rnn_layer_bwd_multi(os2s_stream_t stream, int cell, int ndir,
  * Limits: H % 8 == 0, M % 8 == 0, U % 128 == 0 and <= 512; location-sensitive mode:
  * U == 128, loc_k <= 32. Luong with U != H has no query layer to bridge the two widths:
  * OS2S_ERR_UNSUPPORTED.
+ * Zoneout (parts/rnns/zoneout.py:39-68, wired per layer by parts/rnns/utils.py:68-89): the wrapped
+ * cell's OUTPUT stays the new h (what the layer above, the query layer and the output dropout read);
+ * only the STATE (c, h) the same cell reads at step t+1 is replaced. With p = zoneout_prob:
+ *   zoneout_mode 0: off (all-zero fields: every buffer as without them)
+ *   zoneout_mode 1 (training): state' = m ? new : old per element, m ~ Bernoulli(1 - p), no rescaling;
+ *     masks from the counter hash with keep = 1 - p over the logical [B, T, H] tensor of the layer,
+ *     zoneout_seed_h[l] for h and zoneout_seed_c[l] for c. The zoned h is an exact bf16 copy of
+ *     cat[l] row t, the zoned c an exact copy of c_seq[l] row t-1 (zeros at t = 0).
+ *   zoneout_mode 2 (eval / infer): state' = p old + (1 - p) new, in fp32, rounded once.
+ * cat[l] row t+1 and c_seq[l] row t then hold the ZONED state, y_top / the layer above's input the
+ * unzoned h, gates the activations as before. Backward (mode 1 only; mode 2: OS2S_ERR_UNSUPPORTED):
+ * with G / Gc the gradients reaching the zoned h'_t / c'_t, dh_new = dy terms + m_h G,
+ * dc_new = dh_new o (1 - tanh^2(c_new)) + m_c Gc, and (1 - m) G / (1 - m_c) Gc are carried to step
+ * t-1 (a second fp32 [B, H] carry per layer in the workspace). The unzoned c_new that tanh needs is
+ * c_seq[t] where m_c kept it and is otherwise RECOMPUTED from the saved gates and c_seq[t-1]
+ * (c_new = c'_{t-1} f + i g); no buffer is added. dWcat = dg^T cat as before: cat holds the zoned
+ * state, which is what the cell read. Steps t >= tgt_len[b] leave the sample untouched as before.
  * ---------------------------------------------------------------------- */
 typedef struct os2s_attn_decoder {
   int B, T, S, L, H, M, U;
@@ -1003,6 +1045,9 @@ typedef struct os2s_attn_decoder {
    * per time step); activations, accumulation and the backward pass are unchanged */
   const uint8_t* wcat8[2];
   const float* wcat8_scale[2];
+  /* zoneout on the cells' state (see above); all zero = off */
+  float zoneout_prob; int zoneout_mode;
+  unsigned long long zoneout_seed_h[2]; unsigned long long zoneout_seed_c[2];
 } os2s_attn_decoder_t;
 
 /* Backward through all T steps (t_begin = 0, t_end = T). Inputs: dy_top / dctx_ext = gradients
@@ -1034,7 +1079,8 @@ typedef struct os2s_attn_decoder_grads {
  *   finished |= stop_t > 0  (round(sigmoid) with mask_decoder_sequence); ends when every sample finished.
  * `loop` is the attention cell exactly as os2s_attn_decoder_fwd takes it (score_mode 2, parameters, keys /
  * values / src_len, zeroed sequence buffers, T = step capacity; gx0 is not read: the layer-0 input
- * projection is the first P columns of w0x; tgt_len must be NULL, attn_in_keep = out_keep = 1).
+ * projection is the first P columns of w0x; tgt_len must be NULL, attn_in_keep = out_keep = 1;
+ * zoneout_mode 0 or 2: the expectation blend of the cell state).
  * One step is four launches with no host interaction; the stop decision is device-resident:
  *   state int32 [4 + 2B], zeroed by the caller: [1] = number of steps after which every sample had
  *   finished (0 while running; launches enqueued past that point return at once), [2] finished count,

@@ -1412,15 +1412,34 @@ class _RnnDirBwd(_lib.ctypes.Structure):
               ("reverse", c_int)]
 
 
+class _RnnZoneout(_lib.ctypes.Structure):
+  """ctypes mirror of os2s_rnn_zoneout_t (include/os2s.h)."""
+  _fields_ = [("prob", c_float), ("mode", c_int), ("seed_h", _lib.ctypes.c_ulonglong * 2),
+              ("seed_c", _lib.ctypes.c_ulonglong * 2), ("h_seq", c_void_p * 2)]
+
+
 def _addr(t):
   return None if t is None else t.data_ptr()
 
 
-def rnn_layer_fwd_multi(cell, dirs, lens, H, forget_bias=1.0, save=True):
+def _rnn_zoneout(zoneout, nd, h_seqs=None):
+  """zoneout: dict(prob, mode, seeds_h, seeds_c) (one seed per direction) -> os2s_rnn_zoneout_t."""
+  z = _RnnZoneout()
+  z.prob, z.mode = float(zoneout["prob"]), int(zoneout["mode"])
+  for i in range(nd):
+    z.seed_h[i] = int(zoneout["seeds_h"][i]) & (2**64 - 1)
+    z.seed_c[i] = int(zoneout["seeds_c"][i]) & (2**64 - 1)
+    z.h_seq[i] = _addr(h_seqs[i]) if h_seqs is not None else None
+  return z
+
+
+def rnn_layer_fwd_multi(cell, dirs, lens, H, forget_bias=1.0, save=True, zoneout=None):
   """dirs: list (1 or 2) of dict(gx [B,T,G*H] bf16, wh [G*H,H] bf16, bh fp32|None, y view|None,
   reverse). All directions advance in one launch per time step. Returns a list of
   (y, gates|None, c_seq|None). A `y` may be a [B,T,H] channel-slice VIEW of a wider
-  [B,T,ld] tensor (both directions of a layer share one buffer)."""
+  [B,T,ld] tensor (both directions of a layer share one buffer).
+  zoneout: dict(prob, mode, seeds_h, seeds_c) (os2s_rnn_layer_fwd_zoneout, lstm_tf only): the entries gain a
+  fourth element, h_seq [B,T,H] bf16, the zoned state sequence."""
   B, T, GH = dirs[0]["gx"].shape
   dev = dirs[0]["gx"].device
   nd = len(dirs)
@@ -1445,6 +1464,12 @@ def rnn_layer_fwd_multi(cell, dirs, lens, H, forget_bias=1.0, save=True):
     outs.append((y, gates, c_seq))
   n = nd * int(_lib.C.os2s_rnn_fwd_workspace_bytes(B, H))
   ws = torch.empty((n,), dtype=torch.uint8, device=dev)
+  if zoneout is not None:
+    h_seqs = [torch.empty((B, T, H), dtype=torch.bfloat16, device=dev) for _ in range(nd)]
+    z = _rnn_zoneout(zoneout, nd, h_seqs)
+    _lib.C.os2s_rnn_layer_fwd_zoneout(_stream(), int(cell), nd, _lib.ctypes.byref(arr), _lib.ctypes.byref(z),
+                                      _ptr(lens, torch.int32, True), B, T, H, float(forget_bias), _ptr(ws), n)
+    return [o + (h,) for o, h in zip(outs, h_seqs)]
   _lib.C.os2s_rnn_layer_fwd_multi(_stream(), int(cell), nd, _lib.ctypes.byref(arr), _ptr(lens, torch.int32, True), B, T,
                                   H, float(forget_bias), _ptr(ws), n)
   return outs
@@ -1455,9 +1480,9 @@ def rnn_layer_fwd(cell, gx, wh, bh, lens, H, reverse, forget_bias=1.0, save=True
                              forget_bias, save)[0]
 
 
-def rnn_layer_bwd_multi(cell, dirs, lens, H, forget_bias=1.0):
+def rnn_layer_bwd_multi(cell, dirs, lens, H, forget_bias=1.0, zoneout=None):
   """dirs: list of dict(whT, dy, y, gates, c_seq, reverse); dy / y may be channel-slice views.
-  Returns a list of (dgx [B,T,G*H], dgr (GRU) or dgx again (LSTM))."""
+  Returns a list of (dgx [B,T,G*H], dgr (GRU) or dgx again (LSTM)). zoneout: the forward call's."""
   B, T, _ = dirs[0]["dy"].shape
   G = 3 if cell == CELL_GRU_CUDNN else 4
   dev = dirs[0]["dy"].device
@@ -1478,6 +1503,11 @@ def rnn_layer_bwd_multi(cell, dirs, lens, H, forget_bias=1.0):
     outs.append((dgx, dgr if dgr is not None else dgx))
   n = nd * int(_lib.C.os2s_rnn_bwd_workspace_bytes(B, H))
   ws = torch.empty((n,), dtype=torch.uint8, device=dev)
+  if zoneout is not None:
+    z = _rnn_zoneout(zoneout, nd)
+    _lib.C.os2s_rnn_layer_bwd_zoneout(_stream(), int(cell), nd, _lib.ctypes.byref(arr), _lib.ctypes.byref(z),
+                                      _ptr(lens, torch.int32, True), B, T, H, float(forget_bias), _ptr(ws), n)
+    return outs
   _lib.C.os2s_rnn_layer_bwd_multi(_stream(), int(cell), nd, _lib.ctypes.byref(arr), _ptr(lens, torch.int32, True), B, T,
                                   H, float(forget_bias), _ptr(ws), n)
   return outs
@@ -1508,6 +1538,7 @@ def conv2d_toeplitz_reduce(dwexp, Fi, Fo, sF, padF, dw):
 # attention-RNN decoder loop (NMT gnmt / Tacotron2)
 # --------------------------------------------------------------------------
 SCORE_BAHDANAU, SCORE_BAHDANAU_NORM, SCORE_LOCATION, SCORE_LUONG = 0, 1, 2, 3
+ZONEOUT_OFF, ZONEOUT_SAMPLE, ZONEOUT_BLEND = 0, 1, 2     # os2s_attn_decoder_t.zoneout_mode
 c_ull = _lib.ctypes.c_ulonglong
 
 
@@ -1525,7 +1556,9 @@ class _AttnDecoder(_lib.ctypes.Structure):
       ("cum_seq", c_void_p), ("align_seq", c_void_p), ("q_seq", c_void_p),
       ("y_top", c_void_p), ("y_top_bs", c_ll), ("y_top_ts", c_ll),
       ("ctx", c_void_p), ("ctx_bs", c_ll), ("ctx_ts", c_ll),
-      ("wcat8", c_void_p * 2), ("wcat8_scale", c_void_p * 2)]
+      ("wcat8", c_void_p * 2), ("wcat8_scale", c_void_p * 2),
+      ("zoneout_prob", c_float), ("zoneout_mode", c_int),
+      ("zoneout_seed_h", c_ull * 2), ("zoneout_seed_c", c_ull * 2)]
 
 
 def quantize_rows_e4m3(w2d, q=None, scale=None):
@@ -1552,12 +1585,17 @@ class _AttnDecoderGrads(_lib.ctypes.Structure):
 class AttnDecoder(object):
   """Owns the sequence buffers of one os2s_attn_decoder_{fwd,bwd} call (see include/os2s.h).
   `y_top` / `ctx` may be channel-slice views of a wider [B,T,ld] tensor (Tacotron's
-  concat(cell output, context) is then never materialised by a copy)."""
+  concat(cell output, context) is then never materialised by a copy).
+  zoneout_prob / zoneout_mode (ZONEOUT_SAMPLE: masks from zoneout_seeds_h / _c per layer, training;
+  ZONEOUT_BLEND: eval / infer, forward only): cat[l] row t + 1 and c_seq[l] row t then hold the zoned state."""
 
   def __init__(self, B, T, S, L, H, M, U, mode, device, use_bias=False, loc_k=0, loc_f=0,
                forget_bias=1.0, attn_in_keep=1.0, attn_in_seed=0, out_keep=1.0, out_seeds=(0, 0),
-               save=True, y_top=None, ctx=None):
+               save=True, y_top=None, ctx=None, zoneout_prob=0.0, zoneout_mode=ZONEOUT_OFF,
+               zoneout_seeds_h=(0, 0), zoneout_seeds_c=(0, 0)):
     self.dims = dict(B=B, T=T, S=S, L=L, H=H, M=M, U=U)
+    self.zoneout_prob, self.zoneout_mode = float(zoneout_prob), int(zoneout_mode)
+    self.zoneout_seeds_h, self.zoneout_seeds_c = tuple(zoneout_seeds_h), tuple(zoneout_seeds_c)
     self.mode, self.use_bias, self.loc_k, self.loc_f = mode, use_bias, loc_k, loc_f
     self.forget_bias, self.attn_in_keep, self.attn_in_seed = forget_bias, attn_in_keep, attn_in_seed
     self.out_keep, self.out_seeds = out_keep, tuple(out_seeds)
@@ -1596,8 +1634,11 @@ class AttnDecoder(object):
     d.t_begin, d.t_end = t_begin, t_end
     d.forget_bias, d.attn_in_keep, d.attn_in_seed = self.forget_bias, self.attn_in_keep, self.attn_in_seed
     d.out_keep = self.out_keep
+    d.zoneout_prob, d.zoneout_mode = self.zoneout_prob, self.zoneout_mode
     for l in range(2):
       d.out_seed[l] = self.out_seeds[l]
+      d.zoneout_seed_h[l] = int(self.zoneout_seeds_h[l]) & (2**64 - 1)
+      d.zoneout_seed_c[l] = int(self.zoneout_seeds_c[l]) & (2**64 - 1)
       d.wcat[l] = _addr(p["wcat"][l]) if l < L else None
       w8 = p.get("wcat8")
       d.wcat8[l] = _addr(w8[l][0]) if (w8 is not None and l < L) else None

@@ -23,6 +23,8 @@ def tacotron_gst_config(batch_size_per_gpu=32, max_steps=100000, style=True, dty
       "cnn_dropout_prob": 0.5, "rnn_dropout_prob": 0., "src_emb_size": 512,
       "conv_layers": [_conv(5, 512, False)] * 3, "activation_fn": "relu",
       "num_rnn_layers": 1, "rnn_cell_dim": 256, "rnn_unidirectional": False,
+      # zoneout_prob 0 as the reference's config has it (the cuDNN classes have none: > 0 needs use_cudnn_rnn False
+      # and rnn_type LSTMCell)
       "use_cudnn_rnn": True, "rnn_type": "CudnnLSTM", "zoneout_prob": 0.,
       "data_format": "channels_last",
   }
@@ -47,6 +49,8 @@ def tacotron_gst_config(batch_size_per_gpu=32, max_steps=100000, style=True, dty
       "encoder": Tacotron2Encoder, "encoder_params": enc,
       "decoder": Tacotron2Decoder,
       "decoder_params": {
+          # the reference's config regularises the decoder cells with output dropout; zoneout_prob > 0 needs
+          # dropout_prob 0 (a cell is wrapped in one or the other, parts/rnns/utils.py:71-77)
           "zoneout_prob": 0., "dropout_prob": 0.1, "attention_type": "location",
           "attention_layer_size": 128, "attention_bias": True, "decoder_cell_units": 1024,
           "decoder_cell_type": "LSTMCell", "decoder_layers": 2, "enable_prenet": True,

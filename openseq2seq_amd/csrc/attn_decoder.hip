@@ -49,6 +49,9 @@ struct AdCellFwd {
   long long y_bs, y_ts;
   float out_keep;
   unsigned long long out_seed;
+  int zo_mode;         // zoneout of the STATE stores (h_next, c_seq): 0 off, 1 sampled masks, 2 expectation blend
+  float zo_p;
+  unsigned long long zo_seed_h, zo_seed_c;
 };
 
 // One workgroup = 8 hidden units x 32 samples: the 32 tile rows are (gate, unit) pairs
@@ -107,12 +110,20 @@ __global__ __launch_bounds__(64 * kAdWaves) void ad_cell_fwd_kernel(AdCellFwd p)
   const float fg = sigmoidf_(pre[2] + p.forget_bias), og = sigmoidf_(pre[3]);
   const float cn = cprev * fg + ig * gg;
   float hn = tanhf(cn) * og;
-  p.c_seq[row * H + j] = cn;
+  // zoneout replaces the state the cell reads at step t + 1 (never the output y below)
+  float cst = cn;
+  bf16_t hst = f2bf(hn);
+  if (p.zo_mode) {
+    const bf16_t hprev = p.h_next[((long long)b * (p.T + 1) + p.t) * p.Kc + j];
+    zoneout_state(p.zo_mode, p.zo_p, p.zo_seed_h, p.zo_seed_c, (unsigned long long)row * H + j, hn, hprev, cn,
+                  cprev, hst, cst);
+  }
+  p.c_seq[row * H + j] = cst;
   if (p.gates) {
     bf16_t* gp = p.gates + row * (4 * H) + j;
     gp[0] = f2bf(ig); gp[H] = f2bf(fg); gp[2 * H] = f2bf(gg); gp[3 * H] = f2bf(og);
   }
-  p.h_next[((long long)b * (p.T + 1) + p.t + 1) * p.Kc + j] = f2bf(hn);
+  p.h_next[((long long)b * (p.T + 1) + p.t + 1) * p.Kc + j] = hst;
   if (p.out_keep < 1.f) {
     const unsigned long long idx = (unsigned long long)row * H + j;
     const uint32_t bits = dropout_bits8(p.out_seed, idx >> 3, p.out_keep);
@@ -1503,6 +1514,25 @@ static int ad_launch_fast_score_bwd(hipStream_t stream, const AdAttn& at, const 
 }
 
 // ------------------------------------------------------------------ cell backward
+// One (unit, sample) of the cell backward under zoneout (mode 1). g_h / g_c: the gradients reaching the ZONED
+// h'_t (dgB . WB^T + the carry) and c'_t (the carry); the mask sends each to the new value or past the cell to
+// step t - 1. c_seq[t] holds the zoned c': the unzoned c_new that tanh saw is c_seq[t] where the mask kept it
+// and is otherwise recomputed from the saved gates and c_seq[t-1].
+__device__ __forceinline__ void zoneout_cell_bwd(uint32_t mh, uint32_t mc, float dy, float g_h, float g_c, float ig,
+                                                 float fg, float gg, float og, float cz, float cprev, float& di,
+                                                 float& dj, float& df, float& dout, float& ndc, float& ndh) {
+  const float dh = dy + (mh ? g_h : 0.f);
+  const float cn = mc ? cz : cprev * fg + ig * gg;
+  const float tc = tanhf(cn);
+  const float dc = dh * og * (1.f - tc * tc) + (mc ? g_c : 0.f);
+  di = dc * gg * ig * (1.f - ig);
+  dj = dc * ig * (1.f - gg * gg);
+  df = dc * cprev * fg * (1.f - fg);
+  dout = dh * tc * og * (1.f - og);
+  ndc = dc * fg + (mc ? 0.f : g_c);
+  ndh = mh ? 0.f : g_h;
+}
+
 struct AdCellBwd {
   int B, T, H, t, last, KA, KB, KQ;
   float forget_bias;
@@ -1517,6 +1547,10 @@ struct AdCellBwd {
   bf16_t* dg_out;        // [B,T,4H]
   float out_keep;
   unsigned long long out_seed;
+  int zo;                // zoneout mode 1: c_seq holds the zoned state, dh_carry is live
+  float zo_keep;         // 1 - zoneout_prob
+  unsigned long long zo_seed_h, zo_seed_c;
+  float* dh_carry;       // [B,H] gradient of the zoned h' that its mask sent past the cell (zoneout only)
   float* part;           // split kernel: [H/32][B/32][kCbSplit] partial tiles
   int* ticket;           // split kernel: [H/32][B/32], zero before and after every launch
 };
@@ -1605,17 +1639,34 @@ __global__ __launch_bounds__(64 * kBwdWaves) void ad_cell_bwd_kernel(AdCellBwd p
   if (p.t > 0) cprev = *reinterpret_cast<const f32x4*>(p.c_seq + (row - 1) * H + j);
   f32x4 ndc;
   float dpre[4][4];
+  if (p.zo) {
+    f32x4 hcarry = {0.f, 0.f, 0.f, 0.f};
+    if (!p.last) hcarry = *reinterpret_cast<const f32x4*>(p.dh_carry + (long long)b * H + j);
+    const unsigned long long idx = (unsigned long long)row * H + j;
+    const uint32_t mh = dropout_bits8(p.zo_seed_h, idx >> 3, p.zo_keep) >> (j & 4);
+    const uint32_t mc = dropout_bits8(p.zo_seed_c, idx >> 3, p.zo_keep) >> (j & 4);
+    f32x4 ndh;
 #pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    const float dh = dyv[e] + accB[e];
-    const float ig = sv[0][e], fg = sv[1][e], gg = sv[2][e], og = sv[3][e];
-    const float tc = tanhf(cv[e]);
-    const float dc = dh * og * (1.f - tc * tc) + dcarry[e];
-    dpre[0][e] = dc * gg * ig * (1.f - ig);         // i
-    dpre[1][e] = dc * ig * (1.f - gg * gg);         // j
-    dpre[2][e] = dc * cprev[e] * fg * (1.f - fg);   // f
-    dpre[3][e] = dh * tc * og * (1.f - og);         // o
-    ndc[e] = dc * fg;
+    for (int e = 0; e < 4; ++e) {
+      float nc, nh;
+      zoneout_cell_bwd((mh >> e) & 1u, (mc >> e) & 1u, dyv[e], accB[e] + hcarry[e], dcarry[e], sv[0][e], sv[1][e],
+                       sv[2][e], sv[3][e], cv[e], cprev[e], dpre[0][e], dpre[1][e], dpre[2][e], dpre[3][e], nc, nh);
+      ndc[e] = nc; ndh[e] = nh;
+    }
+    *reinterpret_cast<f32x4*>(p.dh_carry + (long long)b * H + j) = ndh;
+  } else {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const float dh = dyv[e] + accB[e];
+      const float ig = sv[0][e], fg = sv[1][e], gg = sv[2][e], og = sv[3][e];
+      const float tc = tanhf(cv[e]);
+      const float dc = dh * og * (1.f - tc * tc) + dcarry[e];
+      dpre[0][e] = dc * gg * ig * (1.f - ig);         // i
+      dpre[1][e] = dc * ig * (1.f - gg * gg);         // j
+      dpre[2][e] = dc * cprev[e] * fg * (1.f - fg);   // f
+      dpre[3][e] = dh * tc * og * (1.f - og);         // o
+      ndc[e] = dc * fg;
+    }
   }
   *reinterpret_cast<f32x4*>(p.dc_carry + (long long)b * H + j) = ndc;
 #pragma unroll
@@ -1797,17 +1848,34 @@ __global__ __launch_bounds__(64 * kCbWaves) void ad_cell_bwd_split_kernel(AdCell
   }
   f32x4 ndc;
   float dpre[4][4];
+  if (p.zo) {
+    f32x4 hcarry = {0.f, 0.f, 0.f, 0.f};
+    if (!p.last) hcarry = *reinterpret_cast<const f32x4*>(p.dh_carry + (long long)brow * H + ej);
+    const unsigned long long idx = (unsigned long long)erow * H + ej;
+    const uint32_t mh = dropout_bits8(p.zo_seed_h, idx >> 3, p.zo_keep) >> (ej & 4);
+    const uint32_t mc = dropout_bits8(p.zo_seed_c, idx >> 3, p.zo_keep) >> (ej & 4);
+    f32x4 ndh;
 #pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    const float dh = dyv[e] + accb[e];
-    const float ig = sv[0][e], fg = sv[1][e], gg = sv[2][e], og = sv[3][e];
-    const float tc = tanhf(e_cv[e]);
-    const float dc = dh * og * (1.f - tc * tc) + e_dcarry[e];
-    dpre[0][e] = dc * gg * ig * (1.f - ig);         // i
-    dpre[1][e] = dc * ig * (1.f - gg * gg);         // j
-    dpre[2][e] = dc * e_cprev[e] * fg * (1.f - fg); // f
-    dpre[3][e] = dh * tc * og * (1.f - og);         // o
-    ndc[e] = dc * fg;
+    for (int e = 0; e < 4; ++e) {
+      float nc, nh;
+      zoneout_cell_bwd((mh >> e) & 1u, (mc >> e) & 1u, dyv[e], accb[e] + hcarry[e], e_dcarry[e], sv[0][e], sv[1][e],
+                       sv[2][e], sv[3][e], e_cv[e], e_cprev[e], dpre[0][e], dpre[1][e], dpre[2][e], dpre[3][e], nc, nh);
+      ndc[e] = nc; ndh[e] = nh;
+    }
+    *reinterpret_cast<f32x4*>(p.dh_carry + (long long)brow * H + ej) = ndh;
+  } else {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const float dh = dyv[e] + accb[e];
+      const float ig = sv[0][e], fg = sv[1][e], gg = sv[2][e], og = sv[3][e];
+      const float tc = tanhf(e_cv[e]);
+      const float dc = dh * og * (1.f - tc * tc) + e_dcarry[e];
+      dpre[0][e] = dc * gg * ig * (1.f - ig);         // i
+      dpre[1][e] = dc * ig * (1.f - gg * gg);         // j
+      dpre[2][e] = dc * e_cprev[e] * fg * (1.f - fg); // f
+      dpre[3][e] = dh * tc * og * (1.f - og);         // o
+      ndc[e] = dc * fg;
+    }
   }
   *reinterpret_cast<f32x4*>(p.dc_carry + (long long)brow * H + ej) = ndc;
 #pragma unroll
@@ -2001,6 +2069,8 @@ int os2s::ad_check(const os2s_attn_decoder_t* d) {
   OS2S_REQUIRE(d && d->B >= 1 && d->T >= 1 && d->S >= 1 && (d->L == 1 || d->L == 2));
   OS2S_REQUIRE(d->H % 8 == 0 && d->M % 8 == 0 && d->U % 128 == 0 && d->U <= 512);
   OS2S_REQUIRE(d->score_mode >= 0 && d->score_mode <= 3);
+  OS2S_REQUIRE(d->zoneout_mode >= 0 && d->zoneout_mode <= 2);
+  if (d->zoneout_mode) OS2S_REQUIRE(d->zoneout_prob >= 0.f && d->zoneout_prob < 1.f);
   if (d->score_mode == 3 && d->U != d->H) return OS2S_ERR_UNSUPPORTED;     // Luong: the query IS the cell output
   OS2S_REQUIRE(d->t_begin >= 0 && d->t_begin <= d->t_end && d->t_end <= d->T);
   OS2S_REQUIRE(d->wcat[0] && d->wq && d->v && d->keys && d->values && d->src_len && d->gx0);
@@ -2084,6 +2154,8 @@ extern "C" int os2s_attn_decoder_fwd(os2s_stream_t stream_, const os2s_attn_deco
       if (l == L - 1) { c.y = (bf16_t*)d->y_top; c.y_bs = d->y_top_bs; c.y_ts = d->y_top_ts; }
       else { c.y = (bf16_t*)d->cat[l + 1]; c.y_bs = (long long)(T + 1) * 2 * H; c.y_ts = 2 * H; }
       c.out_keep = d->out_keep; c.out_seed = d->out_seed[l];
+      c.zo_mode = d->zoneout_mode; c.zo_p = d->zoneout_prob;
+      c.zo_seed_h = d->zoneout_seed_h[l]; c.zo_seed_c = d->zoneout_seed_c[l];
       OS2S_LAUNCH(ad_cell_fwd_kernel, cgrid, dim3(64 * kAdWaves), 0, stream, c);
     }
     at.t = t;
@@ -2106,6 +2178,7 @@ extern "C" size_t os2s_attn_decoder_bwd_workspace_bytes(const os2s_attn_decoder_
   if (!d) return 0;
   const size_t B = d->B;
   size_t n = B * d->M + B * d->H + 2 * B * d->H + B * d->S + B * d->U;
+  if (d->zoneout_mode) n += 2 * B * d->H;      // the h carries of the two layers
   if (d->score_mode == 2) n += B * d->U + B * d->loc_k * d->U + (size_t)(d->loc_k + 1) * d->U;
   if (d->score_mode == 2) n += B * d->S + B * kLocParts * d->S;     // split kernels: dal, dcum_part
   // cell backward cut along the reduction: partial tiles + tickets per (32 units, 32 samples)
@@ -2131,6 +2204,7 @@ extern "C" int os2s_attn_decoder_bwd(os2s_stream_t stream_, const os2s_attn_deco
   if (d->score_mode == 2) OS2S_REQUIRE(gr->dconv_w && gr->dconv_b && gr->ddense_w);
   if (workspace_bytes < os2s_attn_decoder_bwd_workspace_bytes(d)) return OS2S_ERR_WORKSPACE;
   OS2S_REQUIRE(d->t_begin == 0 && d->t_end == d->T);
+  if (d->zoneout_mode == 2) return OS2S_ERR_UNSUPPORTED;     // the expectation blend is the eval / infer form
   hipStream_t stream = (hipStream_t)stream_;
   const size_t lds = attn_lds_bytes(d, true);
   const int B = d->B, T = d->T, H = d->H, M = d->M, L = d->L, U = d->U, S = d->S;
@@ -2140,6 +2214,8 @@ extern "C" int os2s_attn_decoder_bwd(os2s_stream_t stream_, const os2s_attn_deco
   float* dattn = ws; ws += (size_t)B * M;
   float* dhq = ws; ws += (size_t)B * H;
   float* dcc[2]; dcc[0] = ws; ws += (size_t)B * H; dcc[1] = ws; ws += (size_t)B * H;
+  float* dhc[2] = {nullptr, nullptr};          // zoneout: the carries of the zoned h' (next to those of c': 16-byte rows)
+  if (d->zoneout_mode) { dhc[0] = ws; ws += (size_t)B * H; dhc[1] = ws; ws += (size_t)B * H; }
   float* dcum = ws; ws += (size_t)B * S;
   float* dnv_acc = ws; ws += (size_t)B * U;
   float *dbd_acc = nullptr, *dwck_acc = nullptr, *unfold_tmp = nullptr;
@@ -2223,6 +2299,8 @@ extern "C" int os2s_attn_decoder_bwd(os2s_stream_t stream_, const os2s_attn_deco
       c.wBT = (const bf16_t*)gr->wcatT[l] + (long long)(l == 0 ? M : H) * GH; c.wBT_ld = GH; c.KB = (int)GH;
       c.gates = (const bf16_t*)d->gates[l]; c.c_seq = d->c_seq[l]; c.dc_carry = dcc[l];
       c.dg_out = (bf16_t*)gr->dg[l]; c.out_keep = d->out_keep; c.out_seed = d->out_seed[l];
+      c.zo = d->zoneout_mode == 1; c.zo_keep = 1.f - d->zoneout_prob;
+      c.zo_seed_h = d->zoneout_seed_h[l]; c.zo_seed_c = d->zoneout_seed_c[l]; c.dh_carry = dhc[l];
       c.part = cb_part; c.ticket = cb_ticket;
       if (csplit) {
         OS2S_LAUNCH(ad_cell_bwd_split_kernel, dim3(ceil_div(H, 32), kCbSplit, ceil_div(B, 32)), dim3(64 * kCbWaves), 0,

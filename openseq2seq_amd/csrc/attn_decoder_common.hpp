@@ -14,6 +14,24 @@ constexpr int kLocCtxParts = 8;
 
 __device__ __forceinline__ float tanh_fast(float x) { return 1.f - 2.f / (1.f + __expf(2.f * x)); }
 
+// Zoneout of one (unit, sample) of a cell's STATE stores (os2s_attn_decoder_t.zoneout_mode; the cell's output
+// is never touched). mode 1: Bernoulli(1 - p) masks from the counter hash over the layer's logical [B, T, H]
+// tensor (element idx), one seed for h and one for c; a zoned element is an exact copy of the old state.
+// mode 2: p old + (1 - p) new in fp32, rounded once. hst / cst come in holding the new state.
+__device__ __forceinline__ void zoneout_state(int mode, float p, unsigned long long seed_h, unsigned long long seed_c,
+                                              unsigned long long idx, float hn, bf16_t hprev, float cn, float cprev,
+                                              bf16_t& hst, float& cst) {
+  if (mode == 1) {
+    const float keep = 1.f - p;
+    const int sh = (int)(idx & 7);
+    if (!((dropout_bits8(seed_h, idx >> 3, keep) >> sh) & 1u)) hst = hprev;
+    if (!((dropout_bits8(seed_c, idx >> 3, keep) >> sh) & 1u)) cst = cprev;
+  } else {
+    hst = f2bf(p * bf2f(hprev) + (1.f - p) * hn);
+    cst = p * cprev + (1.f - p) * cn;
+  }
+}
+
 __device__ __forceinline__ float block_sum(float x, float* red) {
   x = wave_sum_dpp(x);
   __syncthreads();
@@ -96,6 +114,9 @@ struct TiLstm {
   const bf16_t* gx; long long ldgx;  // row b: gx + b * ldgx, [4H] (or null)
   bf16_t* gates; long long ldgates;  // row b: gates + b * ldgates, [4H] = i, f, g, o activations (or null)
   float out_keep; unsigned long long out_seed; long long drop_t, drop_T;   // element index ((b * T + t) * H + j)
+  // zoneout of the state stores (c_out, h1): mode 0 off; h_prev = the state row the step read (row b at
+  // h_prev + b * ldh1); mode 1 indexes its masks like the output dropout (drop_t, drop_T)
+  int zo_mode; float zo_p; unsigned long long zo_seed_h, zo_seed_c; const bf16_t* h_prev;
 };
 
 // attn_decoder.hip:

@@ -47,10 +47,14 @@ struct RnnDirFwd {
   bf16_t* gates;           // [B, T, Gs*H] saved activations (Gs = 4)
   float* c_seq;            // [B, T, H] saved cell states (LSTM)
   int reverse;
+  bf16_t* h_seq;           // [B, T, H] zoned state h' per time index (zoneout only)
+  unsigned long long zo_seed_h, zo_seed_c;
 };
 struct RnnStepArgs {
   int cell, B, T, H, G, step;
   float forget_bias;
+  int zo_mode;             // zoneout of the lstm_tf state (os2s_rnn_zoneout_t): 0 off, 1 sampled masks, 2 blend
+  float zo_p;
   const int32_t* lens;     // [B] or null
   RnnDirFwd d[2];          // blockIdx.z selects the direction
 };
@@ -110,6 +114,7 @@ __global__ __launch_bounds__(64 * kRnnWaves) void rnn_step_fwd_kernel(RnnStepArg
   if (!evalid) return;
   const int b = eb, j = ej;
   float hnew = hprev;      // past the sequence end the state passes through (dynamic_rnn)
+  float hstate = hprev;    // the state the next step reads: the output, unless zoneout replaces it
   if (t >= 0) {
     const long long row = (long long)b * pa.T + t;
     float sv[4];
@@ -129,17 +134,34 @@ __global__ __launch_bounds__(64 * kRnnWaves) void rnn_step_fwd_kernel(RnnStepArg
       const float cn = cprev * fg + ig * gg;
       hnew = tanhf(cn) * og;
       sv[0] = ig; sv[1] = fg; sv[2] = gg; sv[3] = og;
-      p.c32[(long long)b * H + j] = cn;
-      if (p.c_seq) p.c_seq[row * H + j] = cn;
+      float cst = cn;
+      hstate = hnew;
+      if (pa.zo_mode) {
+        // zoneout: y below keeps the new h; the state (h32 / h_next16 / c32, c_seq, h_seq) is replaced. Masks index
+        // the logical [B, T, H] tensor of the direction by the TRUE time index t, also when it runs in reverse
+        if (pa.zo_mode == 1) {
+          const unsigned long long idx = (unsigned long long)row * H + j;
+          const float keep = 1.f - pa.zo_p;
+          if (!((dropout_bits8(p.zo_seed_h, idx >> 3, keep) >> (j & 7)) & 1u)) hstate = hprev;
+          if (!((dropout_bits8(p.zo_seed_c, idx >> 3, keep) >> (j & 7)) & 1u)) cst = cprev;
+        } else {
+          hstate = pa.zo_p * hprev + (1.f - pa.zo_p) * hnew;
+          cst = pa.zo_p * cprev + (1.f - pa.zo_p) * cn;
+        }
+        p.h_seq[row * H + j] = f2bf(hstate);
+      }
+      p.c32[(long long)b * H + j] = cst;
+      if (p.c_seq) p.c_seq[row * H + j] = cst;
     }
+    if (pa.cell == kGruCudnn) hstate = hnew;
     if (p.gates) {
       bf16_t* gp = p.gates + row * (4 * H) + j;
       gp[0] = f2bf(sv[0]); gp[H] = f2bf(sv[1]); gp[2 * H] = f2bf(sv[2]); gp[3 * H] = f2bf(sv[3]);
     }
     p.y[row * p.ldy + j] = f2bf(hnew);
   }
-  p.h32[(long long)b * H + j] = hnew;
-  p.h_next16[(long long)b * H + j] = f2bf(hnew);
+  p.h32[(long long)b * H + j] = hstate;
+  p.h_next16[(long long)b * H + j] = f2bf(hstate);
 }
 
 // ---------------------------------------------------------------------------
@@ -161,10 +183,13 @@ struct RnnDirBwd {
   float* dh_carry;          // [B, H] fp32: direct (non-matmul) part of dh flowing to s-1
   float* dc_carry;          // [B, H] fp32 (LSTM)
   int reverse;
+  unsigned long long zo_seed_h, zo_seed_c;
 };
 struct RnnBwdArgs {
   int cell, B, T, H, G, step, first;
   float forget_bias;
+  int zo;                   // zoneout mode 1 (lstm_tf): c_seq holds the zoned state
+  float zo_keep;            // 1 - zoneout probability
   const int32_t* lens;
   RnnDirBwd d[2];
 };
@@ -265,19 +290,37 @@ __global__ __launch_bounds__(64 * kRnnWaves) void rnn_step_bwd_kernel(RnnBwdArgs
       }
     } else {
       f32x4 ndc;
+      // zoneout (mode 1): of the gradient reaching the zoned h'_t (dg_next . Wh + carry) and c'_t (dcarry) the mask
+      // sends each element to the new value or past the cell to step s - 1 (the carries). c_seq holds the zoned
+      // c': the unzoned c_new that tanh saw is c_seq[t] where the mask kept it, else recomputed from the saved
+      // gates and the previous c'
+      uint32_t mh = 0xfu, mc = 0xfu;
+      if (pa.zo) {
+        const unsigned long long idx = ((unsigned long long)b * pa.T + t) * H + j;
+        mh = dropout_bits8(p.zo_seed_h, idx >> 3, pa.zo_keep) >> (j & 4);
+        mc = dropout_bits8(p.zo_seed_c, idx >> 3, pa.zo_keep) >> (j & 4);
+        dh[0] = bflo(dyv[0]); dh[1] = bfhi(dyv[0]); dh[2] = bflo(dyv[1]); dh[3] = bfhi(dyv[1]);
+      }
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         const float ig = sv[0][e], fg = sv[1][e], gg = sv[2][e], og = sv[3][e];
-        const float tc = tanhf(cv[e]);
+        float cnew = cv[e], zc = 0.f;
+        ncarry[e] = 0.f;
+        if (pa.zo) {
+          const float gh = acc[0][e] + carry[e];
+          if ((mh >> e) & 1u) dh[e] += gh; else ncarry[e] = gh;
+          if (!((mc >> e) & 1u)) { cnew = cprev[e] * fg + ig * gg; zc = dcarry[e]; dcarry[e] = 0.f; }
+        }
+        const float tc = tanhf(cnew);
         const float dox = dh[e] * tc * og * (1.f - og);
         const float dc = dh[e] * og * (1.f - tc * tc) + dcarry[e];
         const float dix = dc * gg * ig * (1.f - ig);
         const float dfx = dc * cprev[e] * fg * (1.f - fg);
         const float dgx_ = dc * ig * (1.f - gg * gg);
         ndc[e] = dc * fg;
+        if (pa.zo) ndc[e] += zc;
         if (pa.cell == kLstmCudnn) { dpre[0][e] = dix; dpre[1][e] = dfx; dpre[2][e] = dgx_; dpre[3 % G][e] = dox; }
         else { dpre[0][e] = dix; dpre[1][e] = dgx_; dpre[2][e] = dfx; dpre[3 % G][e] = dox; }
-        ncarry[e] = 0.f;
       }
       *reinterpret_cast<f32x4*>(p.dc_carry + (long long)b * H + j) = ndc;
     }
@@ -324,10 +367,20 @@ extern "C" size_t os2s_rnn_fwd_workspace_bytes(int B, int H) {
   return rnn_fwd_state_bytes(B, H) + os2s_gru_xcd_workspace_bytes(B, H) + 256;
 }
 
-extern "C" int os2s_rnn_layer_fwd_multi(os2s_stream_t stream_, int cell, int ndir,
-                                        const os2s_rnn_dir_fwd_t* dirs, const int32_t* lens,
-                                        int B, int T, int H, float forget_bias, void* workspace,
-                                        size_t workspace_bytes) {
+// zoneout descriptor of the *_zoneout entry points: lstm_tf only, valid fields, something to do
+static int rnn_zoneout_check(int cell, int ndir, const os2s_rnn_zoneout_t* zo, bool fwd) {
+  OS2S_REQUIRE(zo && zo->mode >= 0 && zo->mode <= 2);
+  if (cell != kLstmTf) return OS2S_ERR_UNSUPPORTED;
+  if (zo->mode == 0) return OS2S_OK;
+  OS2S_REQUIRE(zo->prob >= 0.f && zo->prob < 1.f);
+  if (fwd)
+    for (int d = 0; d < ndir; ++d) OS2S_REQUIRE(zo->h_seq[d]);
+  return OS2S_OK;
+}
+
+static int rnn_layer_fwd_impl(os2s_stream_t stream_, int cell, int ndir, const os2s_rnn_dir_fwd_t* dirs,
+                              const os2s_rnn_zoneout_t* zo, const int32_t* lens, int B, int T, int H,
+                              float forget_bias, void* workspace, size_t workspace_bytes) {
   OS2S_REQUIRE(dirs && workspace && (ndir == 1 || ndir == 2));
   OS2S_REQUIRE(B >= 1 && T >= 1 && H >= 8 && H % 8 == 0 && cell >= 0 && cell <= 2);
   const size_t per_dir = os2s_rnn_fwd_workspace_bytes(B, H);
@@ -337,6 +390,7 @@ extern "C" int os2s_rnn_layer_fwd_multi(os2s_stream_t stream_, int cell, int ndi
   RnnStepArgs a;
   a.cell = cell; a.B = B; a.T = T; a.H = H; a.G = rnn_gates(cell);
   a.forget_bias = forget_bias; a.lens = lens;
+  a.zo_mode = zo ? zo->mode : 0; a.zo_p = zo ? zo->prob : 0.f;
   bf16_t* h16[2][2];
   for (int d = 0; d < ndir; ++d) {
     const os2s_rnn_dir_fwd_t& s = dirs[d];
@@ -350,6 +404,11 @@ extern "C" int os2s_rnn_layer_fwd_multi(os2s_stream_t stream_, int cell, int ndi
     k.c32 = (float*)ws;
     k.y = (bf16_t*)s.y; k.ldy = s.ldy; k.gates = (bf16_t*)s.gates; k.c_seq = s.c_seq;
     k.reverse = s.reverse;
+    k.h_seq = nullptr; k.zo_seed_h = k.zo_seed_c = 0;
+    if (a.zo_mode) {
+      k.h_seq = (bf16_t*)zo->h_seq[d]; k.zo_seed_h = zo->seed_h[d]; k.zo_seed_c = zo->seed_c[d];
+      if (lens && hipMemsetAsync(k.h_seq, 0, (size_t)B * T * H * 2, stream) != hipSuccess) return OS2S_ERR_LAUNCH;
+    }
     if (lens) {   // outputs past the sequence ends are zero (rows are ldy apart)
       if (hipMemset2DAsync(s.y, (size_t)s.ldy * 2, 0, (size_t)H * 2, (size_t)B * T, stream) != hipSuccess)
         return OS2S_ERR_LAUNCH;
@@ -381,6 +440,23 @@ extern "C" int os2s_rnn_layer_fwd_multi(os2s_stream_t stream_, int cell, int ndi
   return OS2S_OK;
 }
 
+extern "C" int os2s_rnn_layer_fwd_multi(os2s_stream_t stream_, int cell, int ndir,
+                                        const os2s_rnn_dir_fwd_t* dirs, const int32_t* lens,
+                                        int B, int T, int H, float forget_bias, void* workspace,
+                                        size_t workspace_bytes) {
+  return rnn_layer_fwd_impl(stream_, cell, ndir, dirs, nullptr, lens, B, T, H, forget_bias, workspace, workspace_bytes);
+}
+
+extern "C" int os2s_rnn_layer_fwd_zoneout(os2s_stream_t stream_, int cell, int ndir,
+                                          const os2s_rnn_dir_fwd_t* dirs, const os2s_rnn_zoneout_t* zo,
+                                          const int32_t* lens, int B, int T, int H, float forget_bias,
+                                          void* workspace, size_t workspace_bytes) {
+  OS2S_REQUIRE(ndir == 1 || ndir == 2);
+  const int rc = rnn_zoneout_check(cell, ndir, zo, true);
+  if (rc != OS2S_OK) return rc;
+  return rnn_layer_fwd_impl(stream_, cell, ndir, dirs, zo, lens, B, T, H, forget_bias, workspace, workspace_bytes);
+}
+
 extern "C" int os2s_rnn_layer_fwd(os2s_stream_t stream_, int cell, const uint16_t* gx,
                                   const uint16_t* wh, const float* bh, const int32_t* lens, int B,
                                   int T, int H, int reverse, float forget_bias, uint16_t* y,
@@ -400,10 +476,9 @@ extern "C" size_t os2s_rnn_bwd_workspace_bytes(int B, int H) {
   return rnn_bwd_state_bytes(B, H) + os2s_gru_xcd_bwd_workspace_bytes(B, H) + 256;
 }
 
-extern "C" int os2s_rnn_layer_bwd_multi(os2s_stream_t stream_, int cell, int ndir,
-                                        const os2s_rnn_dir_bwd_t* dirs, const int32_t* lens,
-                                        int B, int T, int H, float forget_bias, void* workspace,
-                                        size_t workspace_bytes) {
+static int rnn_layer_bwd_impl(os2s_stream_t stream_, int cell, int ndir, const os2s_rnn_dir_bwd_t* dirs,
+                              const os2s_rnn_zoneout_t* zo, const int32_t* lens, int B, int T, int H,
+                              float forget_bias, void* workspace, size_t workspace_bytes) {
   OS2S_REQUIRE(dirs && workspace && (ndir == 1 || ndir == 2));
   OS2S_REQUIRE(B >= 1 && T >= 1 && H % 8 == 0 && cell >= 0 && cell <= 2);
   const size_t per_dir = os2s_rnn_bwd_workspace_bytes(B, H);
@@ -413,6 +488,7 @@ extern "C" int os2s_rnn_layer_bwd_multi(os2s_stream_t stream_, int cell, int ndi
   if (hipMemsetAsync(workspace, 0, per_dir * ndir, stream) != hipSuccess) return OS2S_ERR_LAUNCH;
   RnnBwdArgs a;
   a.cell = cell; a.B = B; a.T = T; a.H = H; a.G = G; a.lens = lens; a.forget_bias = forget_bias;
+  a.zo = zo && zo->mode == 1; a.zo_keep = zo ? 1.f - zo->prob : 1.f;
   bf16_t* dg[2][2];
   for (int d = 0; d < ndir; ++d) {
     const os2s_rnn_dir_bwd_t& s = dirs[d];
@@ -428,6 +504,7 @@ extern "C" int os2s_rnn_layer_bwd_multi(os2s_stream_t stream_, int cell, int ndi
     k.dh_carry = (float*)ws; ws += (size_t)B * H * 4;
     k.dc_carry = (float*)ws;
     k.reverse = s.reverse;
+    k.zo_seed_h = a.zo ? zo->seed_h[d] : 0; k.zo_seed_c = a.zo ? zo->seed_c[d] : 0;
     // gate gradients of frames past the sequence ends are zero
     if (hipMemsetAsync(s.dgx, 0, (size_t)B * T * G * H * 2, stream) != hipSuccess) return OS2S_ERR_LAUNCH;
     if (s.dgr && hipMemsetAsync(s.dgr, 0, (size_t)B * T * G * H * 2, stream) != hipSuccess)
@@ -456,6 +533,24 @@ extern "C" int os2s_rnn_layer_bwd_multi(os2s_stream_t stream_, int cell, int ndi
     else { OS2S_LAUNCH((rnn_step_bwd_kernel<4, 32>), grid, dim3(64 * kRnnWaves), 0, stream, a); }
   }
   return OS2S_OK;
+}
+
+extern "C" int os2s_rnn_layer_bwd_multi(os2s_stream_t stream_, int cell, int ndir,
+                                        const os2s_rnn_dir_bwd_t* dirs, const int32_t* lens,
+                                        int B, int T, int H, float forget_bias, void* workspace,
+                                        size_t workspace_bytes) {
+  return rnn_layer_bwd_impl(stream_, cell, ndir, dirs, nullptr, lens, B, T, H, forget_bias, workspace, workspace_bytes);
+}
+
+extern "C" int os2s_rnn_layer_bwd_zoneout(os2s_stream_t stream_, int cell, int ndir,
+                                          const os2s_rnn_dir_bwd_t* dirs, const os2s_rnn_zoneout_t* zo,
+                                          const int32_t* lens, int B, int T, int H, float forget_bias,
+                                          void* workspace, size_t workspace_bytes) {
+  OS2S_REQUIRE(ndir == 1 || ndir == 2);
+  const int rc = rnn_zoneout_check(cell, ndir, zo, false);
+  if (rc != OS2S_OK) return rc;
+  if (zo->mode == 2) return OS2S_ERR_UNSUPPORTED;     // the expectation blend is the eval / infer form
+  return rnn_layer_bwd_impl(stream_, cell, ndir, dirs, zo, lens, B, T, H, forget_bias, workspace, workspace_bytes);
 }
 
 extern "C" int os2s_rnn_layer_bwd(os2s_stream_t stream_, int cell, const uint16_t* whT,

@@ -192,12 +192,19 @@ __global__ __launch_bounds__(64 * kTiWaves) void ti_lstm_kernel(TiLstm p) {
   const float fg = sigmoidf_(pre[2] + p.forget_bias), og = sigmoidf_(pre[3]);
   const float cn = e_c * fg + ig * gg;
   float hv = tanh_fast(cn) * og;
-  p.c_out[(long long)e_b * p.ldc_out + e_j] = cn;
+  float cst = cn;
+  bf16_t hst = f2bf(hv);
+  if (p.zo_mode) {   // uniform. Zoneout replaces the state stores only (c_out, h1); h2 stays the cell's output
+    const unsigned long long idx = ((unsigned long long)e_b * p.drop_T + p.drop_t) * H + e_j;
+    zoneout_state(p.zo_mode, p.zo_p, p.zo_seed_h, p.zo_seed_c, idx, hv, p.h_prev[(long long)e_b * p.ldh1 + e_j], cn,
+                  e_c, hst, cst);
+  }
+  p.c_out[(long long)e_b * p.ldc_out + e_j] = cst;
   if (p.gates) {
     bf16_t* gp = p.gates + (long long)e_b * p.ldgates + e_j;
     gp[0] = f2bf(ig); gp[H] = f2bf(fg); gp[2 * H] = f2bf(gg); gp[3 * H] = f2bf(og);
   }
-  if (p.h1) p.h1[(long long)e_b * p.ldh1 + e_j] = f2bf(hv);
+  if (p.h1) p.h1[(long long)e_b * p.ldh1 + e_j] = hst;
   if (p.out_keep < 1.f) {
     const unsigned long long idx = ((unsigned long long)e_b * p.drop_T + p.drop_t) * H + e_j;
     const uint32_t bits = dropout_bits8(p.out_seed, idx >> 3, p.out_keep);
@@ -755,7 +762,8 @@ static int ti_check(const os2s_tacotron_infer_t* x) {
   OS2S_REQUIRE(x->prenet_keep > 0.f && x->prenet_keep <= 1.f);
   // what the step kernels are built for (anything else: the caller drives os2s_attn_decoder_fwd step by step)
   if (d->score_mode != 2 || !loc_split(d) || d->B > 32 || d->H % 64 || d->M % 64 || x->P % 64 || x->n_mel % 8 ||
-      x->n_mel > 128 || x->P > 1024 || d->attn_in_keep < 1.f || d->out_keep < 1.f || d->tgt_len)
+      x->n_mel > 128 || x->P > 1024 || d->attn_in_keep < 1.f || d->out_keep < 1.f || d->tgt_len ||
+      d->zoneout_mode == 1)      // sampled masks belong to training; decoding blends (mode 2) or is off
     return OS2S_ERR_UNSUPPORTED;
   if (x->P > 256 || x->n_mel / 8 > kTiW1Pieces * (kTiCtxThreads / x->P) || x->n_mel > 16 * kAttnWaves ||
       d->H > 1024 || !x->mh || d->loc_k > 32 || ti_scores_lds_floats(d->S) * sizeof(float) > 64 * 1024)
@@ -831,6 +839,8 @@ static void ti_fill_cell_state(TiLstm& c, const os2s_attn_decoder_t* d, int l, i
   c.c_prev = t > 0 ? d->c_seq[l] + (long long)(t - 1) * H : nullptr; c.ldc_prev = (long long)T * H;
   c.c_out = d->c_seq[l] + (long long)t * H; c.ldc_out = (long long)T * H;
   c.h1 = (bf16_t*)d->cat[l] + (long long)(t + 1) * Kc + (l == 0 ? M : H); c.ldh1 = (long long)(T + 1) * Kc;
+  c.zo_mode = d->zoneout_mode; c.zo_p = d->zoneout_prob; c.h_prev = c.h1 - Kc;
+  c.zo_seed_h = d->zoneout_seed_h[l]; c.zo_seed_c = d->zoneout_seed_c[l];
   if (l == L - 1) { c.h2 = (bf16_t*)d->y_top + (long long)t * d->y_top_ts; c.ldh2 = d->y_top_bs; }
   else { c.h2 = (bf16_t*)d->cat[l + 1] + (long long)t * 2 * H; c.ldh2 = (long long)(T + 1) * 2 * H; }
 }

@@ -86,11 +86,18 @@ class AttentionCell(object):
 
   def _new_loop(self, B, T, S, dev, training, attn_in_keep, out_keep, seeds, y_top=None, ctx=None):
     m = lambda p: None if p is None else p.master
+    # zoneout (ZoneoutWrapper around every cell of the stack): sampled masks when training, the expectation
+    # blend otherwise. The seeds are drawn only then, so that a loop without zoneout sees the seeds it always saw
+    zp = float(getattr(self, "zoneout_prob", 0.0))
+    zo = dict(zoneout_prob=zp, zoneout_mode=capi.ZONEOUT_SAMPLE if training else capi.ZONEOUT_BLEND) if zp > 0. else {}
     dec = capi.AttnDecoder(B, T, S, self.L, self.H, self.M, self.U, self.mode, dev,
                            use_bias=self.use_bias, loc_k=self.loc_k, loc_f=self.loc_f,
                            forget_bias=self.forget_bias, attn_in_keep=attn_in_keep,
                            attn_in_seed=seeds.next(), out_keep=out_keep,
-                           out_seeds=(seeds.next(), seeds.next()), save=training, y_top=y_top, ctx=ctx)
+                           out_seeds=(seeds.next(), seeds.next()), save=training, y_top=y_top, ctx=ctx, **zo)
+    if zo and training:
+      dec.zoneout_seeds_h = (seeds.next(), seeds.next())
+      dec.zoneout_seeds_c = (seeds.next(), seeds.next())
     GH = 4 * self.H
     dec.set_params([w.w16.view(GH, -1) for w in self.wcat],
                    self._eye if self.luong else self.w_q.w16.view(self.U, self.H),

@@ -61,8 +61,12 @@ class Tacotron2Decoder(Decoder):
     p = self.params
     if p['attention_type'] != 'location':
       raise NotImplementedError("attention_type %r (location-sensitive attention is built)" % (p['attention_type'],))
-    if p.get('zoneout_prob', 0.) != 0.:
-      raise NotImplementedError("zoneout")
+    zp = p.get('zoneout_prob', 0.)
+    if not 0. <= zp < 1.:
+      raise ValueError("zoneout_prob must be in [0, 1), got %r" % (zp,))
+    if zp > 0. and p.get('dropout_prob', 0.1) > 0.:
+      # parts/rnns/utils.py:71-77: a cell is wrapped in zoneout OR output dropout, never both
+      raise ValueError("zoneout_prob > 0 needs dropout_prob = 0 (the default dropout_prob is 0.1)")
     if not p.get('enable_prenet', True) or not p.get('enable_postnet', True):
       raise NotImplementedError("decoder without pre-net / post-net")
     if p['decoder_layers'] not in (1, 2):
@@ -101,6 +105,7 @@ class Tacotron2Decoder(Decoder):
                               p['attention_layer_size'], p['decoder_layers'], capi.SCORE_LOCATION,
                               1.0, use_bias=p.get('attention_bias', False), loc_k=32, loc_f=32)
     self.cell.fp8_weights = bool(p.get('fp8_weights', False))
+    self.cell.zoneout_prob = float(p.get('zoneout_prob', 0.))
     for w in [self.cell.w_in, self.cell.w_mem, self.cell.w_q] + self.cell.wcat:
       w.l2 = l2
     self.out_proj = Dense(store, scope + "/output_proj", H + self.M, self.n_mel, True)

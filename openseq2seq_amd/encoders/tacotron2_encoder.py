@@ -37,8 +37,13 @@ class Tacotron2Encoder(Encoder):
   def __init__(self, params, model, name="tacotron2_encoder", mode='train'):
     super(Tacotron2Encoder, self).__init__(params, model, name, mode)
     p = self.params
-    if p.get('zoneout_prob', 0.) != 0.:
-      raise NotImplementedError("zoneout")
+    zp = p.get('zoneout_prob', 0.)
+    if not 0. <= zp < 1.:
+      raise ValueError("zoneout_prob must be in [0, 1), got %r" % (zp,))
+    if zp > 0. and p['use_cudnn_rnn'] and mode != "infer":
+      # tacotron2_encoder.py:225-246: the cuDNN classes have no zoneout; infer builds plain compatible cells
+      raise ValueError("Zoneout is currently not supported for cudnn rnn classes")
+    self._zoneout = float(zp) if not p['use_cudnn_rnn'] else 0.
     if p['rnn_unidirectional']:
       raise NotImplementedError("unidirectional encoder RNN")
     rt = p['rnn_type'] if isinstance(p['rnn_type'], str) else getattr(p['rnn_type'], "__name__", "")
@@ -122,15 +127,21 @@ class Tacotron2Encoder(Encoder):
     rnn_lens = None if (training and self._cudnn_cell) else text_len
     for l, dirs in enumerate(self.rnn):
       last = l == len(self.rnn) - 1
+      zo = None
+      if self._zoneout > 0.:   # every cell of both stacks is wrapped on its own (parts/rnns/utils.py:68-89)
+        zo = dict(prob=self._zoneout, mode=capi.ZONEOUT_SAMPLE if training else capi.ZONEOUT_BLEND,
+                  seeds_h=(0, 0), seeds_c=(0, 0))
+        if training:
+          zo["seeds_h"], zo["seeds_c"] = (seeds.next(), seeds.next()), (seeds.next(), seeds.next())
       if last:
         views = [out.data[:, :, d * H:(d + 1) * H] for d in range(2)]
         fns = [(lambda o=out, d=d: o.grad[:, :, d * H:(d + 1) * H]) for d in range(2)]
-        rnn_directions_forward(dirs, [x], rnn_lens, tape, views, fns)
+        rnn_directions_forward(dirs, [x], rnn_lens, tape, views, fns, zoneout=zo)
       else:
         ybuf = Act(torch.empty((B, S2, 2 * H), dtype=torch.bfloat16, device=text.device), None)
         rnn_directions_forward(
             dirs, [x], rnn_lens, tape, [ybuf.data[:, :, d * H:(d + 1) * H] for d in range(2)],
-            [(lambda o=ybuf, d=d: o.grad[:, :, d * H:(d + 1) * H]) for d in range(2)])
+            [(lambda o=ybuf, d=d: o.grad[:, :, d * H:(d + 1) * H]) for d in range(2)], zoneout=zo)
         x = ybuf
     if not self.rnn:
       out.data[:, :, :self.text_dim].copy_(x.data)

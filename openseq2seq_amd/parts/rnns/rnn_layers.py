@@ -68,8 +68,11 @@ class RNNDirection(object):
   def params(self):
     return [self.wh, self.bx] + self.wx + ([self.bh] if self.bh is not None else [])
 
-  def weight_backward(self, xs, lens, y, dgx, dgr):
-    """dX, dWx, dWh and the bias gradients from the saved gate gradients."""
+  def weight_backward(self, xs, lens, y, dgx, dgr, h_seq=None):
+    """dX, dWx, dWh and the bias gradients from the saved gate gradients. h_seq: under zoneout the state
+    sequence the recurrent product read (the zoned h'), which then stands in for the outputs y in dWh."""
+    if h_seq is not None:
+      y = h_seq
     B, T, _ = xs[0].data.shape
     H, GH = self.H, self.G * self.H
     d2 = dgx.view(B * T, GH)
@@ -114,10 +117,12 @@ class RNNDirection(object):
                                   [dy_view_fn] if dy_view_fn is not None else None)[0]
 
 
-def rnn_directions_forward(dirs, xs, lens, tape, y_views=None, dy_view_fns=None):
+def rnn_directions_forward(dirs, xs, lens, tape, y_views=None, dy_view_fns=None, zoneout=None):
   """Runs 1 or 2 `RNNDirection`s of the same cell/size with ONE kernel launch per time step
   (os2s_rnn_layer_{fwd,bwd}_multi). `xs` is a list of Act shared by the directions, or one
-  such list per direction. Returns one Act per direction."""
+  such list per direction. Returns one Act per direction.
+  zoneout: dict(prob, mode, seeds_h, seeds_c) with one seed per direction (ZoneoutWrapper around each
+  direction's cell, lstm_tf only; capi.ZONEOUT_SAMPLE when training, capi.ZONEOUT_BLEND otherwise)."""
   d0 = dirs[0]
   H = d0.H
   training = tape is not None
@@ -128,7 +133,7 @@ def rnn_directions_forward(dirs, xs, lens, tape, y_views=None, dy_view_fns=None)
       d0.cell, [dict(gx=gx, wh=d.wh.w16.view(d.G * H, H),
                      bh=d.bh.master if d.bh is not None else None, y=yv, reverse=d.reverse)
                 for d, gx, yv in zip(dirs, gxs, y_views)],
-      lens, H, d0.forget_bias, save=training)
+      lens, H, d0.forget_bias, save=training, zoneout=zoneout)
   outs = [Act(r[0], lens) for r in res]
   if not training:
     return outs
@@ -139,9 +144,9 @@ def rnn_directions_forward(dirs, xs, lens, tape, y_views=None, dy_view_fns=None)
     grads = capi.rnn_layer_bwd_multi(
         d0.cell, [dict(whT=d.wh.wt16.view(H, d.G * H), dy=dy, y=r[0], gates=r[1], c_seq=r[2],
                        reverse=d.reverse) for d, dy, r in zip(dirs, dys, res)],
-        lens, H, d0.forget_bias)
+        lens, H, d0.forget_bias, zoneout=zoneout)
     for d, x, r, (dgx, dgr) in zip(dirs, xs_per, res, grads):
-      d.weight_backward(x, lens, r[0], dgx, dgr)
+      d.weight_backward(x, lens, r[0], dgx, dgr, h_seq=r[3] if zoneout is not None else None)
     for o in outs:
       o.grad = None
 
