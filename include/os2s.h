@@ -962,6 +962,55 @@ int os2s_rnn_layer_bwd_zoneout(os2s_stream_t stream, int cell, int ndir,
                                void* workspace, size_t workspace_bytes);
 
 /* ------------------------------------------------------------------------
+ * LayerNorm-LSTM layer of the LSTM language model (csrc/lnlstm.hip): the recurrence of
+ * WeightDropLayerNormBasicLSTMCell with layer_norm=True (parts/rnns/weight_drop.py:140-166; no bias, gate order
+ * i, j, f, o; tf.contrib.layers.layer_norm over the H units of a sample, biased variance, epsilon 1e-12):
+ *   a_g  = gx_g[b,t] + h_{t-1} Wh_g^T,  n_g = LN(a_g; gamma_g, beta_g)              g in {i, j, f, o}
+ *   cand = tanh(n_j) * m / keep_prob            m ~ Bernoulli(keep_prob) per (b, t, unit)
+ *   c~   = c_{t-1} * s(n_f + forget_bias) + s(n_i) * cand
+ *   c_t  = LN(c~; gamma_s, beta_s)              (the normalised state is the one carried)
+ *   h_t  = tanh(c_t) * s(n_o)
+ * Forward direction only; two launches per time step (the recurrent product, then one wave per sample for the
+ * five LayerNorms and the cell). gx [B,T,4H] bf16: the hoisted input projection, no bias; wh [4H,H] bf16;
+ * ln [10,H] fp32: gamma_i, beta_i, gamma_j, beta_j, gamma_f, beta_f, gamma_o, beta_o, gamma_s, beta_s;
+ * lens as for os2s_rnn_layer_fwd (state passes through and y is zero past a length; clamped to [0, T]).
+ * m is bit (idx & 7) of the byte idx >> 3 that os2s_dropout_mask gives for (seed, keep_prob), idx = (b T + t) H +
+ * unit; keep_prob = 1: no dropout. h0 / c0 [B,H] fp32 or NULL (zero); hT / cT [B,H] fp32 or NULL (not wanted):
+ * without dropout a T-step call equals T one-step calls chained through them, bit for bit (a one-step call
+ * indexes its mask with T = 1). y: bf16, row (b,t) at
+ * y + (b T + t) ldy, ldy >= H and a multiple of 8. Saved for the backward (all three NULL for inference):
+ * xhat [B,T,4H] bf16 (the normalised pre-activations before gamma / beta), s_hat [B,T,H] fp32 (the normalised c~),
+ * rstd [B,T,5] fp32; rows past a length are not written.
+ * Backward: dy (row stride lddy, a multiple of 8) -> dgx = d a [B,T,4H] bf16, zero past the lengths, and
+ * dln [10,H] fp32, the gradients of ln, summed in a fixed order (bit-identical on a rerun). whT [H,4H] bf16. The
+ * caller forms dX, dWx and dWh (h_{t-1}: y shifted by one step, h0 in front) from dgx with the GEMM entry points;
+ * there is no bias gradient. Gradients with respect to h0 / c0 are not computed.
+ * H % 8 == 0, 8 <= H <= 2048, else OS2S_ERR_UNSUPPORTED.
+ * ---------------------------------------------------------------------- */
+size_t os2s_lnlstm_fwd_workspace_bytes(int B, int H);
+int os2s_lnlstm_layer_fwd(os2s_stream_t stream, const uint16_t* gx, const uint16_t* wh, const float* ln,
+                          const int32_t* lens, int B, int T, int H, float forget_bias, float keep_prob,
+                          unsigned long long seed, const float* h0, const float* c0, uint16_t* y, long long ldy,
+                          uint16_t* xhat, float* s_hat, float* rstd, float* hT, float* cT, void* workspace,
+                          size_t workspace_bytes);
+size_t os2s_lnlstm_bwd_workspace_bytes(int B, int H);
+int os2s_lnlstm_layer_bwd(os2s_stream_t stream, const uint16_t* whT, const float* ln, const int32_t* lens,
+                          const uint16_t* dy, long long lddy, const uint16_t* xhat, const float* s_hat,
+                          const float* rstd, const float* c0, int B, int T, int H, float forget_bias,
+                          float keep_prob, unsigned long long seed, uint16_t* dgx, float* dln, void* workspace,
+                          size_t workspace_bytes);
+/* Embedding lookup of the language model, with dropout on the MATRIX (encoders/lm_encoders.py:264: tf.nn.dropout of
+ * the [V,E] table, then tf.nn.embedding_lookup): out[n,c] = table[ids[n],c] * m / keep_prob, m = bit (idx & 7) of
+ * the byte idx >> 3 that os2s_dropout_mask gives for (seed, keep_prob), idx = ids[n] D + c: two occurrences of a token
+ * share one mask. table [V,D] bf16 (with weight_tied the transpose of the output layer's kernel, which is stored
+ * [V,E]: the same memory), D % 8 == 0, ids clamped to [0, V - 1]. Backward: dtable[ids[n],c] += dout[n,c] * m /
+ * keep_prob (fp32 atomics; one thread per column chunk in token order under os2s_set_deterministic). */
+int os2s_embed_wdrop_fwd(os2s_stream_t stream, const int32_t* ids, const uint16_t* table, int V, int D, long long N,
+                         float keep_prob, unsigned long long seed, uint16_t* out);
+int os2s_embed_wdrop_bwd(os2s_stream_t stream, const int32_t* ids, const uint16_t* dout, int V, int D, long long N,
+                         float keep_prob, unsigned long long seed, float* dtable);
+
+/* ------------------------------------------------------------------------
  * Attention-RNN decoder loop: the AttentionWrapper cell that tf.contrib.seq2seq.dynamic_decode
  * steps in RNNDecoderWithAttention (gnmt / gnmt_v2: decoders/rnn_decoders.py:147-321,
  * parts/rnns/gnmt.py:32-79) and Tacotron2Decoder (decoders/tacotron2_decoder.py:257-420):

@@ -1087,6 +1087,24 @@ def embed_bwd(ids, dout, dtable, emb_scale, keep_prob, seed, plain=False):
                         _ptr(dtable, torch.float32), int(plain))
 
 
+def embed_wdrop_fwd(ids, table, keep_prob, seed):
+  """tf.nn.embedding_lookup(tf.nn.dropout(table, keep_prob), ids): the mask is indexed by (token id, column)."""
+  N = ids.numel()
+  V, D = table.shape
+  out = torch.empty((N, D), dtype=torch.bfloat16, device=ids.device)
+  _lib.C.os2s_embed_wdrop_fwd(_stream(), _ptr(ids, torch.int32), _ptr(table, torch.bfloat16), V, D, N,
+                              float(keep_prob), int(seed) & (2**64 - 1), _ptr(out))
+  return out
+
+
+def embed_wdrop_bwd(ids, dout, dtable, keep_prob, seed):
+  """dtable [V,D] fp32 += scatter of dout * mask / keep_prob."""
+  N = ids.numel()
+  V, D = dtable.shape
+  _lib.C.os2s_embed_wdrop_bwd(_stream(), _ptr(ids, torch.int32), _ptr(dout, torch.bfloat16), V, D, N,
+                              float(keep_prob), int(seed) & (2**64 - 1), _ptr(dtable, torch.float32))
+
+
 def layernorm_fwd(x, gamma, beta, eps=1e-6, save=True):
   N, D = x.shape
   y = torch.empty_like(x)
@@ -1516,6 +1534,60 @@ def rnn_layer_bwd_multi(cell, dirs, lens, H, forget_bias=1.0, zoneout=None):
 def rnn_layer_bwd(cell, whT, lens, dy, y, gates, c_seq, H, reverse, forget_bias=1.0):
   return rnn_layer_bwd_multi(cell, [dict(whT=whT, dy=dy, y=y, gates=gates, c_seq=c_seq,
                                          reverse=reverse)], lens, H, forget_bias)[0]
+
+
+def lnlstm_layer_fwd(gx, wh, ln, lens, H, forget_bias=1.0, keep_prob=1.0, seed=0, h0=None, c0=None, y=None,
+                     save=True, want_state=False):
+  """os2s_lnlstm_layer_fwd: the LayerNorm-LSTM recurrence. gx [B,T,4H] bf16, wh [4H,H] bf16, ln [10,H] fp32
+  (gamma / beta of i, j, f, o, state), h0 / c0 [B,H] fp32 | None; y may be a channel-slice view (row stride a
+  multiple of 8). Returns dict(y, xhat, s_hat, rstd (None unless save), hT, cT (None unless want_state))."""
+  B, T, GH = gx.shape
+  dev = gx.device
+  assert GH == 4 * H and gx.dtype == torch.bfloat16 and gx.is_contiguous()
+  assert tuple(wh.shape) == (4 * H, H) and wh.is_contiguous() and tuple(ln.shape) == (10, H) and ln.is_contiguous()
+  if y is None:
+    y = (torch.zeros if lens is not None else torch.empty)((B, T, H), dtype=torch.bfloat16, device=dev)
+  assert y.stride(2) == 1 and y.stride(0) == T * y.stride(1)
+  xhat = s_hat = rstd = hT = cT = None
+  if save:
+    alloc = torch.zeros if lens is not None else torch.empty
+    xhat = alloc((B, T, 4 * H), dtype=torch.bfloat16, device=dev)
+    s_hat = alloc((B, T, H), dtype=torch.float32, device=dev)
+    rstd = alloc((B, T, 5), dtype=torch.float32, device=dev)
+  if want_state:
+    hT = torch.empty((B, H), dtype=torch.float32, device=dev)
+    cT = torch.empty((B, H), dtype=torch.float32, device=dev)
+  for s0 in (h0, c0):
+    assert s0 is None or (tuple(s0.shape) == (B, H) and s0.is_contiguous())
+  n = int(_lib.C.os2s_lnlstm_fwd_workspace_bytes(B, H))
+  ws = torch.empty((n,), dtype=torch.uint8, device=dev)
+  _lib.C.os2s_lnlstm_layer_fwd(_stream(), _ptr(gx, torch.bfloat16), _ptr(wh, torch.bfloat16), _ptr(ln, torch.float32),
+                               _ptr(lens, torch.int32, True), B, T, H, float(forget_bias), float(keep_prob),
+                               int(seed) & (2**64 - 1), _ptr(h0, torch.float32, True), _ptr(c0, torch.float32, True),
+                               y.data_ptr(), y.stride(1), _addr(xhat), _addr(s_hat), _addr(rstd), _addr(hT),
+                               _addr(cT), _ptr(ws), n)
+  return dict(y=y, xhat=xhat, s_hat=s_hat, rstd=rstd, hT=hT, cT=cT)
+
+
+def lnlstm_layer_bwd(whT, ln, lens, dy, xhat, s_hat, rstd, H, forget_bias=1.0, keep_prob=1.0, seed=0, c0=None):
+  """os2s_lnlstm_layer_bwd: dy [B,T,H] bf16 (may be a channel-slice view) and the tensors the forward saved ->
+  (dgx [B,T,4H] bf16, dln [10,H] fp32). whT [H,4H] bf16; c0 the forward's."""
+  B, T, _ = dy.shape
+  dev = dy.device
+  assert dy.stride(2) == 1 and dy.stride(0) == T * dy.stride(1)
+  assert tuple(whT.shape) == (H, 4 * H) and whT.is_contiguous() and tuple(ln.shape) == (10, H)
+  assert tuple(xhat.shape) == (B, T, 4 * H) and tuple(s_hat.shape) == (B, T, H) and tuple(rstd.shape) == (B, T, 5)
+  assert c0 is None or (tuple(c0.shape) == (B, H) and c0.is_contiguous())
+  dgx = torch.empty((B, T, 4 * H), dtype=torch.bfloat16, device=dev)
+  dln = torch.empty((10, H), dtype=torch.float32, device=dev)
+  n = int(_lib.C.os2s_lnlstm_bwd_workspace_bytes(B, H))
+  ws = torch.empty((n,), dtype=torch.uint8, device=dev)
+  _lib.C.os2s_lnlstm_layer_bwd(_stream(), _ptr(whT, torch.bfloat16), _ptr(ln, torch.float32),
+                               _ptr(lens, torch.int32, True), dy.data_ptr(), dy.stride(1), _ptr(xhat, torch.bfloat16),
+                               _ptr(s_hat, torch.float32), _ptr(rstd, torch.float32), _ptr(c0, torch.float32, True), B,
+                               T, H, float(forget_bias), float(keep_prob), int(seed) & (2**64 - 1), dgx.data_ptr(),
+                               _ptr(dln, torch.float32), _ptr(ws), n)
+  return dgx, dln
 
 
 # --------------------------------------------------------------------------

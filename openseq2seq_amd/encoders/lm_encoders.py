@@ -1,0 +1,274 @@
+"""LMEncoder — open_seq2seq/encoders/lm_encoders.py on the HIP kernels: the AWD-style LSTM language model
+(Merity et al., 2017). Embedding lookup with dropout on the MATRIX (:264, os2s_embed_wdrop_fwd), a stack of
+WeightDropLayerNormBasicLSTMCell layers under dynamic_rnn (parts/rnns/rnn_layers.py: LNLSTMLayer on
+csrc/lnlstm.hip) with DropoutWrapper output dropout, and the tf.layers.Dense output layer, whose kernel is also the
+(transposed) embedding matrix with weight_tied: the dropped matrix feeds the lookup, the undropped one the logits,
+and both gradients land in the one parameter. Layer widths are H, ..., H, and emb_size for the last layer when
+tied (:236-240). Infer (:404-434): one row per seed token, greedy decoding (argmax, re-embed) for up to
+num_tokens_gen steps, ended early once every row has emitted end_token (impute_finished=False), the state carried
+through h0 / c0 -> hT / cT, no dropout. use_cudnn_rnn runs the existing cuDNN-form LSTM kernels."""
+from __future__ import absolute_import, division, print_function
+
+import math
+
+import torch
+
+from .encoder import Encoder
+from .rnn_encoders import apply_scope_initializer, dropout_act
+from .. import capi
+from ..parts.dense import SeedSeq, bias_grad_from_rows
+from ..parts.rnns.rnn_layers import BiRNNStack, LNLSTMLayer
+from ..parts.streams import on_side_stream
+from ..parts.tape import Act
+
+CELL_SCOPE = "weight_drop_layer_norm_basic_lstm_cell"
+
+
+def _round8(n):
+  return -(-n // 8) * 8
+
+
+def _token_name(tok):
+  return tok if isinstance(tok, str) else getattr(tok, "__name__", str(tok))
+
+
+class LMEncoder(Encoder):
+  @staticmethod
+  def get_required_params():
+    return dict(Encoder.get_required_params(), **{
+        'vocab_size': int, 'emb_size': int, 'encoder_layers': int, 'encoder_use_skip_connections': bool,
+        'core_cell': None, 'core_cell_params': dict, 'end_token': int, 'batch_size': int,
+        'use_cudnn_rnn': bool, 'cudnn_rnn_type': None,
+    })
+
+  @staticmethod
+  def get_optional_params():
+    return dict(Encoder.get_optional_params(), **{
+        'encoder_dp_input_keep_prob': float, 'encoder_dp_output_keep_prob': float,
+        'encoder_last_input_keep_prob': float, 'encoder_last_output_keep_prob': float,
+        'encoder_emb_keep_prob': float, 'variational_recurrent': bool, 'time_major': bool,
+        'use_swap_memory': bool, 'proj_size': int, 'num_groups': int, 'num_tokens_gen': int,
+        'fc_use_bias': bool, 'seed_tokens': list, 'sampling_prob': float, 'schedule_learning': bool,
+        'weight_tied': bool, 'awd_initializer': bool, 'recurrent_keep_prob': float,
+        'input_weight_keep_prob': float, 'recurrent_weight_keep_prob': float, 'weight_variational': bool,
+        'dropout_seed': int, 'num_sampled': int, 'fc_dim': int, 'use_cell_state': bool,
+    })
+
+  def __init__(self, params, model, name="rnn_encoder_awd", mode='train'):
+    super(LMEncoder, self).__init__(params, model, name=name, mode=mode)
+    p = self.params
+    self._vocab_size, self._emb_size = p['vocab_size'], p['emb_size']
+    self._weight_tied = p.get('weight_tied', False)
+    for key, default in (('encoder_dp_input_keep_prob', 1.0), ('encoder_dp_output_keep_prob', 1.0),
+                         ('encoder_last_input_keep_prob', 1.0), ('encoder_last_output_keep_prob', 1.0),
+                         ('encoder_emb_keep_prob', 1.0), ('variational_recurrent', False), ('awd_initializer', False),
+                         ('recurrent_keep_prob', 1.0), ('input_weight_keep_prob', 1.0),
+                         ('recurrent_weight_keep_prob', 1.0), ('weight_variational', False), ('dropout_seed', 1822)):
+      p[key] = p.get(key, default)
+    self._fc_dim = p.get('fc_dim', self._vocab_size)
+    self._num_sampled = p.get('num_sampled', self._fc_dim)
+    self._lm_phase = self._fc_dim == self._vocab_size
+    self._num_tokens_gen = p.get('num_tokens_gen', 200)
+    self._batch_size = p['batch_size']
+    if mode == 'infer' and self._lm_phase:
+      self._batch_size = len(p['seed_tokens'])
+    self._use_cell_state = p.get('use_cell_state', False)
+
+  # ---------------------------------------------------------------- variables
+  def _unsupported(self):
+    """What this package does not build: each raises NotImplementedError naming the parameter."""
+    p, training = self.params, self._mode == "train"
+    if not self._lm_phase:
+      raise NotImplementedError("fc_dim != vocab_size (the text-classification phase)")
+    if self._use_cell_state:
+      raise NotImplementedError("use_cell_state (the text-classification phase)")
+    if training and self._num_sampled < self._fc_dim:
+      raise NotImplementedError("num_sampled < vocabulary (sampled softmax)")
+    for key in ('input_weight_keep_prob', 'recurrent_weight_keep_prob', 'encoder_dp_input_keep_prob',
+                'encoder_last_input_keep_prob'):
+      if p[key] < 1.0:
+        raise NotImplementedError("%s < 1" % key)
+    for key in ('weight_variational', 'variational_recurrent', 'encoder_use_skip_connections'):
+      if p.get(key, False):
+        raise NotImplementedError(key)
+    if p.get('time_major', False):
+      raise NotImplementedError("time_major layouts (batch-major [B,T,...] only)")
+
+  def build(self, store):
+    self._unsupported()
+    p = self.params
+    first = len(store.params)
+    scope = "ForwardPass/" + self._name
+    V, E = self._vocab_size, self._emb_size
+    self.Vpad = _round8(V)
+    cp = p['core_cell_params']
+    H = int(cp['num_units'])
+    nl = int(p['encoder_layers'])
+    self.cudnn = bool(p.get('use_cudnn_rnn', False))
+    if self.cudnn:
+      if 'CudnnLSTM' not in _token_name(p.get('cudnn_rnn_type')):
+        raise NotImplementedError("cudnn_rnn_type %s (CudnnLSTM is built)" % _token_name(p.get('cudnn_rnn_type')))
+      self.last = E
+    else:
+      if 'WeightDropLayerNormBasicLSTMCell' not in _token_name(p['core_cell']):
+        raise NotImplementedError("core_cell %s (WeightDropLayerNormBasicLSTMCell is built)" % _token_name(p['core_cell']))
+      if not cp.get('layer_norm', True):
+        raise NotImplementedError("core_cell_params layer_norm=False")
+      self.last = E if self._weight_tied else H
+    if self._weight_tied and self.last != E:
+      raise ValueError("weight_tied needs a last layer of emb_size units")
+    last = self.last
+    # the reference wires the regularizer to the Dense kernel only (:228-234)
+    l2 = 0.0
+    if p.get('regularizer', None) is not None:
+      l2 = float((p.get('regularizer_params', {}) or {}).get('scale', 0.0))
+
+    def init(shape):   # tf.layers.Dense default: glorot_uniform; vocabulary padding rows stay zero
+      lim = math.sqrt(6.0 / (last + V))
+      w = (torch.rand(shape) * 2 - 1) * lim
+      w[:, V:, :] = 0.0
+      return w
+
+    # variables in the reference's creation order: dense/kernel, dense/bias, [EncoderEmbeddingMatrix], the cells.
+    # With weight_tied the kernel's gradient is complete only after the embedding backward, the last closure to run.
+    self.proj = store.add(scope + "/dense/kernel", (1, self.Vpad, last), init, kind="conv", l2=l2, logical_out=V)
+    self.bias = store.add(scope + "/dense/bias", (self.Vpad,), torch.zeros(self.Vpad), kind="vector",
+                          logical_out=V) if p.get('fc_use_bias', True) else None
+    self.emb = None
+    if not self._weight_tied:
+      def init_e(shape):
+        lim = math.sqrt(6.0 / (V + E))
+        return (torch.rand(shape) * 2 - 1) * lim
+      self.emb = store.add(scope + "/EncoderEmbeddingMatrix", (V, E), init_e, kind="dense")
+    self.layers, self.stack = [], None
+    if self.cudnn:
+      self.stack = BiRNNStack(store, scope + "/cudnn_rnn", "lstm_cudnn", E, E, nl, bidirectional=False)
+    else:
+      cin = E
+      for k in range(nl):
+        width = last if k == nl - 1 else H
+        self.layers.append(LNLSTMLayer(store, "%s/cells/cell_%d/%s" % (scope, k, CELL_SCOPE), cin, width,
+                                       forget_bias=cp.get('forget_bias', 1.0), norm_gain=cp.get('norm_gain', 1.0),
+                                       norm_shift=cp.get('norm_shift', 0.0)))
+        cin = width
+    apply_scope_initializer(store, first, p)
+    if p['awd_initializer'] and not self.cudnn:
+      # parts/rnns/utils.py:52-54: uniform(+-1 / sqrt(num_units)) for the cell kernels
+      for layer in self.layers:
+        val = 1.0 / math.sqrt(layer.H)
+        for w in (layer.wx, layer.wh):
+          store._inits[w.index] = (lambda shape, val=val: (torch.rand(shape) * 2 - 1) * val)
+    self.output_dim = V
+    return self
+
+  # ---------------------------------------------------------------- pieces
+  def _table16(self):
+    return self.proj.w16.view(self.Vpad, self.last) if self._weight_tied else self.emb.w16.view(self._vocab_size, -1)
+
+  def _table_grad(self):
+    return self.proj.grad.view(self.Vpad, self.last) if self._weight_tied else self.emb.grad.view(self._vocab_size, -1)
+
+  def _logits(self, feat2d):
+    return capi.gemm(feat2d, self.proj.w16.view(self.Vpad, self.last),
+                     bias=self.bias.master if self.bias is not None else None)
+
+  # ---------------------------------------------------------------- train / eval
+  def _encode(self, input_dict):
+    if self._mode == "infer":
+      return self._generate(input_dict)
+    p = self.params
+    ids, lens = input_dict['source_tensors'][0], input_dict['source_tensors'][1]
+    B, T = ids.shape
+    training = self._mode == "train"
+    tape = input_dict.get('tape') if training else None
+    seeds = input_dict.get('seeds') or SeedSeq(p['dropout_seed'])
+    keep = (lambda k: p[k]) if training else (lambda k: 1.0)
+    V, E, last = self._vocab_size, self._emb_size, self.last
+    ids_flat = ids.reshape(-1).to(torch.int32).contiguous()
+    emb_keep, emb_seed = keep('encoder_emb_keep_prob'), seeds.next()
+    cur = Act(capi.embed_wdrop_fwd(ids_flat, self._table16(), emb_keep, emb_seed).view(B, T, E), lens)
+    if tape is not None:
+      enc, x0 = self, cur
+
+      def emb_backward():
+        if x0.grad is not None:
+          capi.embed_wdrop_bwd(ids_flat, x0.grad.reshape(B * T, E), enc._table_grad(), emb_keep, emb_seed)
+        x0.grad = None
+
+      tape.record(emb_backward, [self.proj if self._weight_tied else self.emb])
+    if self.cudnn:
+      cur = self.stack.forward(cur, lens, tape)
+    else:
+      nl = len(self.layers)
+      for k, layer in enumerate(self.layers):
+        y = layer.forward(cur, lens, tape, keep_prob=keep('recurrent_keep_prob'), seed=seeds.next())
+        okeep = keep('encoder_last_output_keep_prob' if k == nl - 1 else 'encoder_dp_output_keep_prob')
+        cur = dropout_act(y, okeep, seeds.next(), tape)
+    feat = cur.data.reshape(B * T, last)
+    logits2 = self._logits(feat)
+    logits = Act(logits2.view(B, T, self.Vpad), lens)
+    if tape is not None:
+      enc, top = self, cur
+
+      def backward():
+        dl = logits.grad.reshape(B * T, enc.Vpad)
+        g = top.grad_buffer()
+        capi.gemm(dl, enc.proj.wt16.view(last, enc.Vpad), out=g.view(B * T, last), accumulate=top.grad_init)
+        top.grad_init = True
+        with on_side_stream(dl.device, dl, feat):
+          capi.gemm_wgrad(feat, dl, enc.proj.grad.view(enc.Vpad, last), accumulate=True)
+          if enc.bias is not None:
+            bias_grad_from_rows(dl, enc.bias)
+        logits.grad = None
+
+      tape.record(backward, ([] if self._weight_tied else [self.proj]) + ([self.bias] if self.bias is not None else []))
+    out = logits.data[:, :, :V]
+    return {'logits': logits.data, 'logits_act': logits, 'vocab_size': V, 'outputs': [out], 'src_lengths': lens,
+            'seeds': seeds}
+
+  # ---------------------------------------------------------------- infer
+  def _generate(self, input_dict):
+    """GreedyEmbeddingHelper(start_tokens = seed_tokens, end_token) + BasicDecoder(zero state, output layer) +
+    dynamic_decode(impute_finished=False, maximum_iterations = num_tokens_gen)."""
+    p = self.params
+    dev = self.proj.w16.device
+    V, E = self._vocab_size, self._emb_size
+    tok = torch.tensor([int(t) for t in p['seed_tokens']], dtype=torch.int32, device=dev)
+    B = tok.numel()
+    finished = torch.zeros(B, dtype=torch.bool, device=dev)
+    lengths = torch.zeros(B, dtype=torch.int32, device=dev)
+    state = [(None, None)] * len(self.layers)
+    prefix = tok.view(B, 1)
+    all_logits, all_ids = [], []
+    for _ in range(self._num_tokens_gen):
+      if self.cudnn:
+        # the cuDNN-form kernels take no initial state: the growing prefix is run again each step
+        n = prefix.shape[1]
+        x = capi.embed_wdrop_fwd(prefix.reshape(-1).contiguous(), self._table16(), 1.0, 0).view(B, n, E)
+        x = self.stack.forward(Act(x, requires_grad=False), None, None).data[:, -1].contiguous()
+      else:
+        x = capi.embed_wdrop_fwd(tok, self._table16(), 1.0, 0)
+        for k, layer in enumerate(self.layers):
+          x, h, c = layer.step(x, *state[k])
+          state[k] = (h, c)
+      logits = self._logits(x)
+      nxt = capi.argmax_rows(logits, V)
+      all_logits.append(logits[:, :V])
+      all_ids.append(nxt)
+      lengths += (~finished).to(torch.int32)
+      finished = finished | (nxt == int(p['end_token']))
+      tok = nxt
+      prefix = torch.cat([prefix, nxt.view(B, 1)], dim=1)
+      if bool(finished.all()):
+        break
+    ids = torch.stack(all_ids, dim=1)
+    return {'logits': torch.stack(all_logits, dim=1), 'outputs': [ids], 'final_state': state,
+            'final_sequence_lengths': lengths}
+
+  @property
+  def vocab_size(self):
+    return self._vocab_size
+
+  @property
+  def emb_size(self):
+    return self._emb_size

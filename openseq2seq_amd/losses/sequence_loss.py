@@ -97,3 +97,25 @@ class BasicSequenceLoss(Loss):
       la.grad = dl.view(B, T, Vp)
       la.grad_init = True
     return loss
+
+
+class BasicSampledSequenceLoss(Loss):
+  """Sampled softmax of the language model (losses/sequence_loss.py, `num_sampled` of lstm-wkt103-mixed.py): not
+  built. The class exists so that the config loads; LMEncoder raises the NotImplementedError that names
+  num_sampled when it is built for training, and so does constructing this loss."""
+
+  @staticmethod
+  def get_required_params():
+    return dict(Loss.get_required_params(), **{'tgt_vocab_size': int, 'batch_size': int})
+
+  @staticmethod
+  def get_optional_params():
+    return dict(Loss.get_optional_params(), **{
+        'offset_target_by_one': bool, 'average_across_timestep': bool, 'do_mask': bool, 'hid_dim': int,
+    })
+
+  def __init__(self, params, model, name="basic_sampled_sequence_loss"):
+    raise NotImplementedError("num_sampled < vocabulary (sampled softmax, BasicSampledSequenceLoss)")
+
+  def _compute_loss(self, input_dict):
+    raise NotImplementedError("num_sampled < vocabulary (sampled softmax, BasicSampledSequenceLoss)")

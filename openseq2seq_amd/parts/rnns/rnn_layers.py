@@ -226,3 +226,83 @@ class BiRNNStack(object):
           tape.record(backward)
         cur = dropped
     return cur
+
+
+LN_SCOPES = ("input", "transform", "forget", "output", "state")     # the rows of the kernel's ln [10, H], in pairs
+
+
+class LNLSTMLayer(object):
+  """One layer of WeightDropLayerNormBasicLSTMCell with layer_norm=True (parts/rnns/weight_drop.py:140-166) under
+  dynamic_rnn: no bias, LayerNorm (gamma init norm_gain, beta init norm_shift) on the four gate pre-activations
+  and on the new cell state, recurrent dropout on the candidate. The input projection of all time steps is one
+  GEMM, the recurrence is os2s_lnlstm_layer_fwd / _bwd (csrc/lnlstm.hip), the weight gradients are GEMMs over the
+  saved gate gradients on the side stream (h_{t-1}: y shifted by one step, h0 in front)."""
+
+  def __init__(self, store, name, input_size, hidden, forget_bias=1.0, norm_gain=1.0, norm_shift=0.0):
+    self.H, self.input_size, self.forget_bias = hidden, input_size, float(forget_bias)
+    GH = 4 * hidden
+    if hidden % 8 or not 8 <= hidden <= 2048 or input_size % 8:
+      raise NotImplementedError("LayerNorm-LSTM: num_units %d / input width %d (multiples of 8, units 8 .. 2048)"
+                                % (hidden, input_size))
+
+    def init(shape):    # glorot-uniform over the reference's one [in + H, 4H] kernel
+      lim = math.sqrt(6.0 / (input_size + hidden + GH))
+      return (torch.rand(shape) * 2 - 1) * lim
+
+    self.wx = store.add(name + "/wx_0", (1, GH, input_size), init, kind="conv")
+    self.wh = store.add(name + "/wh", (1, GH, hidden), init, kind="conv")
+    self.ln = []
+    for scope in LN_SCOPES:
+      self.ln.append(store.add("%s/%s/gamma" % (name, scope), (hidden,), torch.full((hidden,), float(norm_gain)),
+                               kind="vector"))
+      self.ln.append(store.add("%s/%s/beta" % (name, scope), (hidden,), torch.full((hidden,), float(norm_shift)),
+                               kind="vector"))
+
+  def params(self):
+    return [self.wx, self.wh] + self.ln
+
+  def forward(self, x, lens, tape, keep_prob=1.0, seed=0, h0=None, c0=None, want_state=False):
+    """x: Act [B,T,In]; lens int32 [B] | None; h0 / c0 fp32 [B,H] | None. Returns Act [B,T,H], or (Act, hT, cT)
+    with want_state. keep_prob: recurrent_keep_prob (the caller passes 1.0 outside training)."""
+    B, T, _ = x.data.shape
+    H, GH = self.H, 4 * self.H
+    x2 = x.data.reshape(B * T, -1)
+    gx = capi.gemm(x2, self.wx.w16.view(GH, -1)).view(B, T, GH)
+    ln = torch.stack([p.master for p in self.ln])
+    r = capi.lnlstm_layer_fwd(gx, self.wh.w16.view(GH, H), ln, lens, H, self.forget_bias, keep_prob, seed, h0, c0,
+                              save=tape is not None, want_state=want_state)
+    out = Act(r["y"], lens)
+    if tape is not None:
+      layer = self
+
+      def backward():
+        assert out.grad is not None, "no gradient reached " + layer.wh.name
+        dgx, dln = capi.lnlstm_layer_bwd(layer.wh.wt16.view(H, GH), ln, lens, out.grad, r["xhat"], r["s_hat"],
+                                         r["rstd"], H, layer.forget_bias, keep_prob, seed, c0)
+        d2 = dgx.view(B * T, GH)
+        if x.requires_grad:
+          g = x.grad_buffer()
+          capi.gemm(d2, layer.wx.wt16.view(-1, GH), out=g.view(B * T, -1), accumulate=x.grad_init)
+          x.grad_init = True
+        for k, p in enumerate(layer.ln):
+          p.grad.add_(dln[k])
+        with on_side_stream(dgx.device, dgx, r["y"], x.data, *([h0] if h0 is not None else [])):
+          capi.gemm_wgrad(x2, d2, layer.wx.grad.view(GH, -1), accumulate=True)
+          # dWh += dgx^T . h_{t-1}. Rows at or past a sample's length carry zero gate gradients
+          ysh = torch.empty((B, T, H), dtype=r["y"].dtype, device=dgx.device)
+          ysh[:, 1:] = r["y"][:, :-1]
+          if h0 is not None:
+            ysh[:, 0] = h0.to(ysh.dtype)
+          else:
+            ysh[:, 0] = 0
+          capi.gemm_wgrad(ysh.view(B * T, H), d2, layer.wh.grad.view(GH, H), accumulate=True)
+        out.grad = None
+
+      tape.record(backward, self.params())
+    return (out, r["hT"], r["cT"]) if want_state else out
+
+  def step(self, x2d, h, c):
+    """One generation step without dropout: x2d bf16 [B,In], h / c fp32 [B,H] | None -> (y bf16 [B,H], h', c')."""
+    out, h, c = self.forward(Act(x2d.view(x2d.shape[0], 1, -1), requires_grad=False), None, None, h0=h, c0=c,
+                             want_state=True)
+    return out.data.view(x2d.shape[0], self.H), h, c

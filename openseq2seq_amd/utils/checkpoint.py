@@ -168,6 +168,10 @@ _RNN_SCOPES = [
      "/rnn_decoder_with_attention/decoder/multi_rnn_cell/cell_0_attention/gnmt_attention/bahdanau_attention/"),
     (r"/rnn_decoder_with_attention/multi_rnn_cell/", "/rnn_decoder_with_attention/decoder/multi_rnn_cell/"),
     (r"/rnn_decoder_with_attention/dense/", "/rnn_decoder_with_attention/decoder/dense/"),
+    # LMEncoder (encoders/lm_encoders.py:352-360: dynamic_rnn(scope='decoder') over a MultiRNNCell; one kernel
+    # [in + H, 4H] per WeightDropLayerNormBasicLSTMCell, input rows first, and its five LayerNorm pairs as they are),
+    # names checked against the reference's executed graph (tests/golden/ref_exec_lm.npz)
+    (r"/rnn_encoder_awd/cells/", "/rnn_encoder_awd/decoder/multi_rnn_cell/"),
     # Tacotron2Decoder (decoders/tacotron2_decoder.py: everything the decoder step touches lives under dynamic_decode's
     # 'decoder' scope; the memory layer is created with the attention mechanism, outside it)
     (r"/tacotron_2_decoder/attention_wrapper/attention/memory_layer/", "/tacotron_2_decoder/AttentionMechanism/memory_layer/"),
@@ -213,6 +217,21 @@ def lstm_kernel_groups(params):
     if order is not None:
       groups.setdefault(ref, []).append((order, p))
   return {k: [p for _, p in sorted(v, key=lambda t: t[0])] for k, v in groups.items()}
+
+
+def variable_shapes(params):
+  """{reference variable name: shape in the TensorFlow layout} that model_variables() writes for these parameters
+  (they need not be finalised: only names, shapes and kinds are read). The cuDNN-form layers are left out."""
+  groups = lstm_kernel_groups(params)
+  grouped = {p.name for ps in groups.values() for p in ps}
+  out = {ref: (sum(p.shape[2] for p in ps), ps[0].shape[1]) for ref, ps in groups.items()}
+  for p in params:
+    if p.name in grouped or _CUDNN_PART.match(p.name):
+      continue
+    for tf_name, tf_arr in export_param(reference_name(p.name)[0], p.shape, p.kind, np.zeros(p.shape, np.float32),
+                                        getattr(p, "logical_out", None)):
+      out[tf_name] = tuple(tf_arr.shape)
+  return out
 
 
 # ---------------------------------------------------------------------------------------------------------
