@@ -377,6 +377,12 @@ int os2s_conv1d_wgrad_ws(os2s_stream_t stream, const uint16_t* x, long long x_ro
                          const uint16_t* dy, float* dw, const int32_t* in_len, int B, int Tin,
                          int Cin, int Cout, int K, int stride, int dil, int padL, int Tout,
                          int accumulate, void* workspace, size_t workspace_bytes);
+/* 1 if os2s_conv1d_wgrad_ws would hand this problem to a kernel in which every dW element has one owner (the
+ * ping-pong kernel, the opt-in one-wave-per-SIMD kernel): accumulate = 0 costs nothing there. 0 for the lockstep
+ * kernels and the K = 1 TN-GEMM kernel (the lockstep kernel splits the batch over the chip only with accumulate = 1).
+ * Reads the same envelope, options included, as the launcher. */
+int os2s_conv1d_wgrad_single_owner(int B, int Tin, int Cin, int Cout, int K, int stride, int dil, int Tout,
+                                   long long x_row_stride);
 
 /* ------------------------------------------------------------------------
  * BatchNorm + residual sum + activation + dropout + sequence mask
@@ -546,6 +552,35 @@ int os2s_opt_apply_range(os2s_stream_t stream, const os2s_opt_config_t* cfg, con
                          int chunk_begin, int chunk_end, const int32_t* chunk_tensor,
                          const float* tensor_l2, const float* tensor_mult,
                          const float* tensor_wd_mask, int zero_grads);
+/* The two halves with the per-chunk sums of w^2 kept from one step to the next (LARC needs each tensor's weight
+ * norm; the weights a step reads are the ones the previous update wrote). partial_w [nchunks] persists across
+ * steps: os2s_opt_apply_range_cached leaves the sum of the NEW w^2 of every chunk it updates there (a skipped step
+ * leaves the entries alone: the weights did not change), and the statistics pass of os2s_opt_prepare_cached reads a
+ * chunk's weights only if its tensor has an l2 term or tensor_need_w[tensor] != 0 (one byte per tensor: "the weights
+ * may have changed since the last update wrote the entry" - the first step, a checkpoint load, any writer other than
+ * the update); such a chunk refreshes its entry. Both sides form the sum in one order, so a cached entry and a
+ * recomputed one are the same bits. tensor_need_w NULL: every tensor's weights are read when LARC is on or tensor_l2
+ * is given, none otherwise (os2s_opt_prepare). mismatch != NULL: checking mode, every chunk's weights are read as well
+ * and *mismatch (device int32, zeroed by the caller) counts the cached entries that differ from the recomputed sum.
+ * partial_w NULL in either call is the entry point without the suffix. */
+int os2s_opt_prepare_cached(os2s_stream_t stream, const os2s_opt_config_t* cfg, void* state,
+                            const float* grads, const float* weights, int nchunks, int ntensors,
+                            const int32_t* chunk_tensor, const int32_t* tensor_chunk_begin,
+                            const float* tensor_l2, float* partial, float* tensor_gnorm2, float* tensor_wnorm2,
+                            float* tensor_amax, float* tensor_mult, float* tensor_v,
+                            float* partial_w, const uint8_t* tensor_need_w, int* mismatch);
+int os2s_opt_apply_range_cached(os2s_stream_t stream, const os2s_opt_config_t* cfg, const void* state,
+                                float* grads, float* weights, float* m1, float* m2, uint16_t* w16,
+                                int chunk_begin, int chunk_end, const int32_t* chunk_tensor,
+                                const float* tensor_l2, const float* tensor_mult,
+                                const float* tensor_wd_mask, int zero_grads, float* partial_w);
+/* buf [nchunks * os2s_opt_chunk_elems()] fp32: zero fill of every chunk whose tensor (chunk_tensor[c]) has
+ * tensor_skip[tensor] == 0. Of the other tensors (tensor_chunk_begin [ntensors + 1], tensor_numel [ntensors]: their
+ * chunk ranges and element counts) only the padding between the last element and the chunk boundary is zeroed: no
+ * element of such a tensor is touched. */
+int os2s_fill_zero_chunks(os2s_stream_t stream, float* buf, int nchunks, const int32_t* chunk_tensor,
+                          const uint8_t* tensor_skip, const int32_t* tensor_chunk_begin,
+                          const long long* tensor_numel);
 int os2s_cast_f32_to_bf16(os2s_stream_t stream, const float* src, uint16_t* dst,
                           long long n);
 /* batched dgrad copies of conv weights: wT[k'][ci][co] = w[K-1-k'][co][ci];

@@ -418,6 +418,14 @@ def conv1d_wgrad(x, dy, K, *, stride=1, dil=1, pad_left=None, in_len=None,
   return out
 
 
+def conv1d_wgrad_single_owner(x, dy, K, *, stride=1, dil=1):
+  """os2s_conv1d_wgrad_single_owner: would conv1d_wgrad(x, dy, K, ...) run on a kernel in which every dW element has
+  one owner (accumulate=False is free there), as the launcher itself decides it (options included)?"""
+  B, Tin, Cin = x.shape
+  return bool(_lib.C.os2s_conv1d_wgrad_single_owner(B, Tin, Cin, dy.shape[2], int(K), int(stride), int(dil),
+                                                    dy.shape[1], x.stride(1)))
+
+
 class _CWgradGroup(_lib.ctypes.Structure):
   _fields_ = [("x", c_void_p), ("dy", c_void_p), ("dw", c_void_p), ("x_row_stride", c_ll)]
 
@@ -779,7 +787,18 @@ def gru_xcd_check(clear=False):
 
 
 def opt_step(cfg, state, grads, weights, m1, m2, w16, chunk_tensor, tensor_chunk_begin,
-             tensor_l2, tensor_wd_mask, partial, gnorm2, wnorm2, amax, mult, tensor_v):
+             tensor_l2, tensor_wd_mask, partial, gnorm2, wnorm2, amax, mult, tensor_v, *, partial_w=None,
+             need_w=None, mismatch=None):
+  """One optimisation step on the current stream. partial_w (fp32 [nchunks], kept by the caller from step to
+  step): the per-chunk sums of w^2 are cached there (os2s_opt_prepare_cached / os2s_opt_apply_range_cached;
+  need_w: uint8 [ntensors], mismatch: int32 [1] of the checking mode)."""
+  if partial_w is not None:
+    opt_prepare(cfg, state, grads, weights, chunk_tensor, tensor_chunk_begin, tensor_l2, partial, gnorm2, wnorm2,
+                amax, mult, tensor_v, partial_w=partial_w, need_w=need_w, mismatch=mismatch)
+    opt_apply_range(cfg, state, grads, weights, m1, m2, w16, 0, chunk_tensor.numel(), chunk_tensor, tensor_l2, mult,
+                    tensor_wd_mask=tensor_wd_mask, partial_w=partial_w)
+    return
+  assert need_w is None and mismatch is None
   nchunks = chunk_tensor.numel()
   ntensors = tensor_chunk_begin.numel() - 1
   _lib.C.os2s_opt_step(_stream(), _lib.ctypes.byref(cfg), _ptr(state, torch.uint8),
@@ -794,25 +813,46 @@ def opt_step(cfg, state, grads, weights, m1, m2, w16, chunk_tensor, tensor_chunk
 
 
 def opt_prepare(cfg, state, grads, weights, chunk_tensor, tensor_chunk_begin, tensor_l2, partial, gnorm2, wnorm2,
-                amax, mult, tensor_v):
-  """First half of opt_step (os2s_opt_prepare): everything that needs all gradients."""
+                amax, mult, tensor_v, *, partial_w=None, need_w=None, mismatch=None):
+  """First half of opt_step (os2s_opt_prepare / os2s_opt_prepare_cached): everything that needs all gradients."""
   nchunks = chunk_tensor.numel()
   ntensors = tensor_chunk_begin.numel() - 1
-  _lib.C.os2s_opt_prepare(_stream(), _lib.ctypes.byref(cfg), _ptr(state, torch.uint8), _ptr(grads, torch.float32),
-                          _ptr(weights, torch.float32), nchunks, ntensors, _ptr(chunk_tensor, torch.int32),
-                          _ptr(tensor_chunk_begin, torch.int32), _ptr(tensor_l2, torch.float32, True),
-                          _ptr(partial, torch.float32), _ptr(gnorm2, torch.float32), _ptr(wnorm2, torch.float32),
-                          _ptr(amax, torch.float32), _ptr(mult, torch.float32), _ptr(tensor_v, torch.float32, True))
+  assert partial_w is None or partial_w.numel() == nchunks
+  assert need_w is None or (partial_w is not None and need_w.numel() == ntensors)
+  assert mismatch is None or partial_w is not None
+  _lib.C.os2s_opt_prepare_cached(
+      _stream(), _lib.ctypes.byref(cfg), _ptr(state, torch.uint8), _ptr(grads, torch.float32),
+      _ptr(weights, torch.float32), nchunks, ntensors, _ptr(chunk_tensor, torch.int32),
+      _ptr(tensor_chunk_begin, torch.int32), _ptr(tensor_l2, torch.float32, True),
+      _ptr(partial, torch.float32), _ptr(gnorm2, torch.float32), _ptr(wnorm2, torch.float32),
+      _ptr(amax, torch.float32), _ptr(mult, torch.float32), _ptr(tensor_v, torch.float32, True),
+      _ptr(partial_w, torch.float32, True), _ptr(need_w, torch.uint8, True), _ptr(mismatch, torch.int32, True))
 
 
 def opt_apply_range(cfg, state, grads, weights, m1, m2, w16, chunk_begin, chunk_end, chunk_tensor, tensor_l2, mult,
-                    zero_grads=False):
-  """Second half (os2s_opt_apply_range): the update of chunks [chunk_begin, chunk_end) of the flat buffers."""
-  _lib.C.os2s_opt_apply_range(_stream(), _lib.ctypes.byref(cfg), _ptr(state, torch.uint8), _ptr(grads, torch.float32),
-                              _ptr(weights, torch.float32), _ptr(m1, torch.float32, True),
-                              _ptr(m2, torch.float32, True), _ptr(w16, torch.bfloat16, True), int(chunk_begin),
-                              int(chunk_end), _ptr(chunk_tensor, torch.int32), _ptr(tensor_l2, torch.float32, True),
-                              _ptr(mult, torch.float32), c_void_p(0), int(bool(zero_grads)))
+                    zero_grads=False, *, tensor_wd_mask=None, partial_w=None):
+  """Second half (os2s_opt_apply_range_cached): the update of chunks [chunk_begin, chunk_end) of the flat buffers."""
+  assert 0 <= chunk_begin <= chunk_end <= chunk_tensor.numel()
+  assert partial_w is None or partial_w.numel() == chunk_tensor.numel()
+  _lib.C.os2s_opt_apply_range_cached(
+      _stream(), _lib.ctypes.byref(cfg), _ptr(state, torch.uint8), _ptr(grads, torch.float32),
+      _ptr(weights, torch.float32), _ptr(m1, torch.float32, True),
+      _ptr(m2, torch.float32, True), _ptr(w16, torch.bfloat16, True), int(chunk_begin),
+      int(chunk_end), _ptr(chunk_tensor, torch.int32), _ptr(tensor_l2, torch.float32, True),
+      _ptr(mult, torch.float32), _ptr(tensor_wd_mask, torch.float32, True), int(bool(zero_grads)),
+      _ptr(partial_w, torch.float32, True))
+
+
+def fill_zero_chunks(buf, chunk_tensor, tensor_skip, tensor_chunk_begin, tensor_numel):
+  """os2s_fill_zero_chunks: zero fill of the chunks of `buf` (fp32, chunk_tensor.numel() chunks) whose tensor is not
+  marked in tensor_skip (uint8 [ntensors]); of a marked tensor only the padding behind its last element
+  (tensor_chunk_begin int32 [ntensors + 1], tensor_numel int64 [ntensors])."""
+  nt = tensor_chunk_begin.numel() - 1
+  assert buf.numel() == chunk_tensor.numel() * opt_chunk_elems() and buf.is_contiguous()
+  assert nt >= 1 and tensor_skip.numel() == nt and tensor_numel.numel() == nt
+  _lib.C.os2s_fill_zero_chunks(_stream(), _ptr(buf, torch.float32), chunk_tensor.numel(),
+                               _ptr(chunk_tensor, torch.int32), _ptr(tensor_skip, torch.uint8),
+                               _ptr(tensor_chunk_begin, torch.int32), _ptr(tensor_numel, torch.int64))
 
 
 def cast_f32_to_bf16(src, dst):

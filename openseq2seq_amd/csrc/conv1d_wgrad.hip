@@ -1232,6 +1232,42 @@ static int launch_wgrad1x1_pp(hipStream_t stream, os2s::WgradArgs a, const os2s:
   return OS2S_OK;
 }
 
+// Which of the two kernels that own every dW element once — (128 co, 128 ci, 4 taps) units, no atomics, accumulate = 0
+// costs nothing — takes the problem in `a`: kWgradPingPong, kWgradOneWave (opt-in), or kWgradOther (the lockstep
+// kernels, the K = 1 TN-GEMM kernel). The ONE place the envelope is written: the launcher below and
+// os2s_conv1d_wgrad_single_owner both ask here. units / smem: the launch's units and dynamic LDS bytes.
+enum { kWgradOther = 0, kWgradPingPong = 1, kWgradOneWave = 3 };
+static int wgrad_tap_quad_choice(os2s::WgradArgs a, long long x_row_stride, bool grouped, int* units, size_t* smem_out) {
+  using namespace os2s;
+  const int B = a.B, Tin = a.Tin, Tout = a.Tout, Cin = a.Cin, Cout = a.Cout, K = a.K, stride = a.stride, dil = a.dil;
+  const bool pp_shape = stride == 1 && K >= 2 && B <= 64 && Cout >= 128 && Cin >= 64 &&
+                        Tin < 65536 && Tout <= 255 * 64 && 63 + 3 * dil + 1 <= 96 &&
+                        (long long)Tin * x_row_stride * 2 < (1ll << 30) &&
+                        (long long)Tin * x_row_stride * 2 < (1ll << 31) &&
+                        (long long)Tout * Cout * 2 < (1ll << 31);
+  // (co, ci, 4-tap) tiles of the ping-pong kernel; with the reduction split across workgroups even
+  // the 256-channel layers (12 tiles) beat the lockstep kernel (0.076 vs 0.093 ms ragged)
+  const int pp_units = ceil_div(Cout, 128) * ceil_div(Cin, 128) * ceil_div(K, kWppTaps);
+  // ---- one wave per SIMD, 16 accumulator blocks per wave (conv1d_wgrad_sw.hpp; round 6): the same units ----
+  const bool sw_shape = pp_shape && 63 + 3 * dil + 1 <= kSwXInstr * 16 &&     // the X window fits the 20 KB slot
+                        Cout % 128 == 0 && Cin % 128 == 0;                      // whole tiles only
+  // Opt-in (conv1d_wgrad.variant 3): measured against the ping-pong kernel on the 768 x 768 x 25 layer it needs 3 050
+  // cycles per 64-row step at 2.11 GHz where the ping-pong kernel needs 2 400 at 1.75 GHz — 0.648 vs 0.612 ms
+  // (profiles/r06_wgrad_sw_ablation.txt, DESIGN.md "Round-6 kernel work").
+  *units = pp_units;
+  if (sw_shape && g_wgrad_variant == 3 && !grouped) {
+    wgrad_tap_quad_geometry(a, kSwXBuf);
+    *smem_out = (size_t)kSwRing * (kSwYBuf + kSwXBuf) + a.steptab_bytes;
+    if (*smem_out <= 160 * 1024) return kWgradOneWave;
+  }
+  if (pp_shape && g_wgrad_variant != 0 && (grouped || g_wgrad_variant == 1 || pp_units >= g_wgrad_pp_min_units)) {
+    wgrad_tap_quad_geometry(a, 24 * 1024);              // 3 DMA rounds of 8 waves x 1 KB
+    *smem_out = (size_t)2 * 64 * 256 + (size_t)3 * a.xbuf_bytes + a.steptab_bytes + (a.dbg ? 2 * 48 * 10 * 8 : 0);
+    if (*smem_out <= 160 * 1024) return kWgradPingPong;
+  }
+  return kWgradOther;
+}
+
 // accumulate = 0 : dW = grad;  accumulate = 1 : dW += grad.
 // With a workspace (os2s_conv1d_workspace_bytes(), zero tickets, one per stream — the same
 // contract as os2s_conv1d_fwd_ws) the ping-pong kernel spreads small layers over the chip by
@@ -1261,51 +1297,38 @@ static int conv1d_wgrad_impl_g(os2s_stream_t stream, const uint16_t* x, long lon
     for (int i = 0; i < ngroups; ++i) { a.gx[i] = groups[i].x; a.gdy[i] = groups[i].dy; a.gdw[i] = groups[i].dw; }
   }
 
-  // ---- ping-pong kernel ------------------------------------------------------------------
-  const bool pp_shape = stride == 1 && K >= 2 && B <= 64 && Cout >= 128 && Cin >= 64 &&
-                        Tin < 65536 && Tout <= 255 * 64 && 63 + 3 * dil + 1 <= 96 &&
-                        (long long)Tin * x_row_stride * 2 < (1ll << 30) &&
-                        (long long)Tin * x_row_stride * 2 < (1ll << 31) &&
-                        (long long)Tout * Cout * 2 < (1ll << 31);
-  // (co, ci, 4-tap) tiles of the ping-pong kernel; with the reduction split across workgroups even
-  // the 256-channel layers (12 tiles) beat the lockstep kernel (0.076 vs 0.093 ms ragged)
-  const int pp_units = ceil_div(Cout, 128) * ceil_div(Cin, 128) * ceil_div(K, kWppTaps);
-  // ---- one wave per SIMD, 16 accumulator blocks per wave (conv1d_wgrad_sw.hpp; round 6): the same units ----
-  const bool sw_shape = pp_shape && 63 + 3 * dil + 1 <= kSwXInstr * 16 &&     // the X window fits the 20 KB slot
-                        Cout % 128 == 0 && Cin % 128 == 0;                      // whole tiles only
-  // Opt-in (conv1d_wgrad.variant 3): measured against the ping-pong kernel on the 768 x 768 x 25 layer it needs 3 050
-  // cycles per 64-row step at 2.11 GHz where the ping-pong kernel needs 2 400 at 1.75 GHz — 0.648 vs 0.612 ms
-  // (profiles/r06_wgrad_sw_ablation.txt, DESIGN.md "Round-6 kernel work").
-  if (sw_shape && g_wgrad_variant == 3 && !groups) {
+  // ---- the kernels of (128 co, 128 ci, 4 taps) units: ping-pong, one wave per SIMD (wgrad_tap_quad_choice) -------
+  int pp_units = 0;
+  size_t tq_smem = 0;
+  const int choice = wgrad_tap_quad_choice(a, x_row_stride, groups != nullptr, &pp_units, &tq_smem);
+  if (choice == kWgradOneWave) {
     wgrad_tap_quad_geometry(a, kSwXBuf);
-    const size_t smem = (size_t)kSwRing * (kSwYBuf + kSwXBuf) + a.steptab_bytes;
-    if (smem <= 160 * 1024) {
+    {
       const int grid = wgrad_split_grid(a, pp_units, workspace, workspace_bytes);
 #ifdef OS2S_SW_ABLATE      // measurement build only (tools/sw_ablate.py): the stream with one ingredient removed
       switch (g_wgrad_sw_ablate) {
-        case 1: OS2S_LAUNCH_LDS(conv1d_wgrad_sw_kernel<1>, dim3(grid), dim3(256), smem, (hipStream_t)stream, a); return OS2S_OK;
-        case 2: OS2S_LAUNCH_LDS(conv1d_wgrad_sw_kernel<2>, dim3(grid), dim3(256), smem, (hipStream_t)stream, a); return OS2S_OK;
-        case 3: OS2S_LAUNCH_LDS(conv1d_wgrad_sw_kernel<3>, dim3(grid), dim3(256), smem, (hipStream_t)stream, a); return OS2S_OK;
-        case 4: OS2S_LAUNCH_LDS(conv1d_wgrad_sw_kernel<4>, dim3(grid), dim3(256), smem, (hipStream_t)stream, a); return OS2S_OK;
-        case 5: OS2S_LAUNCH_LDS(conv1d_wgrad_sw_kernel<5>, dim3(grid), dim3(256), smem, (hipStream_t)stream, a); return OS2S_OK;
-        case 8: OS2S_LAUNCH_LDS(conv1d_wgrad_sw_kernel<8>, dim3(grid), dim3(256), smem, (hipStream_t)stream, a); return OS2S_OK;
+        case 1: OS2S_LAUNCH_LDS(conv1d_wgrad_sw_kernel<1>, dim3(grid), dim3(256), tq_smem, (hipStream_t)stream, a); return OS2S_OK;
+        case 2: OS2S_LAUNCH_LDS(conv1d_wgrad_sw_kernel<2>, dim3(grid), dim3(256), tq_smem, (hipStream_t)stream, a); return OS2S_OK;
+        case 3: OS2S_LAUNCH_LDS(conv1d_wgrad_sw_kernel<3>, dim3(grid), dim3(256), tq_smem, (hipStream_t)stream, a); return OS2S_OK;
+        case 4: OS2S_LAUNCH_LDS(conv1d_wgrad_sw_kernel<4>, dim3(grid), dim3(256), tq_smem, (hipStream_t)stream, a); return OS2S_OK;
+        case 5: OS2S_LAUNCH_LDS(conv1d_wgrad_sw_kernel<5>, dim3(grid), dim3(256), tq_smem, (hipStream_t)stream, a); return OS2S_OK;
+        case 8: OS2S_LAUNCH_LDS(conv1d_wgrad_sw_kernel<8>, dim3(grid), dim3(256), tq_smem, (hipStream_t)stream, a); return OS2S_OK;
         default: break;
       }
 #endif
-      OS2S_LAUNCH_LDS(conv1d_wgrad_sw_kernel<0>, dim3(grid), dim3(256), smem, (hipStream_t)stream, a);
+      OS2S_LAUNCH_LDS(conv1d_wgrad_sw_kernel<0>, dim3(grid), dim3(256), tq_smem, (hipStream_t)stream, a);
       return OS2S_OK;
     }
   }
 
-  if (pp_shape && g_wgrad_variant != 0 && (groups || g_wgrad_variant == 1 || pp_units >= g_wgrad_pp_min_units)) {
+  if (choice == kWgradPingPong) {
     wgrad_tap_quad_geometry(a, 24 * 1024);              // 3 DMA rounds of 8 waves x 1 KB
-    const size_t smem = (size_t)2 * 64 * 256 + (size_t)3 * a.xbuf_bytes + a.steptab_bytes + (a.dbg ? 2 * 48 * 10 * 8 : 0);
-    if (smem <= 160 * 1024) {
+    {
       const int grid = wgrad_split_grid(a, a.NG * pp_units, workspace, workspace_bytes);
       if (a.dbg) {
-        OS2S_LAUNCH_LDS(conv1d_wgrad_pp_kernel<true>, dim3(grid), dim3(512), smem, (hipStream_t)stream, a);
+        OS2S_LAUNCH_LDS(conv1d_wgrad_pp_kernel<true>, dim3(grid), dim3(512), tq_smem, (hipStream_t)stream, a);
       } else {
-        OS2S_LAUNCH_LDS(conv1d_wgrad_pp_kernel<false>, dim3(grid), dim3(512), smem, (hipStream_t)stream, a);
+        OS2S_LAUNCH_LDS(conv1d_wgrad_pp_kernel<false>, dim3(grid), dim3(512), tq_smem, (hipStream_t)stream, a);
       }
       return OS2S_OK;
     }
@@ -1385,6 +1408,20 @@ static int conv1d_wgrad_impl_g(os2s_stream_t stream, const uint16_t* x, long lon
                 (const float*)a.part, dw, dw_elems, a.NSPLIT);
   }
   return OS2S_OK;
+}
+
+// Would os2s_conv1d_wgrad_ws hand this problem to a kernel that owns every dW element once (1) or not (0)? The caller
+// that may choose between accumulate = 0 and a zero fill + accumulate = 1 asks: the lockstep kernel splits the batch
+// over the chip only when it accumulates.
+extern "C" int os2s_conv1d_wgrad_single_owner(int B, int Tin, int Cin, int Cout, int K, int stride, int dil, int Tout,
+                                              long long x_row_stride) {
+  if (B < 1 || Tin < 1 || Tout < 1 || Cin < 8 || Cout < 8 || K < 1 || stride < 1 || dil < 1) return 0;
+  os2s::WgradArgs a = wgrad_args(nullptr, x_row_stride, nullptr, nullptr, nullptr, B, Tin, Cin, Cout, 0);
+  a.Tout = Tout; a.K = K; a.stride = stride; a.dil = dil;
+  a.dbg = g_wgrad_dbg;
+  int units = 0;
+  size_t smem = 0;
+  return wgrad_tap_quad_choice(a, x_row_stride, false, &units, &smem) != kWgradOther ? 1 : 0;
 }
 
 extern "C" int os2s_conv1d_wgrad_ws(os2s_stream_t stream, const uint16_t* x, long long x_row_stride,

@@ -95,46 +95,117 @@ __device__ float lr_policy_value(const os2s_opt_config_t& c, long long step) {
   }
 }
 
+// ---- sum of squares of one chunk held in registers (16 elements per thread, 256 threads) ---------------------
+// The ONE order in which a thread adds up the squares of its 16 values, written with explicit fused multiply-adds so
+// that no compiler decision is left in it: round(v1 * v1) first, then v0, v2, v3, ... v15 each with one fma. (It is
+// the order the statistics loop of the earlier versions compiled to — `s += v * v` over (i, e), whose first two terms
+// the compiler contracted as fma(v0, v0, v1 * v1) in both of its instantiations, read off their assembly. Checked
+// on the device for the LARC path only: a NovoGrad / LARC trajectory and the Jasper, DeepSpeech2 and NMT bench
+// losses are the earlier bits; the no-LARC Adam path is exercised by Transformer steps that are not reproducible
+// from run to run, so there the equality rests on the assembly alone.)
+__device__ __forceinline__ float thread_sum_squares(const f32x4 (&v)[kChunk / 4 / 256]) {
+  float s = v[0][1] * v[0][1];
+  s = __builtin_fmaf(v[0][0], v[0][0], s);
+  s = __builtin_fmaf(v[0][2], v[0][2], s);
+  s = __builtin_fmaf(v[0][3], v[0][3], s);
+#pragma unroll
+  for (int i = 1; i < kChunk / 4 / 256; ++i) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) s = __builtin_fmaf(v[i][e], v[i][e], s);
+  }
+  return s;
+}
+
+// The chunk's sum of w^2: thread_sum_squares, wave_sum, then the four waves in order. The statistics pass (weights read
+// from memory) and the update (weights it has just computed) both call it, so a sum cached by the update and one
+// recomputed from the stored weights are the same bits. Every thread of the workgroup must call it (one barrier); the
+// result is valid on thread 0.
+__device__ __forceinline__ float chunk_sum_squares(const f32x4 (&w)[kChunk / 4 / 256], float* red4) {
+  float s = wave_sum(thread_sum_squares(w));
+  if ((threadIdx.x & 63) == 0) red4[threadIdx.x >> 6] = s;
+  __syncthreads();
+  float b = 0.f;
+  if (threadIdx.x == 0) {
+    for (int k = 0; k < 4; ++k) b += red4[k];
+  }
+  return b;
+}
+
 // ---- pass 1: per-chunk statistics of the effective gradient ----------------
 // g_eff = g * inv_scale + l2[tensor] * w      (mp_wrapper.py:79-95)
 // partial[c] = {sum g_eff^2, sum w^2, max |g_eff|, nan flag}
-// NEED_W = false: no tensor has an l2 term and LARC is off — the weights are not read at all (a third of
-// this pass's 2.7 GB for Transformer-big; round 5)
-template <bool NEED_W>
+// Whether a chunk's weights are read is decided per workgroup (a workgroup is one chunk of one tensor, so the test
+// is uniform): the tensor has an l2 term, or its sum of w^2 is wanted and not known. tensor_need_w (one byte per
+// tensor; NULL: need_default for every tensor) says which tensors' weights may have changed since the update last
+// wrote partial_w[c] (mt_apply_kernel); for the others the cached sum is taken and only the gradient is read — for
+// Jasper (LARC, no l2) half of this pass's 2.7 GB. A chunk that does read its weights refreshes partial_w[c].
+// partial_w NULL: nothing is cached, a chunk that does not need its weights reports 0 (no LARC, no l2: round 5).
+// mismatch != NULL (checking mode): the weights are read for every chunk and a cached sum that differs from the
+// recomputed one in any bit is counted.
+// Block 0 also latches the scale the gradients in the buffer were produced with: every workgroup reads
+// st->loss_scale (unchanged until mt_finalize_kernel), nobody reads the latch before the update.
 __global__ __launch_bounds__(256) void mt_grad_stats_kernel(
     const float* __restrict__ grads, const float* __restrict__ weights,
     const int32_t* __restrict__ chunk_tensor, const float* __restrict__ tensor_l2,
-    const OptDeviceState* __restrict__ st, int world_size, float* __restrict__ partial) {
-  __shared__ float red[4][4];
+    OptDeviceState* __restrict__ st, int world_size, float* __restrict__ partial,
+    float* __restrict__ partial_w, const uint8_t* __restrict__ tensor_need_w, int need_default,
+    int* __restrict__ mismatch) {
+  constexpr int N = kChunk / 4 / 256;
+  __shared__ float red[4][3];
+  __shared__ float red_w[4];
   const int c = blockIdx.x;
   const int ti = chunk_tensor[c];
-  const float inv = 1.f / (st->grad_scale_latched * (float)world_size);
+  const float scale = st->loss_scale;
+  if (c == 0 && threadIdx.x == 0) st->grad_scale_latched = scale;
+  const float inv = 1.f / (scale * (float)world_size);
   const float l2 = tensor_l2 ? tensor_l2[ti] : 0.f;
+  const bool need_w = (tensor_need_w ? tensor_need_w[ti] != 0 : need_default != 0) || l2 != 0.f;
+  const bool read_w = need_w || (mismatch != nullptr && partial_w != nullptr);
   const f32x4* g4 = reinterpret_cast<const f32x4*>(grads + (long long)c * kChunk);
   const f32x4* w4 = reinterpret_cast<const f32x4*>(weights + (long long)c * kChunk);
-  float sg = 0.f, sw = 0.f, mx = 0.f, nan = 0.f;
+  f32x4 g[N], w[N];
 #pragma unroll
-  for (int i = 0; i < kChunk / 4 / 256; ++i) {
-    const f32x4 g = g4[i * 256 + threadIdx.x];
-    f32x4 w = {0.f, 0.f, 0.f, 0.f};
-    if (NEED_W) w = w4[i * 256 + threadIdx.x];
+  for (int i = 0; i < N; ++i) g[i] = g4[i * 256 + threadIdx.x];
+  if (read_w) {
+#pragma unroll
+    for (int i = 0; i < N; ++i) w[i] = w4[i * 256 + threadIdx.x];
+  } else {
+#pragma unroll
+    for (int i = 0; i < N; ++i) w[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+  }
+  // the effective gradient in place of g: one fma on the rounded l2 term where the weights count, a product otherwise
+  // (explicit, like the sums: the bits do not depend on what the compiler contracts)
+  float mx = 0.f, nan = 0.f;
+#pragma unroll
+  for (int i = 0; i < N; ++i) {
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-      const float ge = NEED_W ? g[e] * inv + l2 * w[e] : g[e] * inv;
-      sg += ge * ge;
-      sw += w[e] * w[e];
+      const float ge = need_w ? __builtin_fmaf(inv, g[i][e], l2 * w[i][e]) : inv * g[i][e];
+      g[i][e] = ge;
       mx = fmaxf(mx, fabsf(ge));   // fmaxf drops NaN -> tracked separately
       nan = (ge != ge) ? 1.f : nan;
     }
   }
-  sg = wave_sum(sg); sw = wave_sum(sw); mx = wave_max(mx); nan = wave_max(nan);
+  float sg = thread_sum_squares(g);
+  float sw = 0.f;
+  if (read_w) sw = chunk_sum_squares(w, red_w);     // (uniform per workgroup; valid on thread 0)
+  sg = wave_sum(sg); mx = wave_max(mx); nan = wave_max(nan);
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  if (lane == 0) { red[wid][0] = sg; red[wid][1] = sw; red[wid][2] = mx; red[wid][3] = nan; }
+  if (lane == 0) { red[wid][0] = sg; red[wid][1] = mx; red[wid][2] = nan; }
   __syncthreads();
   if (threadIdx.x == 0) {
-    float a = 0.f, b = 0.f, m = 0.f, n = 0.f;
-    for (int w = 0; w < 4; ++w) { a += red[w][0]; b += red[w][1]; m = fmaxf(m, red[w][2]); n = fmaxf(n, red[w][3]); }
-    partial[c * 4 + 0] = a; partial[c * 4 + 1] = b; partial[c * 4 + 2] = m; partial[c * 4 + 3] = n;
+    float a = 0.f, m = 0.f, n = 0.f;
+    for (int k = 0; k < 4; ++k) { a += red[k][0]; m = fmaxf(m, red[k][1]); n = fmaxf(n, red[k][2]); }
+    if (partial_w) {
+      if (need_w) {
+        partial_w[c] = sw;
+      } else {
+        const float cached = partial_w[c];
+        if (read_w && __float_as_uint(cached) != __float_as_uint(sw)) atomicAdd(mismatch, 1);
+        sw = cached;
+      }
+    }
+    partial[c * 4 + 0] = a; partial[c * 4 + 1] = sw; partial[c * 4 + 2] = m; partial[c * 4 + 3] = n;
   }
 }
 
@@ -315,14 +386,18 @@ __global__ __launch_bounds__(256) void mt_finalize_kernel(
 // after each, so that the next step's forward pass can start on the variables already updated). zero_grads: the
 // gradient chunk is written back as zeros once it has been read — the next step needs no separate fill of the
 // gradient buffer, which would have to wait for the whole apply pass (a skipped step zeroes without applying).
+// partial_w != NULL: the chunk's sum of the NEW w^2 is left in partial_w[c] for the next step's statistics pass
+// (chunk_sum_squares: the bits that pass would compute from the stored weights). A skipped step returns before the
+// write: the weights did not change, the entry stays valid.
 template <int OPT>
 __global__ __launch_bounds__(256) void mt_apply_kernel(
     float* __restrict__ grads, float* __restrict__ weights, float* __restrict__ m1,
     float* __restrict__ m2, bf16_t* __restrict__ w16, const int32_t* __restrict__ chunk_tensor,
     const float* __restrict__ tensor_l2, const float* __restrict__ tensor_mult,
     const float* __restrict__ tensor_wd_mask, os2s_opt_config_t cfg,
-    const OptDeviceState* __restrict__ st, int chunk0, int zero_grads) {
+    const OptDeviceState* __restrict__ st, int chunk0, int zero_grads, float* __restrict__ partial_w) {
   constexpr int N = kChunk / 4 / 256;
+  __shared__ float red_w[4];
   const int c = blockIdx.x + chunk0;
   if (st->skip) {
     if (zero_grads) {
@@ -391,10 +466,34 @@ __global__ __launch_bounds__(256) void mt_apply_kernel(
       __builtin_nontemporal_store(o, reinterpret_cast<u32x2*>(w16 + off));
     }
   }
+  if (partial_w) {      // (kernel argument: uniform)
+    const float sw = chunk_sum_squares(w, red_w);
+    if (threadIdx.x == 0) partial_w[c] = sw;
+  }
 }
 
-// remember the scale the current gradients were produced with
-__global__ void opt_latch_scale_kernel(OptDeviceState* st) { st->grad_scale_latched = st->loss_scale; }
+// Zero fill of the chunks of the tensors tensor_skip does not mark (one workgroup per chunk): the step-start fill of
+// the gradient buffer without the tensors whose producer overwrites its gradient on the first write of the step. A
+// workgroup of a skipped tensor returns at once, except the one of the tensor's last chunk: it zeroes the padding
+// behind the tensor's last element, which no producer writes and the statistics pass reads.
+__global__ __launch_bounds__(256) void fill_zero_chunks_kernel(float* __restrict__ buf,
+                                                               const int32_t* __restrict__ chunk_tensor,
+                                                               const uint8_t* __restrict__ tensor_skip,
+                                                               const int32_t* __restrict__ tensor_chunk_begin,
+                                                               const long long* __restrict__ tensor_numel) {
+  const int c = blockIdx.x;
+  const int t = chunk_tensor[c];
+  if (tensor_skip[t]) {
+    if (c != tensor_chunk_begin[t + 1] - 1) return;
+    const long long first = tensor_numel[t] - (long long)(c - tensor_chunk_begin[t]) * kChunk;   // in (0, kChunk]
+    float* p = buf + (long long)c * kChunk;
+    for (long long i = (first < 0 ? 0 : first) + threadIdx.x; i < kChunk; i += 256) p[i] = 0.f;
+    return;
+  }
+  f32x4* p = reinterpret_cast<f32x4*>(buf + (long long)c * kChunk);
+#pragma unroll
+  for (int i = 0; i < kChunk / 4 / 256; ++i) p[i * 256 + threadIdx.x] = f32x4{0.f, 0.f, 0.f, 0.f};
+}
 
 __global__ void opt_init_state_kernel(OptDeviceState* st, float loss_scale) {
   st->global_step = 0; st->scaler_iteration = 0; st->last_overflow_iteration = -1;
@@ -501,25 +600,24 @@ extern "C" int os2s_opt_init_state(os2s_stream_t stream, void* state, float loss
 //   partial: scratch [nchunks*4]; tensor_* arrays: [ntensors] (tensor_chunk_begin: [ntensors+1])
 // = os2s_opt_prepare (statistics of the gradient, overflow / skip decision, loss-scale update, learning rate, LARC /
 // NovoGrad factors: everything that needs ALL gradients) + os2s_opt_apply_range over all chunks.
-extern "C" int os2s_opt_prepare(os2s_stream_t stream_, const os2s_opt_config_t* cfg, void* state,
-                                const float* grads, const float* weights, int nchunks, int ntensors,
-                                const int32_t* chunk_tensor, const int32_t* tensor_chunk_begin,
-                                const float* tensor_l2, float* partial, float* tensor_gnorm2, float* tensor_wnorm2,
-                                float* tensor_amax, float* tensor_mult, float* tensor_v) {
+extern "C" int os2s_opt_prepare_cached(os2s_stream_t stream_, const os2s_opt_config_t* cfg, void* state,
+                                       const float* grads, const float* weights, int nchunks, int ntensors,
+                                       const int32_t* chunk_tensor, const int32_t* tensor_chunk_begin,
+                                       const float* tensor_l2, float* partial, float* tensor_gnorm2,
+                                       float* tensor_wnorm2, float* tensor_amax, float* tensor_mult, float* tensor_v,
+                                       float* partial_w, const uint8_t* tensor_need_w, int* mismatch) {
   OS2S_REQUIRE(cfg && state && grads && weights && chunk_tensor && tensor_chunk_begin);
   OS2S_REQUIRE(partial && tensor_gnorm2 && tensor_wnorm2 && tensor_amax && tensor_mult);
   OS2S_REQUIRE(nchunks >= 1 && ntensors >= 1 && cfg->world_size >= 1);
+  OS2S_REQUIRE(partial_w || (!tensor_need_w && !mismatch));
   if (cfg->optimizer == 2) OS2S_REQUIRE(tensor_v);
   hipStream_t stream = (hipStream_t)stream_;
   OptDeviceState* st = (OptDeviceState*)state;
-  OS2S_LAUNCH(opt_latch_scale_kernel, dim3(1), dim3(1), 0, stream, st);
-  if (tensor_l2 != nullptr || cfg->use_larc) {
-    OS2S_LAUNCH(mt_grad_stats_kernel<true>, dim3(nchunks), dim3(256), 0, stream, grads, weights,
-                chunk_tensor, tensor_l2, st, cfg->world_size, partial);
-  } else {
-    OS2S_LAUNCH(mt_grad_stats_kernel<false>, dim3(nchunks), dim3(256), 0, stream, grads, weights,
-                chunk_tensor, tensor_l2, st, cfg->world_size, partial);
-  }
+  // without a per-tensor mask: every tensor's weights are read when LARC wants their norms or any tensor has an l2
+  // term, none otherwise
+  const int need_default = (tensor_l2 != nullptr || cfg->use_larc) ? 1 : 0;
+  OS2S_LAUNCH(mt_grad_stats_kernel, dim3(nchunks), dim3(256), 0, stream, grads, weights, chunk_tensor, tensor_l2, st,
+              cfg->world_size, partial, partial_w, tensor_need_w, need_default, mismatch);
   OS2S_LAUNCH(mt_tensor_reduce_kernel, dim3(ntensors), dim3(256), 0, stream, partial,
               tensor_chunk_begin, tensor_gnorm2, tensor_wnorm2, tensor_amax, tensor_mult);
   OS2S_LAUNCH(mt_finalize_kernel, dim3(1), dim3(256), 0, stream, ntensors, *cfg, st,
@@ -527,11 +625,21 @@ extern "C" int os2s_opt_prepare(os2s_stream_t stream_, const os2s_opt_config_t* 
   return OS2S_OK;
 }
 
-extern "C" int os2s_opt_apply_range(os2s_stream_t stream_, const os2s_opt_config_t* cfg, const void* state,
-                                    float* grads, float* weights, float* m1, float* m2, uint16_t* w16,
-                                    int chunk_begin, int chunk_end, const int32_t* chunk_tensor,
-                                    const float* tensor_l2, const float* tensor_mult,
-                                    const float* tensor_wd_mask, int zero_grads) {
+extern "C" int os2s_opt_prepare(os2s_stream_t stream_, const os2s_opt_config_t* cfg, void* state,
+                                const float* grads, const float* weights, int nchunks, int ntensors,
+                                const int32_t* chunk_tensor, const int32_t* tensor_chunk_begin,
+                                const float* tensor_l2, float* partial, float* tensor_gnorm2, float* tensor_wnorm2,
+                                float* tensor_amax, float* tensor_mult, float* tensor_v) {
+  return os2s_opt_prepare_cached(stream_, cfg, state, grads, weights, nchunks, ntensors, chunk_tensor,
+                                 tensor_chunk_begin, tensor_l2, partial, tensor_gnorm2, tensor_wnorm2, tensor_amax,
+                                 tensor_mult, tensor_v, nullptr, nullptr, nullptr);
+}
+
+extern "C" int os2s_opt_apply_range_cached(os2s_stream_t stream_, const os2s_opt_config_t* cfg, const void* state,
+                                           float* grads, float* weights, float* m1, float* m2, uint16_t* w16,
+                                           int chunk_begin, int chunk_end, const int32_t* chunk_tensor,
+                                           const float* tensor_l2, const float* tensor_mult,
+                                           const float* tensor_wd_mask, int zero_grads, float* partial_w) {
   OS2S_REQUIRE(cfg && state && grads && weights && chunk_tensor && tensor_mult);
   OS2S_REQUIRE(chunk_begin >= 0 && chunk_end >= chunk_begin);
   if (cfg->optimizer != 0) OS2S_REQUIRE(m1);
@@ -542,7 +650,7 @@ extern "C" int os2s_opt_apply_range(os2s_stream_t stream_, const os2s_opt_config
   const int n = chunk_end - chunk_begin;
 #define OS2S_APPLY(OPT)                                                                    \
   OS2S_LAUNCH(mt_apply_kernel<OPT>, dim3(n), dim3(256), 0, stream, grads, weights, m1, m2, \
-              w16, chunk_tensor, tensor_l2, tensor_mult, tensor_wd_mask, *cfg, st, chunk_begin, zero_grads ? 1 : 0)
+              w16, chunk_tensor, tensor_l2, tensor_mult, tensor_wd_mask, *cfg, st, chunk_begin, zero_grads ? 1 : 0, partial_w)
   switch (cfg->optimizer) {
     case 0: OS2S_APPLY(0); break;
     case 1: OS2S_APPLY(1); break;
@@ -550,6 +658,24 @@ extern "C" int os2s_opt_apply_range(os2s_stream_t stream_, const os2s_opt_config
     default: OS2S_APPLY(3); break;
   }
 #undef OS2S_APPLY
+  return OS2S_OK;
+}
+
+extern "C" int os2s_opt_apply_range(os2s_stream_t stream_, const os2s_opt_config_t* cfg, const void* state,
+                                    float* grads, float* weights, float* m1, float* m2, uint16_t* w16,
+                                    int chunk_begin, int chunk_end, const int32_t* chunk_tensor,
+                                    const float* tensor_l2, const float* tensor_mult,
+                                    const float* tensor_wd_mask, int zero_grads) {
+  return os2s_opt_apply_range_cached(stream_, cfg, state, grads, weights, m1, m2, w16, chunk_begin, chunk_end,
+                                     chunk_tensor, tensor_l2, tensor_mult, tensor_wd_mask, zero_grads, nullptr);
+}
+
+extern "C" int os2s_fill_zero_chunks(os2s_stream_t stream, float* buf, int nchunks, const int32_t* chunk_tensor,
+                                     const uint8_t* tensor_skip, const int32_t* tensor_chunk_begin,
+                                     const long long* tensor_numel) {
+  OS2S_REQUIRE(buf && chunk_tensor && tensor_skip && tensor_chunk_begin && tensor_numel && nchunks >= 1);
+  OS2S_LAUNCH(fill_zero_chunks_kernel, dim3(nchunks), dim3(256), 0, (hipStream_t)stream, buf, chunk_tensor,
+              tensor_skip, tensor_chunk_begin, tensor_numel);
   return OS2S_OK;
 }
 

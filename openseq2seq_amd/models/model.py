@@ -279,10 +279,10 @@ class Model(object):
       iter_size = p.get('iter_size', 1)
       micro = self._step_count % iter_size
       if micro == 0:
-        if self._store.grads_zeroed:
-          self._store.grads_zeroed = False      # the asynchronous update zeroed each chunk behind its last read
-        else:
-          self._store.zero_grads()
+        # a new gradient epoch: the convolution kernels' first producers write their gradients, the rest of the
+        # buffer is zeroed in one launch — unless the asynchronous update zeroed each chunk behind its last read
+        self._store.begin_grad_epoch(already_zeroed=self._store.grads_zeroed)
+        self._store.grads_zeroed = False
       last_micro = (micro == iter_size - 1)
       overlap = self._reducer is not None and last_micro
       # what a persistent-GRU abort must be able to roll back (see _recover_gru_abort): the non-trainable state
@@ -297,7 +297,7 @@ class Model(object):
       if getattr(self, "_halves_enabled", None) is not None and self._halves_enabled():
         loss = self._forward_backward_halves(batch)          # experiment: two half-batches on two streams
       else:
-        tape = Tape(on_done=self._reducer.mark_done if overlap else None)
+        tape = Tape(on_done=self._grads_final if overlap else None)
         tape.defer_free = DEFER_TAPE_FREE
         loss = self._forward_backward(batch, tape)
         tape.backward()
@@ -313,6 +313,7 @@ class Model(object):
         loss = self._recover_gru_abort(batch, loss, snap, micro, overlap, ran_persistent)
       self._step_count += 1
       if last_micro:
+        self._store.finish_grad_epoch()        # (a layer the step did not run: nobody wrote its kernel's gradient)
         if self._reducer is not None:
           self._reducer.finish()
         # the update runs on its own stream next to the NEXT step's forward pass (TrainOp.run_async) unless
@@ -326,6 +327,12 @@ class Model(object):
     finally:
       set_side_stream_enabled(prev)
     return loss
+
+  def _grads_final(self, offset):
+    """Backward has passed every gradient at flat offsets >= `offset`: an overwrite_first gradient of a layer the step
+    did not run is zeroed before the reducer may all-reduce its bucket."""
+    self._store.finish_grad_epoch(offset)
+    self._reducer.mark_done(offset)
 
   def _has_gru_layers(self):
     """Does the configuration build cuDNN-form GRU layers (the only ones the persistent kernels take)?"""
@@ -380,7 +387,7 @@ class Model(object):
       self._store.grads.copy_(snap[1])
     else:
       raise RuntimeError("persistent GRU abort inside an accumulation window before a snapshot existed")
-    tape = Tape(on_done=self._reducer.mark_done if overlap else None)
+    tape = Tape(on_done=self._grads_final if overlap else None)
     loss = self._forward_backward(batch, tape)
     tape.backward()
     torch.cuda.current_stream().synchronize()

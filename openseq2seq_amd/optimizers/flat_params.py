@@ -18,8 +18,31 @@ import torch
 
 from .. import capi
 
+# A/B switches of the optimizer tail. They are host-side decisions about which entry point and which arguments a step
+# uses, so they live here and not in the library's option registry. Nothing is latched: a module attribute left at
+# None means "ask the environment now", every time the switch is read; True / False (tests, a driver) overrides it.
+# OS2S_OPT_CACHED_WNORM=0: the statistics pass reads every tensor's weights for LARC, as before the sums were cached
+CACHED_WNORM = None
+# OS2S_OPT_CHECK_WNORM=1: the statistics pass recomputes every cached sum as well and counts the ones that differ
+# (FlatParams.wnorm_mismatches())
+CHECK_WNORM = None
+# OS2S_GRAD_OVERWRITE=0: every gradient is accumulated into a buffer the step start has zeroed in full
+GRAD_OVERWRITE = None
 
-def _guarded(slot, wt=False):
+
+def cached_wnorm():
+  return os.environ.get("OS2S_OPT_CACHED_WNORM", "1") != "0" if CACHED_WNORM is None else bool(CACHED_WNORM)
+
+
+def check_wnorm():
+  return os.environ.get("OS2S_OPT_CHECK_WNORM", "0") == "1" if CHECK_WNORM is None else bool(CHECK_WNORM)
+
+
+def grad_overwrite():
+  return os.environ.get("OS2S_GRAD_OVERWRITE", "1") != "0" if GRAD_OVERWRITE is None else bool(GRAD_OVERWRITE)
+
+
+def _guarded(slot, wt=False, marks_w=False, is_grad=False):
   """A view into the flat buffers that the asynchronous optimizer (TrainOp.run_async) may still be writing: reading
   the attribute first makes the calling stream wait for the update range that holds the variable
   (FlatParams._ready). No update in flight: one list test."""
@@ -27,6 +50,13 @@ def _guarded(slot, wt=False):
     st = self.store
     if st is not None and (st._pending or st._wt_event is not None):
       st._ready(self, wt)
+    if marks_w:
+      self.need_w = True        # whoever holds the view may write: the cached sums of w^2 are not trusted
+    elif is_grad and self.overwrite_first and st is not None and self.grad_epoch != st.grad_epoch:
+      # The view of a gradient nobody has zeroed or written in this epoch: whoever takes it (a foreign producer that
+      # adds to it, a reader) finds zeros. This is the safety net, not the protocol: a producer asks prepare_grad
+      # first. Either order is correct — taking the view first only turns the overwrite into zero + accumulate.
+      st.prepare_grad(self, can_overwrite=False, keep=True)
     return getattr(self, slot)
 
   def put(self, value):
@@ -36,9 +66,10 @@ def _guarded(slot, wt=False):
 
 class Param(object):
   __slots__ = ("name", "shape", "index", "offset", "numel", "l2", "kind", "store",
-               "_master", "_grad", "_w16", "_wt16", "wt_offset", "trainable_mask", "logical_out", "logical_in")
-  master = _guarded("_master")
-  grad = _guarded("_grad")
+               "_master", "_grad", "_w16", "_wt16", "wt_offset", "trainable_mask", "logical_out", "logical_in",
+               "need_w", "overwrite_first", "grad_epoch")
+  master = _guarded("_master", marks_w=True)
+  grad = _guarded("_grad", is_grad=True)
   w16 = _guarded("_w16")
   wt16 = _guarded("_wt16", wt=True)
 
@@ -53,13 +84,22 @@ class Param(object):
     self.logical_in = None
     self.store = None
     self._master = self._grad = self._w16 = self._wt16 = None
+    # need_w: the weights may have changed since the optimizer last left their sum of squares in store.partial_w (set
+    # by every read of the public `master` attribute, cleared by the update). overwrite_first: the first producer of
+    # this gradient in a step writes it instead of adding to it, the step start does not zero it
+    # (FlatParams.prepare_grad); grad_epoch: the gradient epoch of the store in which it was last written that way.
+    self.need_w = True
+    self.overwrite_first = False
+    self.grad_epoch = -1
 
 
-def _whole(slot):
+def _whole(slot, marks_w=False):
   """A whole flat buffer: the reader waits for everything the asynchronous optimizer has in flight."""
   def get(self):
     if self._pending or self._wt_event is not None:
       self.wait_all()
+    if marks_w:
+      self.invalidate_wnorm()
     return getattr(self, slot)
 
   def put(self, value):
@@ -70,7 +110,7 @@ def _whole(slot):
 class FlatParams(object):
   """kind: 'conv' ([K,Cout,Cin], gets a dgrad copy), 'dense', 'vector' (BN/bias)."""
 
-  master = _whole("_master")
+  master = _whole("_master", marks_w=True)
   grads = _whole("_grads")
   m1 = _whole("_m1")
   m2 = _whole("_m2")
@@ -86,6 +126,7 @@ class FlatParams(object):
     self._pending, self._wt_event, self._main_stream, self._opt_stream = [], None, None, None
     self._done_upto = 0               # elements of the flat buffers the current stream has already waited for
     self.grads_zeroed = False
+    self.grad_epoch = 0               # advanced where a step zeroes its gradients (begin_grad_epoch)
     self._master = self._grads = self._m1 = self._m2 = self._w16 = self._wt16 = self._t_v = None
     self.params = []
     self.state = {}       # named non-trainable variables (BatchNorm moving statistics)
@@ -143,6 +184,16 @@ class FlatParams(object):
     # knows; a caller that writes into tensor_l2 afterwards sets this flag too)
     self.l2_active = any(float(p.l2) != 0.0 for p in self.params)
     self.partial = torch.zeros(off // ch * 4, dtype=torch.float32, device=dev)
+    # per-chunk sums of w^2 the update leaves for the next step's statistics pass (LARC), the per-tensor "read the
+    # weights" mask on the device with the host copy it was uploaded from, the checking mode's counter; and the
+    # per-tensor "not part of the step-start fill" mask of the gradient buffer
+    self.partial_w = torch.zeros(off // ch, dtype=torch.float32, device=dev)
+    self._need_w_dev = torch.ones(max(nt, 1), dtype=torch.uint8, device=dev)
+    self._need_w_sent = b"\x01" * nt
+    self._wnorm_mismatch = torch.zeros(1, dtype=torch.int32, device=dev)
+    self._skip_fill_dev = torch.zeros(max(nt, 1), dtype=torch.uint8, device=dev)
+    self._skip_fill_sent = b"\x00" * nt
+    self.tensor_numel = torch.tensor([p.numel for p in self.params], dtype=torch.int64, device=dev)
     self.t_gnorm2 = torch.zeros(nt, dtype=torch.float32, device=dev)
     self.t_wnorm2 = torch.zeros(nt, dtype=torch.float32, device=dev)
     self.t_amax = torch.zeros(nt, dtype=torch.float32, device=dev)
@@ -173,7 +224,7 @@ class FlatParams(object):
 
   def refresh_compute_copies(self):
     """master fp32 -> bf16 compute copy (+ the conv dgrad copies)."""
-    capi.cast_f32_to_bf16(self.master, self.w16)
+    capi.cast_f32_to_bf16(self.master, self.w16)     # (reading `master` marks every tensor "need w")
     self.refresh_dgrad_copies()
 
   def refresh_dgrad_copies(self):
@@ -193,7 +244,99 @@ class FlatParams(object):
                                   self._wt_tiles)
 
   def zero_grads(self):
+    """The full fill. It starts a gradient epoch as well: the producers that can overwrite do so after every fill,
+    so that two passes over one store take the same kernels' paths."""
+    self.grad_epoch += 1
     self.grads.zero_()
+
+  # ---- cached sums of w^2 (LARC) ------------------------------------------------------------------------------
+  def invalidate_wnorm(self):
+    """Every tensor's weights may have changed behind the optimizer's back."""
+    for p in self.params:
+      p.need_w = True
+
+  def _mask(self, flags, dev_tensor, sent):
+    """The device copy of a per-tensor byte mask, uploaded (pinned, non-blocking, on the current stream) only when
+    the host set differs from the one last sent. Returns (device tensor, the bytes now on the device)."""
+    cur = bytes(bytearray(flags))
+    if cur != sent:
+      host = torch.frombuffer(bytearray(cur), dtype=torch.uint8)
+      if dev_tensor.is_cuda:
+        host = host.pin_memory()
+      dev_tensor.copy_(host, non_blocking=True)
+    return dev_tensor, cur
+
+  def need_w_mask(self):
+    """uint8 [ntensors] on the device: 1 = the statistics pass reads the tensor's weights. Call on the stream the
+    optimizer runs on."""
+    m, self._need_w_sent = self._mask([p.need_w for p in self.params], self._need_w_dev, self._need_w_sent)
+    return m
+
+  def weights_updated(self):
+    """An update that covered every tensor (and left its sums in partial_w) has been enqueued."""
+    for p in self.params:
+      p.need_w = False
+
+  def wnorm_check_buffer(self):
+    return self._wnorm_mismatch if check_wnorm() else None
+
+  def wnorm_mismatches(self):
+    """Checking mode: cached sums that differed from the recomputed ones so far (synchronises)."""
+    self.wait_all()
+    return int(self._wnorm_mismatch.item())
+
+  # ---- gradients written, not accumulated, by their first producer of a step -------------------------------------
+  def begin_grad_epoch(self, already_zeroed=False):
+    """Start of a step's (or accumulation window's) gradients: a new epoch, and the zero fill of every gradient but
+    those whose first producer overwrites (one launch). already_zeroed: the asynchronous update zeroed the buffer."""
+    self.grad_epoch += 1
+    on = grad_overwrite()
+    # (ascending flat offsets; finish_grad_epoch walks them from the top as backward declares ranges final)
+    self._unfinished = [p for p in self.params if p.overwrite_first] if on else []
+    if already_zeroed:
+      return
+    skip = [on and p.overwrite_first for p in self.params]
+    if not any(skip):
+      self.zero_grads()
+      return
+    m, self._skip_fill_sent = self._mask(skip, self._skip_fill_dev, self._skip_fill_sent)
+    capi.fill_zero_chunks(self.grads, self.chunk_tensor, m, self.tensor_chunk_begin, self.tensor_numel)
+
+  def prepare_grad(self, p, can_overwrite=True, keep=False):
+    """The `accumulate` flag for a producer of p's gradient, called on the producer's stream right before its
+    launch (and before the producer takes `p.grad`). False: this is the first write of an overwrite_first gradient
+    in this epoch and the producer can write instead of add — nothing zeroed the gradient. A producer that cannot
+    (a grouped or deferred launch) gets the gradient zeroed here, on its stream, and the variable joins the
+    step-start fill from the next step on (keep: it does not — an occasional access, not the layer's producer)."""
+    if not self.overwrites(p):
+      return True
+    p.grad_epoch = self.grad_epoch
+    if can_overwrite:
+      return False
+    if not keep:
+      p.overwrite_first = False
+    if self._pending:
+      self._ready(p)                # (an asynchronous update may still be reading or zeroing the range)
+    p._grad.zero_()
+    return True
+
+  def overwrites(self, p):
+    """Is the next producer of p's gradient the first of an overwrite_first gradient in this epoch?"""
+    return p.overwrite_first and p.grad_epoch != self.grad_epoch and grad_overwrite()
+
+  def finish_grad_epoch(self, offset=0):
+    """Every gradient at flat offsets >= `offset` is final (backward has passed them; 0: before the optimizer or the
+    last all-reduce reads the buffer): an overwrite_first gradient among them that no producer wrote in this epoch —
+    a layer the step did not run — was not zeroed by anybody, and is zeroed here, BEFORE the range is handed to a
+    gradient reducer. Each variable is looked at once per epoch; no device work in the normal case."""
+    todo = getattr(self, "_unfinished", None)
+    if todo is None:                  # no begin_grad_epoch yet (a hand-written step after zero_grads())
+      todo = self._unfinished = [p for p in self.params if p.overwrite_first] if grad_overwrite() else []
+    while todo and todo[-1].offset >= offset:
+      p = todo.pop()
+      if p.overwrite_first and p.grad_epoch != self.grad_epoch:
+        p._grad.zero_()
+        p.grad_epoch = self.grad_epoch
 
   # ---- readiness of the variables while an asynchronous update is in flight ---------------------------------
   def _streams(self):

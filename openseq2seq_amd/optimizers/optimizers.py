@@ -17,6 +17,7 @@ import torch
 
 from .. import capi
 from ..utils.utils import check_params
+from . import flat_params
 from . import lr_policies
 from .automatic_loss_scaler import AutomaticLossScaler
 from .novograd import NovoGrad
@@ -116,11 +117,31 @@ class TrainOp(object):
     self.loss_scale_view = self.state[32:36].view(torch.float32)
     self.lr_view = self.state[36:40].view(torch.float32)
 
+  def _wnorm_cache(self):
+    """Keyword arguments of the statistics pass and of the update: with LARC the per-chunk sums of w^2 come from
+    the previous update (store.partial_w) for every tensor nobody can have written since; () when nothing is
+    cached (no LARC: no weight norm is needed; flat_params.cached_wnorm() off: every tensor's weights are read)."""
+    s = self.store
+    if not (self.cfg.use_larc and flat_params.cached_wnorm()):
+      return {}, {}
+    return (dict(partial_w=s.partial_w, need_w=s.need_w_mask(), mismatch=s.wnorm_check_buffer()),
+            dict(partial_w=s.partial_w))
+
+  def _updated(self, cached):
+    s = self.store
+    if cached:
+      s.weights_updated()           # partial_w holds every tensor's sum (a skipped step left weights and sums alone)
+    else:
+      s.invalidate_wnorm()          # this update left nothing in partial_w
+
   def run(self):
     s = self.store
-    capi.opt_step(self.cfg, self.state, s.grads, s.master, s.m1, s.m2, s.w16,
+    s.wait_all()                    # (the raw buffers below: `s.master` would mark every tensor as written)
+    prep, _ = self._wnorm_cache()
+    capi.opt_step(self.cfg, self.state, s._grads, s._master, s._m1, s._m2, s._w16,
                   s.chunk_tensor, s.tensor_chunk_begin, s.tensor_l2 if s.l2_active else None, None, s.partial,
-                  s.t_gnorm2, s.t_wnorm2, s.t_amax, s.t_mult, s.t_v)
+                  s.t_gnorm2, s.t_wnorm2, s.t_amax, s.t_mult, s._t_v, **prep)
+    self._updated(bool(prep))
     s.refresh_dgrad_copies()
 
   def run_async(self, nranges=8):
@@ -143,15 +164,18 @@ class TrainOp(object):
     bounds = [(nchunks * i) // nranges for i in range(nranges + 1)]
     pending = []
     with torch.cuda.stream(side):
+      prep, apply = self._wnorm_cache()
       capi.opt_prepare(self.cfg, self.state, s._grads, s._master, s.chunk_tensor, s.tensor_chunk_begin,
                        s.tensor_l2 if s.l2_active else None, s.partial, s.t_gnorm2, s.t_wnorm2, s.t_amax,
-                       s.t_mult, s._t_v)
+                       s.t_mult, s._t_v, **prep)
       for c0, c1 in zip(bounds[:-1], bounds[1:]):
         capi.opt_apply_range(self.cfg, self.state, s._grads, s._master, s._m1, s._m2, s._w16, c0, c1,
-                             s.chunk_tensor, s.tensor_l2 if s.l2_active else None, s.t_mult, zero_grads=True)
+                             s.chunk_tensor, s.tensor_l2 if s.l2_active else None, s.t_mult, zero_grads=True,
+                             **apply)
         ev = torch.cuda.Event()
         ev.record(side)
         pending.append((c1 * s.chunk, ev))
+      self._updated(bool(prep))
       s.version = getattr(s, "version", 0) + 1
       s._refresh_dgrad_copies_raw()
       evw = torch.cuda.Event()

@@ -77,6 +77,8 @@ class ConvBN(object):
     self._set_geometry(name, cin, cout, k, stride, dilation, padding)
     self.momentum, self.eps = bn_momentum, bn_epsilon
     self.kernel = store.add(name + "/kernel", (k, cout, cin), initializer, kind="conv", l2=l2)
+    # its weight gradient is written, not accumulated, by the first producer of a step (FlatParams.prepare_grad)
+    self.kernel.overwrite_first = True
     self._add_bn(store, bn_name, cout, l2)
 
   def _set_geometry(self, name, cin, cout, k, stride, dilation, padding):
@@ -140,6 +142,7 @@ class ConvBN(object):
       # (the envelope of the ping-pong weight-gradient kernel; everything else goes out alone as before)
       key = (tuple(x.shape), tuple(dy.shape), x.stride(1), self.k, self.dil, f["pad_left"],
              None if inp.lens is None else inp.lens.data_ptr())
+      self.kernel.store.prepare_grad(self.kernel, can_overwrite=False)     # (a grouped launch accumulates)
       tape.defer_conv_wgrad(self.kernel, key, dict(x=x, dy=dy, dw=self.kernel.grad), units,
                             dict(K=self.k, stride=1, dil=self.dil, pad_left=f["pad_left"], in_len=inp.lens))
       return
@@ -147,9 +150,17 @@ class ConvBN(object):
     _WGRAD_RR += 1
     # (experiment, OS2S_WGRAD_STREAMS=2: the layers' weight gradients alternate between two side streams)
     with on_side_stream(dy.device, inp.data, dy, which=0 if WGRAD_STREAMS < 2 else (0, 2)[_WGRAD_RR & 1]):
+      # The first write of a step overwrites where a kernel with one owner per dW element takes the layer (the
+      # ping-pong kernel: the same bits as 0 + x) — the launcher's own decision, asked of the library. The lockstep
+      # kernel (strided, K = 1, narrow or small layers) splits the batch over the chip only when it accumulates:
+      # those layers keep their zero fill.
+      store = self.kernel.store
+      owner = store.overwrites(self.kernel) and x.dim() == 3 and \
+          capi.conv1d_wgrad_single_owner(x, dy, self.k, stride=self.stride, dil=self.dil)
+      accumulate = store.prepare_grad(self.kernel, can_overwrite=owner)
       capi.conv1d_wgrad(inp.data, dy, self.k, stride=self.stride, dil=self.dil,
                         pad_left=f["pad_left"], in_len=inp.lens, out=self.kernel.grad,
-                        accumulate=True)
+                        accumulate=accumulate)
 
   def backward_branch(self, inp, dy, f, final=False):
     """Weight and data gradients of the convolution given dy = d(conv output). Nothing in the
@@ -492,6 +503,8 @@ def conv_bn_res_bn_actv(main, res_branches, x, res_inputs, out_lens, activation_
       # the K = 1 weight gradients of all branches in one launch, on the side stream like every
       # parameter gradient (ConvBN.backward_branch)
       with on_side_stream(dz.device, *([w[1].data for w in wgrouped] + [w[2] for w in wgrouped])):
+        for br, _, _ in wgrouped:           # (the grouped launch accumulates)
+          br.kernel.store.prepare_grad(br.kernel, can_overwrite=False)
         for i0 in range(0, len(wgrouped), 16):
           capi.conv1x1_wgrad_grouped([dict(x=inp.data, dy=dy, dw=br.kernel.grad)
                                       for br, inp, dy in wgrouped[i0:i0 + 16]], in_len=wgrouped[0][1].lens,

@@ -208,6 +208,7 @@ class DenseResidualPass(object):
     if self.dzcat is None:
       self.dzcat = torch.empty((self.B, self.T, plan.dtot), dtype=torch.bfloat16, device=dz.device)
     for br in E.branches:
+      br.kernel.store.prepare_grad(br.kernel, can_overwrite=False)       # (dres_bn_bwd accumulates)
       br.kernel.grad, br.gamma.grad, br.beta.grad
     # (dz_lens: dz came out of a data-gradient epilogue that writes the live windows only — rows past a sequence
     # end are unwritten memory: masked here; the TN GEMM below visits live 64-row chunks only)

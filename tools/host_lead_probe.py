@@ -1,5 +1,5 @@
 """Is the GPU waiting for the HOST at the optimizer of a train step? (profiles/r05_gpu_idle_gaps.txt: 0.27-0.33 ms of
-idle GPU per step end exactly where opt_latch_scale_kernel, the optimizer's first kernel, starts — in Jasper AND in
+idle GPU per step end exactly where the optimizer's first kernel (mt_grad_stats_kernel; opt_latch_scale_kernel when this was measured) starts — in Jasper AND in
 Transformer-big.) For N steps: an event is recorded on the main stream after Tape.backward returned (everything of the
 backward pass enqueued, side streams joined); right before the optimizer is enqueued the host asks whether that event
 has already completed. "done" = the GPU had finished the backward pass before the host got to the optimizer: the gap is

@@ -1,5 +1,5 @@
 """Print the kernels around the optimizer's first launch of a step from a rocprofv3 --kernel-trace CSV: start / end
-(us, relative), queue, name — to see what the GPU does in the 0.3 ms before opt_latch_scale_kernel.
+(us, relative), queue, name — to see what the GPU does in the 0.3 ms before mt_grad_stats_kernel, the optimizer's first kernel.
 Usage: python tools/trace_tail.py <kernel_trace.csv> [n_before] [n_after]"""
 import csv
 import sys
@@ -12,7 +12,7 @@ with open(path) as f:
   for r in csv.DictReader(f):
     rows.append((int(r["Start_Timestamp"]), int(r["End_Timestamp"]), r["Kernel_Name"], r["Queue_Id"]))
 rows.sort()
-marks = [i for i, r in enumerate(rows) if "opt_latch_scale_kernel" in r[2]]
+marks = [i for i, r in enumerate(rows) if "mt_grad_stats_kernel" in r[2]]
 for m in marks[2:4]:
   t0 = rows[m][0]
   print("---- step ending at row %d" % m)
