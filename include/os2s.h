@@ -1078,9 +1078,14 @@ int os2s_embed_wdrop_bwd(os2s_stream_t stream, const int32_t* ids, const uint16_
  * cum_seq, whose row t+1 then repeats row t.
  * Dropout masks come from the library's counter hash: attention-input dropout indexes the
  * logical [B, T+1, M] tensor (row t+1 = attention_t), output dropout [B, T, H] per layer.
- * Limits: H % 8 == 0, M % 8 == 0, U % 128 == 0 and <= 512; location-sensitive mode:
- * U == 128, loc_k <= 32. Luong with U != H has no query layer to bridge the two widths:
- * OS2S_ERR_UNSUPPORTED.
+ * Limits: H % 8 == 0, M % 8 == 0, U % 8 == 0 and 8 <= U <= 1024 (else OS2S_ERR_INVALID_ARG);
+ * location-sensitive mode: U == 128, loc_k <= 32. Luong with U != H has no query layer to bridge
+ * the two widths: OS2S_ERR_UNSUPPORTED. Modes 0, 1, 3 take any source length whose per-sample LDS
+ * footprint fits, judged per pass (forward calls by the forward footprint): the keys of a sample
+ * stay in LDS while S * U allows and are streamed from global memory otherwise, with bit-identical
+ * results; S <= 1024 is guaranteed for H, M, U <= 1024, beyond the streamed footprint the call
+ * returns OS2S_ERR_UNSUPPORTED. The backward scratch dpre_seq is bf16 [B, T, S, U]: 164 MB at
+ * B 32, T 50, S 50, U 1024.
  * Zoneout (parts/rnns/zoneout.py:39-68, wired per layer by parts/rnns/utils.py:68-89): the wrapped
  * cell's OUTPUT stays the new h (what the layer above, the query layer and the output dropout read);
  * only the STATE (c, h) the same cell reads at step t+1 is replaced. With p = zoneout_prob:

@@ -145,18 +145,28 @@ __device__ long long g_attn_dbg[2][16];
 // LDS carve-up (floats) shared by the forward and backward attention kernels
 struct AttnLds {
   float *hq, *q, *nv, *bs, *e, *red, *cum, *scratch;
-  uint32_t* keys;   // [S][U/2] bf16 pairs of this sample's keys (staged once per launch)
+  uint32_t* keys;   // resident: [S][U/2] bf16 pairs of this sample's keys (staged once per launch);
+                    // streamed: [kAttnWaves][U/2], the key row each wave is working on
 };
 constexpr int kCtxSplitMax = 8;
-__host__ __device__ inline size_t attn_lds_floats(int H, int M, int U, int S, int mode, int K, bool bwd) {
-  size_t n = (size_t)H + 3 * U + S + 64 + (size_t)S * U / 2;
+// Two residency modes of the keys in the one-workgroup-per-sample kernels (non-location modes). Resident: all
+// S rows of the sample are staged in LDS before the score loop. Streamed: a wave fetches the row of its source
+// position from global memory with 16-byte loads (the next row is in flight while the current one is used) and
+// passes it through a row buffer of its own, because the score loops give a lane the unit pairs 2*lane + 128*i
+// — a 4-byte interleave — while a 16-byte load delivers four neighbouring pairs. Every key element is read once
+// per launch in both modes, the loops read the same pairs in the same order, so the results are bit-identical;
+// the streamed footprint does not grow with S * U.
+__host__ __device__ inline size_t attn_lds_floats(int H, int M, int U, int S, int mode, int K, bool bwd,
+                                                  bool resident = true) {
+  size_t n = (size_t)H + 3 * U + S + 64 + (resident ? (size_t)S * U / 2 : (size_t)kAttnWaves * U / 2);
   if (mode == 2) n += (size_t)(S + kLocKMax);
   size_t scratch = (size_t)kCtxSplitMax * M;     // forward: context partials
   if (bwd)   // dctx, dalign, de, dcum, dq/dnv partials, dWck
     scratch = (size_t)M + 3 * S + 2 * (size_t)kAttnWaves * U + (mode == 2 ? (size_t)K * U : 0);
   return n + scratch + 64;
 }
-__device__ __forceinline__ AttnLds attn_lds_carve(float* base, int H, int U, int S, int mode, int K) {
+__device__ __forceinline__ AttnLds attn_lds_carve(float* base, int H, int U, int S, int mode, int K,
+                                                  bool resident = true) {
   AttnLds l;
   l.hq = base; base += H;
   l.q = base; base += U;
@@ -166,7 +176,7 @@ __device__ __forceinline__ AttnLds attn_lds_carve(float* base, int H, int U, int
   l.red = base; base += 64;
   l.cum = nullptr;
   if (mode == 2) { l.cum = base; base += S + kLocKMax; }
-  l.keys = reinterpret_cast<uint32_t*>(base); base += (size_t)S * U / 2;
+  l.keys = reinterpret_cast<uint32_t*>(base); base += resident ? (size_t)S * U / 2 : (size_t)kAttnWaves * U / 2;
   l.scratch = base;
   return l;
 }
@@ -210,12 +220,36 @@ __device__ __forceinline__ void attn_load_cum(const AdAttn& p, const AttnLds& l,
   }
 }
 
-// pre-activation of the score for (s, unit pair u, u+1) without the location term
-__device__ __forceinline__ void attn_pre2(const AdAttn& p, const AttnLds& l, int b, int s, int u,
-                                          float& x0, float& x1) {
-  const uint32_t kv = l.keys[(s * p.U + u) >> 1];
+// pre-activation of the score for (s, unit pair u, u+1) without the location term; krow = the U/2 pairs of row s
+__device__ __forceinline__ void attn_pre2(const AttnLds& l, const uint32_t* krow, int u, float& x0, float& x1) {
+  const uint32_t kv = krow[u >> 1];
   x0 = bflo(kv) + l.q[u] + l.bs[u];
   x1 = bfhi(kv) + l.q[u + 1] + l.bs[u + 1];
+}
+
+// Streamed keys: the 16-byte pieces of one key row that a lane fetches (U <= 1024: at most 128 pieces, two per
+// lane). attn_row_fetch issues the loads (addresses clamped, never under a branch on the data), attn_row_put
+// hands the row to the wave's LDS row buffer. LDS operations of one wave complete in order; the wave barriers
+// only keep the compiler from moving a lane's reads across another lane's writes.
+constexpr int kRowPieces = 2;
+struct AttnRow { u32x4 v[kRowPieces]; };
+__device__ __forceinline__ AttnRow attn_row_fetch(const AdAttn& p, int b, int s) {
+  const int lane = threadIdx.x & 63, n16 = p.U / 8;
+  const u32x4* src = reinterpret_cast<const u32x4*>(p.keys + ((long long)b * p.S + s) * p.U);
+  AttnRow r;
+#pragma unroll
+  for (int i = 0; i < kRowPieces; ++i) r.v[i] = src[min(lane + 64 * i, n16 - 1)];
+  return r;
+}
+__device__ __forceinline__ void attn_row_put(const AdAttn& p, uint32_t* krow, const AttnRow& r) {
+  const int lane = threadIdx.x & 63, n16 = p.U / 8;
+  __builtin_amdgcn_wave_barrier();       // the reads of the previous row come first
+#pragma unroll
+  for (int i = 0; i < kRowPieces; ++i)
+    if (lane + 64 * i < n16) reinterpret_cast<u32x4*>(krow)[lane + 64 * i] = r.v[i];
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
 // finished sample (t >= tgt_len[b]) in location mode: the cumulative alignments carry over, row t + 1 =
@@ -227,12 +261,14 @@ __device__ __forceinline__ void attn_carry_cum(const AdAttn& p, int b) {
 }
 
 // ------------------------------------------------------------------ attention forward
+// RES: keys resident in LDS (always in location mode); !RES: streamed, see attn_lds_floats
+template <bool RES>
 __global__ __launch_bounds__(kAttnThreads) void ad_attn_fwd_kernel(AdAttn p) {
   extern __shared__ float lds_raw[];
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   if (p.tgt_len && p.t >= p.tgt_len[b]) { attn_carry_cum(p, b); return; }
   const int H = p.H, M = p.M, U = p.U, S = p.S, K = p.loc_k;
-  const AttnLds l = attn_lds_carve(lds_raw, H, U, S, p.mode, K);
+  const AttnLds l = attn_lds_carve(lds_raw, H, U, S, p.mode, K, RES);
   const int slen = min(max(p.src_len[b], 0), S);
   AD_TICK(0, 0);
   // query input
@@ -242,7 +278,7 @@ __global__ __launch_bounds__(kAttnThreads) void ad_attn_fwd_kernel(AdAttn p) {
 #pragma unroll
     for (int e = 0; e < 4; ++e) { l.hq[h8 * 8 + 2 * e] = bflo(v[e]); l.hq[h8 * 8 + 2 * e + 1] = bfhi(v[e]); }
   }
-  attn_stage_keys(p, l, b, slen);
+  if constexpr (RES) attn_stage_keys(p, l, b, slen);
   if (p.mode == 2) attn_load_cum(p, l, b);
   attn_load_score_params(p, l);   // ends with a barrier
   AD_TICK(0, 1);
@@ -327,15 +363,23 @@ __global__ __launch_bounds__(kAttnThreads) void ad_attn_fwd_kernel(AdAttn p) {
       }
     }
   } else {
+    AttnRow nxt;
+    if constexpr (!RES) nxt = attn_row_fetch(p, b, max(min(wave, slen - 1), 0));
     for (int s = wave; s < slen; s += kAttnWaves) {
+      const uint32_t* krow = l.keys + (RES ? (s * U) >> 1 : (wave * U) >> 1);
+      if constexpr (!RES) {
+        const AttnRow cur = nxt;
+        nxt = attn_row_fetch(p, b, min(s + kAttnWaves, slen - 1));
+        attn_row_put(p, l.keys + ((wave * U) >> 1), cur);
+      }
       float part = 0.f;
       for (int u = 2 * lane; u < U; u += 128) {
         if (p.mode == 3) {        // Luong: score = keys . query (query = cell output, w_q = I)
-          const uint32_t kv = l.keys[(s * U + u) >> 1];
+          const uint32_t kv = krow[u >> 1];
           part += bflo(kv) * l.q[u] + bfhi(kv) * l.q[u + 1];
         } else {
           float x0, x1;
-          attn_pre2(p, l, b, s, u, x0, x1);
+          attn_pre2(l, krow, u, x0, x1);
           part += l.nv[u] * tanh_fast(x0) + l.nv[u + 1] * tanh_fast(x1);
         }
       }
@@ -601,13 +645,15 @@ __device__ __forceinline__ float wave_reduce32(float (&v)[32]) {
   return v[0] + __shfl_xor(v[0], 1, 64);
 }
 
-template <bool LOC>
+// UP: unit pairs per lane of the non-location score loop (4: U <= 512, 8: U <= 1024); RES as in the forward
+template <bool LOC, int UP = 4, bool RES = true>
 __global__ __launch_bounds__(kAttnThreads) void ad_attn_bwd_kernel(AdAttn p) {
+  static_assert(!LOC || RES, "location mode keeps its keys in LDS");
   extern __shared__ float lds_raw[];
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   if (p.tgt_len && p.t >= p.tgt_len[b]) return;
   const int H = p.H, M = p.M, U = p.U, S = p.S, K = p.loc_k;
-  const AttnLds l = attn_lds_carve(lds_raw, H, U, S, p.mode, K);
+  const AttnLds l = attn_lds_carve(lds_raw, H, U, S, p.mode, K, RES);
   float* dctx = l.scratch;            // [M]
   float* dal = dctx + M;              // [S]
   float* de = dal + S;                // [S]
@@ -649,7 +695,7 @@ __global__ __launch_bounds__(kAttnThreads) void ad_attn_bwd_kernel(AdAttn p) {
     }
   }
   AD_TICK(1, 1);
-  attn_stage_keys(p, l, b, slen);
+  if constexpr (RES) attn_stage_keys(p, l, b, slen);
   for (int u = tid; u < U; u += kAttnThreads) l.q[u] = p.q_seq[row * U + u];
   for (int s = tid; s < S; s += kAttnThreads) l.e[s] = p.align_seq[row * S + s];
   if (p.mode == 2) {
@@ -745,25 +791,32 @@ __global__ __launch_bounds__(kAttnThreads) void ad_attn_bwd_kernel(AdAttn p) {
     dqp[wave * U + (u ^ 64)] = 0.f;
     dnvp[wave * U + (u ^ 64)] = 0.f;
   } else {
-    constexpr int UP = 4;   // unit pairs per lane (U <= 512)
-    float dq_acc[2 * UP], dnv_acc[2 * UP];
+    float dq_acc[2 * UP], dnv_acc[2 * UP];   // a lane owns the unit pairs 2 * lane + 128 * i, i < UP
 #pragma unroll
     for (int i = 0; i < 2 * UP; ++i) { dq_acc[i] = 0.f; dnv_acc[i] = 0.f; }
+    AttnRow nxt;
+    if constexpr (!RES) nxt = attn_row_fetch(p, b, max(min(wave, slen - 1), 0));
     for (int s = wave; s < slen; s += kAttnWaves) {
+      const uint32_t* krow = l.keys + (RES ? (s * U) >> 1 : (wave * U) >> 1);
+      if constexpr (!RES) {
+        const AttnRow cur = nxt;
+        nxt = attn_row_fetch(p, b, min(s + kAttnWaves, slen - 1));
+        attn_row_put(p, l.keys + ((wave * U) >> 1), cur);
+      }
       const float des = de[s];
 #pragma unroll
       for (int i = 0; i < UP; ++i) {
         const int u = 2 * lane + 128 * i;
         if (u < U) {
           if (p.mode == 3) {      // Luong: d score / d key = query, d score / d query = key
-            const uint32_t kv = l.keys[(s * U + u) >> 1];
+            const uint32_t kv = krow[u >> 1];
             dq_acc[2 * i] += des * bflo(kv);
             dq_acc[2 * i + 1] += des * bfhi(kv);
             *reinterpret_cast<uint32_t*>(p.dpre_seq + (row * S + s) * U + u) =
                 pack2bf(des * l.q[u], des * l.q[u + 1]);
           } else {
             float x0, x1;
-            attn_pre2(p, l, b, s, u, x0, x1);
+            attn_pre2(l, krow, u, x0, x1);
             const float t0 = tanh_fast(x0), t1 = tanh_fast(x1);
             const float d0 = des * l.nv[u] * (1.f - t0 * t0), d1 = des * l.nv[u + 1] * (1.f - t1 * t1);
             dq_acc[2 * i] += d0;
@@ -2044,8 +2097,8 @@ extern "C" int os2s_debug_attn_phases(long long* out32) {
 }
 #endif
 
-static size_t attn_lds_bytes(const os2s_attn_decoder_t* d, bool bwd) {
-  return attn_lds_floats(d->H, d->M, d->U, d->S, d->score_mode, d->loc_k, bwd) * sizeof(float);
+static size_t attn_lds_bytes(const os2s_attn_decoder_t* d, bool bwd, bool resident = true) {
+  return attn_lds_floats(d->H, d->M, d->U, d->S, d->score_mode, d->loc_k, bwd, resident) * sizeof(float);
 }
 
 // A/B switches: attn_decoder.attn_split = 0: the one-workgroup-per-sample attention kernels; attn_decoder.cell_split
@@ -2053,6 +2106,17 @@ static size_t attn_lds_bytes(const os2s_attn_decoder_t* d, bool bwd) {
 static int g_attn_split = 1, g_cell_split = 1;
 static os2s::OptionReg r_attn_split("attn_decoder.attn_split", &g_attn_split, "OS2S_ATTN_SPLIT");
 static os2s::OptionReg r_cell_split("attn_decoder.cell_split", &g_cell_split, "OS2S_CELL_SPLIT");
+
+// Where the one-workgroup-per-sample attention kernel of a forward (bwd = false) or backward launch keeps the
+// keys, from that launch's own LDS footprint: resident while it fits (every shape that ran before streaming
+// existed stays resident), else streamed, else refused. Location mode has the resident form only, and one
+// budget, the backward's, for both passes, as it always had.
+enum { kKeysRefused = 0, kKeysLds = 1, kKeysStreamed = 2 };
+static int attn_keys_mode(const os2s_attn_decoder_t* d, bool bwd) {
+  if (d->score_mode == 2) return attn_lds_bytes(d, true) <= (size_t)kLdsMax ? kKeysLds : kKeysRefused;
+  if (attn_lds_bytes(d, bwd) <= (size_t)kLdsMax) return kKeysLds;
+  return attn_lds_bytes(d, bwd, false) <= (size_t)kLdsMax ? kKeysStreamed : kKeysRefused;
+}
 
 // the split location-attention kernels apply
 bool os2s::loc_split(const os2s_attn_decoder_t* d) {
@@ -2067,7 +2131,7 @@ extern "C" size_t os2s_attn_decoder_loc_ws_floats(int B, int S, int U, int loc_k
 
 int os2s::ad_check(const os2s_attn_decoder_t* d) {
   OS2S_REQUIRE(d && d->B >= 1 && d->T >= 1 && d->S >= 1 && (d->L == 1 || d->L == 2));
-  OS2S_REQUIRE(d->H % 8 == 0 && d->M % 8 == 0 && d->U % 128 == 0 && d->U <= 512);
+  OS2S_REQUIRE(d->H % 8 == 0 && d->M % 8 == 0 && d->U % 8 == 0 && d->U >= 8 && d->U <= 1024);
   OS2S_REQUIRE(d->score_mode >= 0 && d->score_mode <= 3);
   OS2S_REQUIRE(d->zoneout_mode >= 0 && d->zoneout_mode <= 2);
   if (d->zoneout_mode) OS2S_REQUIRE(d->zoneout_prob >= 0.f && d->zoneout_prob < 1.f);
@@ -2082,7 +2146,8 @@ int os2s::ad_check(const os2s_attn_decoder_t* d) {
     OS2S_REQUIRE(d->conv_w && d->conv_b && d->dense_w && d->cum_seq && d->loc_ws);
     if (d->use_bias) OS2S_REQUIRE(d->b);
   }
-  if (attn_lds_bytes(d, true) > 160 * 1024) return OS2S_ERR_UNSUPPORTED;
+  // the other modes are judged per pass, by the entry point that launches it (attn_keys_mode)
+  if (d->score_mode == 2 && attn_keys_mode(d, true) == kKeysRefused) return OS2S_ERR_UNSUPPORTED;
   return OS2S_OK;
 }
 
@@ -2113,7 +2178,9 @@ extern "C" int os2s_attn_decoder_fwd(os2s_stream_t stream_, const os2s_attn_deco
   const int rc = ad_check(d);
   if (rc != OS2S_OK) return rc;
   hipStream_t stream = (hipStream_t)stream_;
-  const size_t lds = attn_lds_bytes(d, false);
+  const int keys_mode = attn_keys_mode(d, false);
+  if (keys_mode == kKeysRefused) return OS2S_ERR_UNSUPPORTED;
+  const size_t lds = attn_lds_bytes(d, false, keys_mode == kKeysLds);
   const int B = d->B, T = d->T, H = d->H, M = d->M, L = d->L;
   AdAttn at;
   ad_fill_attn(d, at);
@@ -2167,8 +2234,10 @@ extern "C" int os2s_attn_decoder_fwd(os2s_stream_t stream_, const os2s_attn_deco
         OS2S_LAUNCH(ad_loc_scores_kernel, dim3(kLocParts, B), dim3(kAttnThreads), lds_s, stream, at, lx);
       }
       OS2S_LAUNCH(ad_loc_context_kernel, dim3(ctx_parts, B), dim3(256), lds_c, stream, at, lx, ncg, nsp);
+    } else if (keys_mode == kKeysLds) {
+      OS2S_LAUNCH_LDS(ad_attn_fwd_kernel<true>, dim3(B), dim3(kAttnThreads), lds, stream, at);
     } else {
-      OS2S_LAUNCH_LDS(ad_attn_fwd_kernel, dim3(B), dim3(kAttnThreads), lds, stream, at);
+      OS2S_LAUNCH_LDS(ad_attn_fwd_kernel<false>, dim3(B), dim3(kAttnThreads), lds, stream, at);
     }
   }
   return OS2S_OK;
@@ -2206,7 +2275,9 @@ extern "C" int os2s_attn_decoder_bwd(os2s_stream_t stream_, const os2s_attn_deco
   OS2S_REQUIRE(d->t_begin == 0 && d->t_end == d->T);
   if (d->zoneout_mode == 2) return OS2S_ERR_UNSUPPORTED;     // the expectation blend is the eval / infer form
   hipStream_t stream = (hipStream_t)stream_;
-  const size_t lds = attn_lds_bytes(d, true);
+  const int keys_mode = attn_keys_mode(d, true);
+  if (keys_mode == kKeysRefused) return OS2S_ERR_UNSUPPORTED;
+  const size_t lds = attn_lds_bytes(d, true, keys_mode == kKeysLds);
   const int B = d->B, T = d->T, H = d->H, M = d->M, L = d->L, U = d->U, S = d->S;
   const int K = d->loc_k, F = d->loc_f;
   if (hipMemsetAsync(workspace, 0, os2s_attn_decoder_bwd_workspace_bytes(d), stream) != hipSuccess) return OS2S_ERR_LAUNCH;
@@ -2280,7 +2351,13 @@ extern "C" int os2s_attn_decoder_bwd(os2s_stream_t stream_, const os2s_attn_deco
         OS2S_LAUNCH_LDS(ad_loc_score_bwd_kernel, dim3(kLocParts, B), dim3(kAttnThreads), lds_sb, stream, at, lx);
       }
     } else if (d->score_mode == 2) { OS2S_LAUNCH_LDS(ad_attn_bwd_kernel<true>, dim3(B), dim3(kAttnThreads), lds, stream, at); }
-    else { OS2S_LAUNCH_LDS(ad_attn_bwd_kernel<false>, dim3(B), dim3(kAttnThreads), lds, stream, at); }
+    else if (keys_mode == kKeysLds) {
+      if (U <= 512) { OS2S_LAUNCH_LDS(ad_attn_bwd_kernel<false>, dim3(B), dim3(kAttnThreads), lds, stream, at); }
+      else { OS2S_LAUNCH_LDS((ad_attn_bwd_kernel<false, 8>), dim3(B), dim3(kAttnThreads), lds, stream, at); }
+    } else {
+      if (U <= 512) { OS2S_LAUNCH_LDS((ad_attn_bwd_kernel<false, 4, false>), dim3(B), dim3(kAttnThreads), lds, stream, at); }
+      else { OS2S_LAUNCH_LDS((ad_attn_bwd_kernel<false, 8, false>), dim3(B), dim3(kAttnThreads), lds, stream, at); }
+    }
     for (int l = L - 1; l >= 0; --l) {
       AdCellBwd c;
       c.B = B; c.T = T; c.H = H; c.t = t; c.last = last; c.forget_bias = d->forget_bias; c.lens = d->tgt_len;
