@@ -476,6 +476,16 @@ int os2s_dropout_mask(os2s_stream_t stream, unsigned long long seed, long long n
  *   NULL (the device-resident loss scale of the mixed-precision optimizer).
  * ---------------------------------------------------------------------- */
 size_t os2s_ctc_loss_workspace_bytes(int T, int B, int V, int Lmax);
+/* The alpha / beta recursion kernel os2s_ctc_loss launches for (V, Lmax) under the ctc_loss.wave option in force:
+ * 4 / 8 / 16 = one wave per (sample, direction) with that many states per lane, 0 = the 256-thread kernel,
+ * -1 = unsupported (Lmax > 909: a kernel would need more than 64 KB of LDS; os2s_ctc_loss then gives
+ * OS2S_ERR_UNSUPPORTED). os2s_ctc_loss chooses its launch through this function. */
+int os2s_ctc_loss_kernel_class(int V, int Lmax);
+/* How os2s_ctc_loss carves its workspace (test hook): out[0..6] = byte offsets, from the workspace pointer
+ * rounded up to a multiple of 256, of logp [B,T,V] fp32, alpha and beta [B,T,Sld] fp32 (stored minus the running
+ * normalisers), coff_a and coff_b [B,T] fp64 (those normalisers), loglik [B] fp64 and valid [B] int32;
+ * out[7] = Sld, the floats of one alpha / beta row (entries >= 2 label_len + 1 are padding). */
+int os2s_ctc_loss_workspace_layout(int T, int B, int V, int Lmax, long long* out);
 int os2s_ctc_loss(os2s_stream_t stream, const float* logits, const int32_t* in_len,
                   const int32_t* labels, const int32_t* label_len, int T, int B,
                   int V, int Lmax, int blank, float grad_scale,

@@ -679,27 +679,79 @@ def dropout_mask(seed, n_elems, keep_prob, device):
 # --------------------------------------------------------------------------
 # CTC loss
 # --------------------------------------------------------------------------
+def ctc_loss_kernel_class(V, Lmax):
+  """The alpha / beta kernel os2s_ctc_loss launches for (V, Lmax) under the ctc_loss.wave option in force: 4 / 8 /
+  16 (one wave, that many states per lane), 0 (the 256-thread kernel), -1 (unsupported)."""
+  return int(_lib.C.os2s_ctc_loss_kernel_class(int(V), int(Lmax)))
+
+
+def _ctc_workspace_views(ws, T, B, V, Lmax):
+  """Named views of the sections os2s_ctc_loss carved out of the uint8 workspace `ws`."""
+  lay = (c_ll * 8)()
+  _lib.check(_lib.C.os2s_ctc_loss_workspace_layout(T, B, V, Lmax, lay), "os2s_ctc_loss_workspace_layout")
+  base = -ws.data_ptr() % 256
+  Sld = int(lay[7])
+
+  def view(i, dtype, shape):
+    n = 1
+    for d in shape:
+      n *= d
+    lo = base + int(lay[i])
+    return ws[lo:lo + n * torch.empty((), dtype=dtype).element_size()].view(dtype).view(shape)
+
+  return {"logp": view(0, torch.float32, (B, T, V)), "alpha": view(1, torch.float32, (B, T, Sld)),
+          "beta": view(2, torch.float32, (B, T, Sld)), "coff_a": view(3, torch.float64, (B, T)),
+          "coff_b": view(4, torch.float64, (B, T)), "loglik": view(5, torch.float64, (B,)),
+          "valid": view(6, torch.int32, (B,))}
+
+
 def ctc_loss(logits, in_len, labels, label_len, blank=None, grad_scale=1.0,
-             want_grad=True, want_grad_bf16=False, vpad=32, grad_scale_dev=None):
-  """logits [T,B,V] fp32. Returns dict(loss_per_sample, loss_mean, dlogits, dlogits_bf16)."""
+             want_grad=True, want_grad_bf16=False, vpad=32, grad_scale_dev=None,
+             workspace=None, out=None, want_workspace=False):
+  """logits [T,B,V] fp32. Returns dict(loss_per_sample, loss_mean, dlogits, dlogits_bf16).
+  workspace: a uint8 device tensor of at least os2s_ctc_loss_workspace_bytes to use instead of a fresh one;
+  out: a dict of preallocated outputs under the names of the result (the missing ones are allocated);
+  want_workspace: the result also holds "workspace", the views logp [B,T,V], alpha / beta [B,T,Sld] (each row
+  minus its running normaliser), coff_a / coff_b [B,T] float64 (the normalisers), loglik [B] float64 and valid [B]
+  int32 of the workspace the call used."""
   T, B, V = logits.shape
   Lmax = labels.shape[1]
   if blank is None:
     blank = V - 1
   dev = logits.device
   nbytes = int(_lib.C.os2s_ctc_loss_workspace_bytes(T, B, V, Lmax))
-  ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
-  lps = torch.empty((B,), dtype=torch.float32, device=dev)
-  lm = torch.empty((1,), dtype=torch.float32, device=dev)
-  dl = torch.empty((T, B, V), dtype=torch.float32, device=dev) if want_grad else None
-  dl16 = (torch.empty((B, T, vpad), dtype=torch.bfloat16, device=dev)
-          if want_grad_bf16 else None)
+  if workspace is None:
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+  else:
+    ws = workspace
+    if ws.dtype is not torch.uint8 or ws.dim() != 1:
+      raise TypeError("workspace: a 1-d uint8 tensor")
+    nbytes = ws.numel()        # the entry point refuses one that is too small
+  out = out or {}
+  lps = out.get("loss_per_sample")
+  lm = out.get("loss_mean")
+  dl = out.get("dlogits") if want_grad else None
+  dl16 = out.get("dlogits_bf16") if want_grad_bf16 else None
+  if lps is None:
+    lps = torch.empty((B,), dtype=torch.float32, device=dev)
+  if lm is None:
+    lm = torch.empty((1,), dtype=torch.float32, device=dev)
+  if dl is None and want_grad:
+    dl = torch.empty((T, B, V), dtype=torch.float32, device=dev)
+  if dl16 is None and want_grad_bf16:
+    dl16 = torch.empty((B, T, vpad), dtype=torch.bfloat16, device=dev)
+  assert lps.shape == (B,) and lm.shape == (1,)
+  assert dl is None or dl.shape == (T, B, V)
+  assert dl16 is None or dl16.shape == (B, T, vpad)
   _lib.C.os2s_ctc_loss(_stream(), _ptr(logits, torch.float32), _ptr(in_len, torch.int32),
                        _ptr(labels, torch.int32), _ptr(label_len, torch.int32), T, B, V, Lmax,
                        int(blank), float(grad_scale), _ptr(grad_scale_dev, torch.float32, True),
-                       _ptr(lps), _ptr(lm),
-                       _ptr(dl, None, True), _ptr(dl16, None, True), int(vpad), _ptr(ws), nbytes)
-  return {"loss_per_sample": lps, "loss_mean": lm, "dlogits": dl, "dlogits_bf16": dl16}
+                       _ptr(lps, torch.float32), _ptr(lm, torch.float32),
+                       _ptr(dl, torch.float32, True), _ptr(dl16, torch.bfloat16, True), int(vpad), _ptr(ws), nbytes)
+  res = {"loss_per_sample": lps, "loss_mean": lm, "dlogits": dl, "dlogits_bf16": dl16}
+  if want_workspace:
+    res["workspace"] = _ctc_workspace_views(ws, T, B, V, Lmax)
+  return res
 
 
 # --------------------------------------------------------------------------

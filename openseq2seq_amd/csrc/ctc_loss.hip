@@ -453,6 +453,41 @@ extern "C" size_t os2s_ctc_loss_workspace_bytes(int T, int B, int V, int Lmax) {
 static int g_ctc_wave = 1;   // ctc_loss.wave: 0 = always the 256-thread alpha / beta kernel (A/B switch)
 static os2s::OptionReg r_ctc_wave("ctc_loss.wave", &g_ctc_wave, "OS2S_CTC_WAVE");
 
+// The alpha / beta kernel os2s_ctc_loss launches for (V, Lmax): 4 / 8 / 16 = ctc_alpha_beta_wave_kernel<KS> (one
+// wave per (sample, direction) when the extended label fits 64 lanes x KS registers), 0 = the 256-thread kernel,
+// -1 = unsupported (the 256-thread recursion or the gradient kernel would need more than 64 KB of LDS).
+extern "C" int os2s_ctc_loss_kernel_class(int V, int Lmax) {
+  if (V < 2 || Lmax < 0) return -1;
+  const size_t Smax = 2 * (size_t)Lmax + 1;
+  const size_t smem_ab = Smax * 4 * 3 + (size_t)kTC * V * 4;
+  const size_t smem_g = Smax * 4 * (1 + kGR);
+  if (smem_ab > 64 * 1024 || smem_g > 64 * 1024) return -1;
+  if (g_ctc_wave != 0 && V <= 32) {
+    if (Smax <= 64 * 4) return 4;
+    if (Smax <= 64 * 8) return 8;
+    if (Smax <= 64 * 16) return 16;
+  }
+  return 0;
+}
+
+// out[0..6]: byte offsets, from the workspace pointer rounded up to 256, of logp [B,T,V] f32, alpha, beta
+// [B,T,Sld] f32, coff_a, coff_b [B,T] f64, loglik [B] f64, valid [B] i32; out[7] = Sld, the floats of an alpha /
+// beta row.
+extern "C" int os2s_ctc_loss_workspace_layout(int T, int B, int V, int Lmax, long long* out) {
+  OS2S_REQUIRE(out && T >= 1 && B >= 1 && V >= 2 && Lmax >= 0);
+  const size_t Sld = (size_t)ctc_row_floats(Lmax);
+  size_t n = 0;
+  out[0] = (long long)n; n += ctc_round256((size_t)B * T * V * 4);
+  out[1] = (long long)n; n += ctc_round256((size_t)B * T * Sld * 4);
+  out[2] = (long long)n; n += ctc_round256((size_t)B * T * Sld * 4);
+  out[3] = (long long)n; n += ctc_round256((size_t)B * T * 8);
+  out[4] = (long long)n; n += ctc_round256((size_t)B * T * 8);
+  out[5] = (long long)n; n += (size_t)B * 8;
+  out[6] = (long long)n;
+  out[7] = (long long)Sld;
+  return OS2S_OK;
+}
+
 extern "C" int os2s_ctc_loss(os2s_stream_t stream_, const float* logits,
                              const int32_t* in_len, const int32_t* labels,
                              const int32_t* label_len, int T, int B, int V, int Lmax,
@@ -464,32 +499,34 @@ extern "C" int os2s_ctc_loss(os2s_stream_t stream_, const float* logits,
   OS2S_REQUIRE(T >= 1 && B >= 1 && V >= 2 && Lmax >= 0 && blank >= 0 && blank < V);
   if (dlogits_bf16) OS2S_REQUIRE(Vpad >= V && Vpad % 8 == 0);
   if (workspace_bytes < os2s_ctc_loss_workspace_bytes(T, B, V, Lmax)) return OS2S_ERR_WORKSPACE;
+  const int kclass = os2s_ctc_loss_kernel_class(V, Lmax);
+  if (kclass < 0) return OS2S_ERR_UNSUPPORTED;
   hipStream_t stream = (hipStream_t)stream_;
-  const int Smax = 2 * Lmax + 1, Sld = ctc_row_floats(Lmax);
+  const int Smax = 2 * Lmax + 1;
+  long long lay[8];
+  if (os2s_ctc_loss_workspace_layout(T, B, V, Lmax, lay) != OS2S_OK) return OS2S_ERR_INVALID_ARG;
+  const int Sld = (int)lay[7];
   char* ws = (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
-  float* logp = (float*)ws; ws += ctc_round256((size_t)B * T * V * 4);
-  float* alpha = (float*)ws; ws += ctc_round256((size_t)B * T * Sld * 4);
-  float* beta = (float*)ws; ws += ctc_round256((size_t)B * T * Sld * 4);
-  double* coff_a = (double*)ws; ws += ctc_round256((size_t)B * T * 8);
-  double* coff_b = (double*)ws; ws += ctc_round256((size_t)B * T * 8);
-  double* ll = (double*)ws; ws += (size_t)B * 8;
-  int32_t* valid = (int32_t*)ws;
+  float* logp = (float*)(ws + lay[0]);
+  float* alpha = (float*)(ws + lay[1]);
+  float* beta = (float*)(ws + lay[2]);
+  double* coff_a = (double*)(ws + lay[3]);
+  double* coff_b = (double*)(ws + lay[4]);
+  double* ll = (double*)(ws + lay[5]);
+  int32_t* valid = (int32_t*)(ws + lay[6]);
 
   OS2S_LAUNCH(ctc_log_softmax_kernel, dim3(ceil_div((long long)T * B, 256)), dim3(256), 0,
               stream, logits, in_len, T, B, V, logp);
   const size_t smem_ab = (size_t)Smax * 4 * 3 + (size_t)kTC * V * 4;
   const size_t smem_g = (size_t)Smax * 4 * (1 + kGR);
-  if (smem_ab > 64 * 1024 || smem_g > 64 * 1024) return OS2S_ERR_UNSUPPORTED;
-  // one wave per (sample, direction) when the extended label fits 64 lanes x KS registers
-  const bool wave_path = g_ctc_wave != 0;
   const size_t smem_w = (size_t)2 * kTC * V * 4;
-  if (wave_path && V <= 32 && Smax <= 64 * 4) {
+  if (kclass == 4) {
     OS2S_LAUNCH(ctc_alpha_beta_wave_kernel<4>, dim3(2 * B), dim3(64), smem_w, stream, logp, labels,
                 Lmax, label_len, in_len, T, B, V, blank, Smax, Sld, alpha, beta, coff_a, coff_b, ll, valid);
-  } else if (wave_path && V <= 32 && Smax <= 64 * 8) {
+  } else if (kclass == 8) {
     OS2S_LAUNCH(ctc_alpha_beta_wave_kernel<8>, dim3(2 * B), dim3(64), smem_w, stream, logp, labels,
                 Lmax, label_len, in_len, T, B, V, blank, Smax, Sld, alpha, beta, coff_a, coff_b, ll, valid);
-  } else if (wave_path && V <= 32 && Smax <= 64 * 16) {
+  } else if (kclass == 16) {
     OS2S_LAUNCH(ctc_alpha_beta_wave_kernel<16>, dim3(2 * B), dim3(64), smem_w, stream, logp, labels,
                 Lmax, label_len, in_len, T, B, V, blank, Smax, Sld, alpha, beta, coff_a, coff_b, ll, valid);
   } else {

@@ -62,8 +62,9 @@ def ctc_loss_numpy(logits, in_len, labels, label_len, blank=None):
   return out
 
 
-def ctc_loss_torch(logits, in_len, labels, label_len, blank=None, want_grad=False):
-  """Returns (loss_per_sample [B], mean over batch, dlogits [T,B,V] of sum_b loss_b)."""
+def ctc_loss_torch(logits, in_len, labels, label_len, blank=None, want_grad=False, dtype=torch.float32):
+  """Returns (loss_per_sample [B], mean over batch, dlogits [T,B,V] of sum_b loss_b), computed in float64 and
+  returned as `dtype`."""
   # float64 internally: the fp32 alpha/beta recursions of any implementation
   # (TF's included) carry ~1e-3 absolute noise on peaky inputs; the oracle should
   # not contribute its own.
@@ -87,5 +88,5 @@ def ctc_loss_torch(logits, in_len, labels, label_len, blank=None, want_grad=Fals
     loss.sum().backward()
     # frames past in_len get no gradient
     tmask = (torch.arange(T)[:, None] < in_len[None, :]).double()[:, :, None]
-    grad = (logits.grad.detach() * tmask).float()
-  return loss.detach().float(), loss.detach().mean().float(), grad
+    grad = (logits.grad.detach() * tmask).to(dtype)
+  return loss.detach().to(dtype), loss.detach().mean().to(dtype), grad
