@@ -593,6 +593,45 @@ int os2s_fill_zero_chunks(os2s_stream_t stream, float* buf, int nchunks, const i
                           const long long* tensor_numel);
 int os2s_cast_f32_to_bf16(os2s_stream_t stream, const float* src, uint16_t* dst,
                           long long n);
+
+/* ------------------------------------------------------------------------
+ * Training-summary statistics (csrc/summary.hip): what the reference computes in its graph for TensorBoard,
+ * tf.norm and tf.summary.histogram of every variable and gradient (optimizers.py:289-330), as ONE pass over a flat
+ * fp32 buffer laid out like the optimizer's: nchunks chunks of os2s_opt_chunk_elems() elements, every tensor
+ * starting at a chunk boundary (chunk_tensor [nchunks], tensor_chunk_begin [ntensors + 1]).
+ *   tensor_count [ntensors] (device): the leading elements of each tensor that are summarised (clamped to the
+ *     tensor's chunks); max_count: the largest of them, which the caller knows on the host
+ *   tensor_select [ntensors] (device, one byte each): 0 = the tensor is not read and its outputs are left untouched
+ *   the value summarised is v = x * m in fp32, widened to double; m = host_mult * dev_mult[0] (fp32 product;
+ *     dev_mult NULL: m = host_mult), so that a loss scale or a clip factor gets in without a host read
+ *   flags: OS2S_SUMMARY_MASK_NONFINITE: a non-finite v counts as 0.0 (mask_nans, optimizers.py:318); without it such
+ *     a v is left out of every statistic and counted in `nonfinite`. OS2S_SUMMARY_COMBINE_LANES (measurement; same
+ *     counts): the lanes of a wave that share the leading lane's bucket are combined into one LDS add first, where
+ *     the default is one LDS add per lane
+ *   stats [ntensors][6] doubles: min, max, num, sum, sum_squares, nonfinite; num == 0: min = DBL_MAX, max = -DBL_MAX
+ *     (TensorFlow's initial values). sum and sum_squares are added in one fixed order (thread, wave, workgroup, then
+ *     the tensor's chunks in chunk order) without floating-point atomics: the same bits in every run.
+ *   hist (may be NULL) uint32 [ntensors][os2s_summary_num_buckets() = 1551]: counts of TensorFlow's default histogram
+ *     buckets. limits = {-DBL_MAX, -p[773] .. -p[0], 0, p[0] .. p[773], DBL_MAX}, p[0] = 1e-12, p[k + 1] = p[k] * 1.1
+ *     in double; bucket(v) = index of the first limit > v (+0 and -0: 776). Refused (invalid argument) when
+ *     max_count >= 2^32.
+ *   workspace: os2s_summary_stats_workspace_bytes(nchunks) bytes, 8-byte aligned; contents need not be kept.
+ * os2s_summary_grad_mult (one thread): the multipliers of the gradient summaries, out[0] = 1 / (loss_scale[0] *
+ * world_size) (loss_scale NULL: 1) and out[1] = out[0] * clip * min(1 / norm, 1 / clip), norm = sqrt of the sum of
+ * the selected tensors' sum_squares in `stats` (NaN when one of them counted a non-finite value); clip <= 0 or
+ * stats NULL: out[1] = out[0].
+ * ---------------------------------------------------------------------- */
+#define OS2S_SUMMARY_MASK_NONFINITE 1
+#define OS2S_SUMMARY_COMBINE_LANES 2
+int os2s_summary_num_buckets(void);
+size_t os2s_summary_stats_workspace_bytes(int nchunks);
+int os2s_summary_stats(os2s_stream_t stream, const float* buf, int nchunks, int ntensors,
+                       const int32_t* chunk_tensor, const int32_t* tensor_chunk_begin,
+                       const long long* tensor_count, long long max_count, const uint8_t* tensor_select,
+                       float host_mult, const float* dev_mult, int flags, double* stats,
+                       uint32_t* hist, void* workspace, size_t workspace_bytes);
+int os2s_summary_grad_mult(os2s_stream_t stream, const float* loss_scale, int world_size, float clip,
+                           const double* stats, const uint8_t* tensor_select, int ntensors, float* out);
 /* batched dgrad copies of conv weights: wT[k'][ci][co] = w[K-1-k'][co][ci];
  * descs: device array of {int64 src_off, int64 dst_off, int32 K, Cout, Cin, tile_begin} */
 int os2s_conv_weight_dgrad_copy(os2s_stream_t stream, const uint16_t* w16,

@@ -907,6 +907,55 @@ def fill_zero_chunks(buf, chunk_tensor, tensor_skip, tensor_chunk_begin, tensor_
                                _ptr(tensor_chunk_begin, torch.int32), _ptr(tensor_numel, torch.int64))
 
 
+SUMMARY_STAT_FIELDS = ("min", "max", "num", "sum", "sum_squares", "nonfinite")
+
+
+def summary_num_buckets():
+  return int(_lib.C.os2s_summary_num_buckets())
+
+
+def summary_stats_workspace(nchunks, device):
+  """The scratch buffer of summary_stats for a flat buffer of `nchunks` chunks (float64, so 8-byte aligned)."""
+  nbytes = int(_lib.C.os2s_summary_stats_workspace_bytes(int(nchunks)))
+  return torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=device)
+
+
+def summary_stats(buf, chunk_tensor, tensor_chunk_begin, tensor_count, tensor_select, stats, hist=None, *,
+                  host_mult=1.0, dev_mult=None, mask_nonfinite=False, combine_lanes=False, workspace=None,
+                  max_count=None):
+  """os2s_summary_stats on the current stream: per-tensor min / max / num / sum / sum_squares / nonfinite
+  (stats: float64 [ntensors, 6], SUMMARY_STAT_FIELDS) of v = x * (host_mult * dev_mult[0]) over the flat fp32 buffer
+  `buf`, and with hist (uint32 [ntensors, 1551]) the counts of TensorFlow's default histogram buckets.
+  tensor_count: int64 [ntensors] on the device, the leading elements of each tensor that count; max_count: their
+  maximum as a host int (None: read back here, which synchronises). tensor_select: uint8 [ntensors]; the rows of a
+  tensor that is not selected are left untouched. combine_lanes: the other way of counting buckets (measurement)."""
+  nchunks = chunk_tensor.numel()
+  nt = tensor_chunk_begin.numel() - 1
+  assert buf.numel() == nchunks * opt_chunk_elems()
+  assert tensor_count.numel() == nt and tensor_select.numel() == nt
+  assert tuple(stats.shape) == (nt, len(SUMMARY_STAT_FIELDS))
+  assert hist is None or tuple(hist.shape) == (nt, summary_num_buckets())
+  if workspace is None:
+    workspace = summary_stats_workspace(nchunks, buf.device)
+  if max_count is None:
+    max_count = int(tensor_count.max().item())
+  _lib.C.os2s_summary_stats(_stream(), _ptr(buf, torch.float32), nchunks, nt, _ptr(chunk_tensor, torch.int32),
+                            _ptr(tensor_chunk_begin, torch.int32), _ptr(tensor_count, torch.int64), int(max_count),
+                            _ptr(tensor_select, torch.uint8), float(host_mult), _ptr(dev_mult, torch.float32, True),
+                            int(bool(mask_nonfinite)) | (2 if combine_lanes else 0), _ptr(stats, torch.float64), _ptr(hist, torch.uint32, True),
+                            _ptr(workspace, torch.float64), workspace.numel() * 8)
+
+
+def summary_grad_mult(loss_scale, world_size, clip, stats, tensor_select, out):
+  """os2s_summary_grad_mult: out (fp32 [2]) = {1 / (loss_scale * world_size), that times the global-norm clip factor
+  computed from the sum_squares in `stats`} (stats None or clip <= 0: both the same)."""
+  assert out.numel() >= 2
+  nt = tensor_select.numel() if tensor_select is not None else (stats.shape[0] if stats is not None else 0)
+  _lib.C.os2s_summary_grad_mult(_stream(), _ptr(loss_scale, torch.float32, True), int(world_size), float(clip or 0.0),
+                                _ptr(stats, torch.float64, True), _ptr(tensor_select, torch.uint8, True), nt,
+                                _ptr(out, torch.float32))
+
+
 def cast_f32_to_bf16(src, dst):
   n = src.numel()
   _lib.C.os2s_cast_f32_to_bf16(_stream(), _ptr(src, torch.float32), _ptr(dst, torch.bfloat16), n)

@@ -145,6 +145,8 @@ class Model(object):
     self._train_op = None
     self._compiled = False
     self._data_layer = None
+    # TensorBoard summaries (open_summaries): the event file, every how many steps, the StepCounterHook's mark
+    self._summary_writer, self._summary_every, self._rate_mark = None, 0, None
 
   # ---- accessors mirroring the reference ---------------------------------
   @property
@@ -241,6 +243,8 @@ class Model(object):
       n = self._data_layer.get_size_in_samples()
     except Exception:
       return None
+    if n is None:
+      return None
     world = self._hvd.size() if self._hvd is not None else 1
     return n // (p['batch_size_per_gpu'] * world * p.get('iter_size', 1))
 
@@ -268,8 +272,64 @@ class Model(object):
   def _get_num_objects_per_step(self, batch):
     pass
 
+  # ---- TensorBoard summaries (model.py:526-532, optimizers.py:289-376, funcs.py:161-167) ------------------------
+  def open_summaries(self, logdir=None):
+    """Rank 0 of a training model with a logdir and `save_summaries_steps` = N opens the event file; train_step
+    then writes the summaries of every step it is given with step % N == 0. Returns the writer, or None when the
+    configuration asks for none (no file is created then)."""
+    p = self._params
+    logdir = logdir or p.get('logdir', None)
+    every = p.get('save_summaries_steps', None)
+    rank = self._hvd.rank() if self._hvd is not None else 0
+    if not (logdir and every and rank == 0 and self._mode == "train" and self._compiled):
+      return None
+    from ..utils.summary import EventFileWriter
+    self._summary_writer, self._summary_every, self._rate_mark = EventFileWriter(logdir), int(every), None
+    self._train_op.set_summary_writer(self._summary_writer)
+    return self._summary_writer
+
+  @property
+  def summary_writer(self):
+    return self._summary_writer
+
+  def summaries_due(self, step):
+    return self._summary_writer is not None and step is not None and step % self._summary_every == 0
+
+  def _write_step_summaries(self, step, loss):
+    """train_loss, epoch and global_step/sec of a summary step (one host read of the loss, on these steps only)."""
+    from ..utils import summary as S
+    scalars = {S.tag("train_loss"): float(loss.float().cpu().reshape(-1)[0])}
+    spe = self.steps_in_epoch
+    if spe:
+      scalars[S.tag("epoch")] = float(step // spe)
+    now = time.time()
+    if self._rate_mark is not None and step > self._rate_mark[0] and now > self._rate_mark[1]:
+      # StepCounterHook(every_n_steps = save_summaries_steps): steps since its last trigger over the time they took
+      scalars[S.tag("global_step_sec")] = (step - self._rate_mark[0]) / (now - self._rate_mark[1])
+    self._rate_mark = (step, now)
+    self._summary_writer.add_scalars(step, scalars)
+
+  def write_eval_summaries(self, step, results, eval_model=None):
+    """utils/hooks.py:219-245: the numbers of an evaluation, when summaries are on."""
+    if self._summary_writer is None:
+      return
+    from ..utils import summary as S
+    from ..data.lm.lmdata import WKTDataLayer
+    dl = getattr(eval_model if eval_model is not None else self, "_data_layer", None)
+    self._summary_writer.add_scalars(step, S.eval_scalars(results, isinstance(dl, WKTDataLayer)))
+    self._summary_writer.flush()
+
+  def close_summaries(self):
+    """The last step's statistics become events and the file is closed."""
+    if self._summary_writer is not None:
+      self._train_op.close()
+      self._train_op.set_summary_writer(None)
+      self._summary_writer.close()
+      self._summary_writer = None
+
   # ---- one training step (funcs.py:184: sess.run([train_op, ...])) ----------
-  def train_step(self, batch):
+  def train_step(self, batch, step=None):
+    """`step`: the global step of this call, for the summaries (open_summaries); None: no summaries."""
     assert self._compiled and self._mode == "train"
     p = self._params
     # the side-stream switch is this model's, for the duration of its step only (a second model in the
@@ -318,10 +378,15 @@ class Model(object):
           self._reducer.finish()
         # the update runs on its own stream next to the NEXT step's forward pass (TrainOp.run_async) unless
         # the configuration or OS2S_ASYNC_OPT=0 asks for the one-stream form
+        due = self.summaries_due(step)
+        if due:
+          self._train_op.collect_summaries(step)
         if p.get('os2s_async_optimizer', ASYNC_OPTIMIZER):
           self._train_op.run_async()
         else:
           self._train_op.run()
+        if due:
+          self._write_step_summaries(step, loss)
       if tape is not None:
         tape.ops = []            # (Tape.defer_free: the step's closures are released behind the optimizer launch)
     finally:

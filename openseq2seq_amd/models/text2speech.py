@@ -2,8 +2,8 @@
 text2speech_tacotron.py. The model shell (feature sizes flow from the data layer to the decoder and the loss),
 and the audio end of the infer mode: `griffin_lim` / `save_audio` (:111-198) and `finalize_inference` (:339-413)
 turn the predicted spectrograms into wav files in logdir. The Griffin-Lim iterations run on the GPU
-(csrc/griffin_lim.hip: a whole ragged batch per call, exact fp32); plotting and tensorboard summaries are not
-provided. The reference defines no objects-per-step for TTS; benchmarks here count target mel frames."""
+(csrc/griffin_lim.hip: a whole ragged batch per call, exact fp32); the plots and the image / audio summaries built from
+them are not provided (the scalar and histogram summaries of training are: utils/summary.py). The reference defines no objects-per-step for TTS; benchmarks here count target mel frames."""
 from __future__ import absolute_import, division, print_function
 
 import struct

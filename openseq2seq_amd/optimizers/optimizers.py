@@ -109,13 +109,43 @@ class TrainOp(object):
   """The object optimize_loss returns: `run()` performs one optimisation step on
   the flat parameter store (after backward filled store.grads)."""
 
-  def __init__(self, store, cfg, initial_scale):
+  def __init__(self, store, cfg, initial_scale, summaries=None, larc_params=None, automatic_loss_scaling=False):
     self.store, self.cfg = store, cfg
+    # the `summaries` list of the configuration, kept for collect_summaries (optimizers.py:289-376)
+    self.summaries = list(summaries or ())
+    self._summary_args = (larc_params, automatic_loss_scaling)
+    self._summ = None                 # OptimizerSummaries, built by the first set_summary_writer
+    self._summary_step = None         # the step the next run() / run_async() collects summaries for
     self.state = torch.zeros(capi.opt_state_bytes(), dtype=torch.uint8, device=store.device)
     capi.opt_init_state(self.state, initial_scale)
     # float view of the loss scale (offset 32 in OptDeviceState) for device-side consumers
     self.loss_scale_view = self.state[32:36].view(torch.float32)
     self.lr_view = self.state[36:40].view(torch.float32)
+
+  # ---- summaries ---------------------------------------------------------------------------------------------
+  def set_summary_writer(self, writer):
+    """The EventFileWriter the optimizer's summaries go to (builds the device buffers of the statistics pass)."""
+    if self._summ is None:
+      from .summaries import OptimizerSummaries
+      self._summ = OptimizerSummaries(self.store, self.cfg, self.summaries, *self._summary_args)
+    self._summ.writer = writer
+
+  def collect_summaries(self, step):
+    """Makes the next run() / run_async() a summary step, labelled `step`: the statistics pass is enqueued on the
+    update's stream before the update, the result block is copied to pinned memory behind it. The block of the
+    previous summary step becomes events here. Any other step launches, copies and waits for nothing."""
+    if self._summ is None:
+      raise RuntimeError("collect_summaries needs set_summary_writer first")
+    self._summ.flush()
+    self._summary_step = int(step)
+
+  def flush_summaries(self):
+    if self._summ is not None:
+      self._summ.flush()
+
+  def close(self):
+    """The last summary block becomes events (the writer itself belongs to the caller)."""
+    self.flush_summaries()
 
   def _wnorm_cache(self):
     """Keyword arguments of the statistics pass and of the update: with LARC the per-chunk sums of w^2 come from
@@ -138,9 +168,14 @@ class TrainOp(object):
     s = self.store
     s.wait_all()                    # (the raw buffers below: `s.master` would mark every tensor as written)
     prep, _ = self._wnorm_cache()
+    step, self._summary_step = self._summary_step, None
+    if step is not None:
+      self._summ.before_update(self.loss_scale_view)
     capi.opt_step(self.cfg, self.state, s._grads, s._master, s._m1, s._m2, s._w16,
                   s.chunk_tensor, s.tensor_chunk_begin, s.tensor_l2 if s.l2_active else None, None, s.partial,
                   s.t_gnorm2, s.t_wnorm2, s.t_amax, s.t_mult, s._t_v, **prep)
+    if step is not None:
+      self._summ.after_update(step, self.lr_view)
     self._updated(bool(prep))
     s.refresh_dgrad_copies()
 
@@ -163,11 +198,16 @@ class TrainOp(object):
     nranges = max(1, min(int(nranges), nchunks))
     bounds = [(nchunks * i) // nranges for i in range(nranges + 1)]
     pending = []
+    step, self._summary_step = self._summary_step, None
     with torch.cuda.stream(side):
       prep, apply = self._wnorm_cache()
+      if step is not None:
+        self._summ.before_update(self.loss_scale_view)
       capi.opt_prepare(self.cfg, self.state, s._grads, s._master, s.chunk_tensor, s.tensor_chunk_begin,
                        s.tensor_l2 if s.l2_active else None, s.partial, s.t_gnorm2, s.t_wnorm2, s.t_amax,
                        s.t_mult, s._t_v, **prep)
+      if step is not None:             # (the learning rate is final behind the prepare half; the copy does not
+        self._summ.after_update(step, self.lr_view)      # wait for the update ranges)
       for c0, c1 in zip(bounds[:-1], bounds[1:]):
         capi.opt_apply_range(self.cfg, self.state, s._grads, s._master, s._m1, s._m2, s._w16, c0, c1,
                              s.chunk_tensor, s.tensor_l2 if s.l2_active else None, s.t_mult, zero_grads=True,
@@ -194,7 +234,8 @@ def optimize_loss(store, optimizer, optimizer_params, learning_rate_decay_fn,
                   on_horovod=False, iter_size=1, world_size=1):
   """Same argument meaning as optimizers.py:107-160 (loss/var_list are implicit in
   `store`). Returns a TrainOp."""
-  if summaries is not None:
+  summaries = list(summaries or ())
+  if summaries:
     for summ in summaries:
       if summ not in OPTIMIZER_SUMMARIES:
         raise ValueError("Summaries should be one of [{}], you provided {}.".format(
@@ -210,4 +251,5 @@ def optimize_loss(store, optimizer, optimizer_params, learning_rate_decay_fn,
   cfg.world_size = int(world_size) * int(iter_size)
   if cfg.optimizer == 3 and store.m2 is None:
     raise ValueError("Adam needs FlatParams.finalize(need_m2=True)")
-  return TrainOp(store, cfg, scale)
+  return TrainOp(store, cfg, scale, summaries=summaries, larc_params=larc_params,
+                 automatic_loss_scaling=(dtype == "mixed" and isinstance(loss_scaling, six.string_types)))

@@ -20,8 +20,22 @@ from openseq2seq_amd.utils import distributed as dist_utils
 from openseq2seq_amd.utils.utils import create_model, deco_print, get_base_config
 
 
-def train(model, args):
-  """utils/funcs.py:22-220 reduced to the hot loop + benchmark timing."""
+def train(model, args, final_eval=False):
+  """Training with its record: rank 0 with a logdir and `save_summaries_steps` writes a TensorBoard event file
+  (never under --benchmark), closed when training ends. final_eval (main): the evaluation that follows the last
+  step runs here, before the file is closed, so that its numbers are in it (utils/hooks.py:196)."""
+  if not args.benchmark:
+    model.open_summaries()
+  try:
+    max_steps = _train(model, args)
+    if final_eval and getattr(model, "eval_model", None) is not None:
+      run_eval(model, model.eval_model, model.hvd.rank() if model.hvd else 0, max_steps)
+  finally:
+    model.close_summaries()
+
+
+def _train(model, args):
+  """utils/funcs.py:22-220 reduced to the hot loop + benchmark timing. Returns the step it stopped at."""
   p = model.params
   # models/model.py:346-365 / utils/funcs.py:45: stop at max_steps, else num_epochs * steps_in_epoch
   # (100 steps when neither can be known: synthetic batches without dataset files)
@@ -52,10 +66,10 @@ def train(model, args):
     if batches is not None:
       batch = next(batches)
     if eval_model is not None and eval_steps and step > 0 and step % eval_steps == 0:
-      run_eval(model, eval_model, rank)
+      run_eval(model, eval_model, rank, step)
     torch.cuda.synchronize()
     t0 = time.time()
-    loss = model.train_step(batch)
+    loss = model.train_step(batch, step)
     torch.cuda.synchronize()
     dt = time.time() - t0
     if step >= bench_start:
@@ -77,12 +91,15 @@ def train(model, args):
     deco_print("Finished training")
     deco_print("Avg time per step: {:.3f}s".format(total_time / n))
     deco_print("Avg objects per second: {:.3f}".format(total_objects / total_time))
+  return max_steps
 
 
-def run_eval(model, eval_model, rank):
+def run_eval(model, eval_model, rank, step=None):
   if model is not None:
     eval_model.copy_weights_from(model)
   res = eval_model.evaluate()
+  if model is not None and step is not None:
+    model.write_eval_summaries(step, res, eval_model)
   if rank == 0:
     if "bleu" in res:
       deco_print("Validation: Eval BLUE score: %.4f  exact match: %.4f  (%d samples)"
@@ -156,9 +173,7 @@ def main():
     return
   if args.mode not in ("train", "train_eval"):
     raise NotImplementedError("mode %s" % args.mode)
-  train(model, args)
-  if getattr(model, "eval_model", None) is not None:
-    run_eval(model, model.eval_model, model.hvd.rank() if model.hvd else 0)
+  train(model, args, final_eval=True)
 
 
 if __name__ == '__main__':
