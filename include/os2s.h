@@ -1093,6 +1093,40 @@ int os2s_embed_wdrop_fwd(os2s_stream_t stream, const int32_t* ids, const uint16_
                          float keep_prob, unsigned long long seed, uint16_t* out);
 int os2s_embed_wdrop_bwd(os2s_stream_t stream, const int32_t* ids, const uint16_t* dout, int V, int D, long long N,
                          float keep_prob, unsigned long long seed, float* dtable);
+/* os2s_lnlstm_layer_bwd with a gradient on the final state as well (the text-classification phase,
+ * encoders/lm_encoders.py:362-373, classifies the last layer's final state, not its outputs): dhT / dcT [B,H]
+ * fp32 are the gradients of the forward's hT / cT, either may be NULL, and dy may be NULL (zero). They enter at
+ * step min(max(lens[b], 0), T) - 1 of sample b (T - 1 without lens), the step whose state the forward copied
+ * through the padding; a sample of length 0 receives nothing (its hT is h0, and gradients to h0 / c0 are not
+ * computed). With dhT = dcT = NULL and dy given the result has the bits of os2s_lnlstm_layer_bwd; everything
+ * else, workspace and determinism included, is as stated there. */
+int os2s_lnlstm_layer_bwd_state(os2s_stream_t stream, const uint16_t* whT, const float* ln, const int32_t* lens,
+                                const uint16_t* dy, long long lddy, const float* dhT, const float* dcT,
+                                const uint16_t* xhat, const float* s_hat, const float* rstd, const float* c0,
+                                int B, int T, int H, float forget_bias, float keep_prob, unsigned long long seed,
+                                uint16_t* dgx, float* dln, void* workspace, size_t workspace_bytes);
+
+/* ------------------------------------------------------------------------
+ * Final-state classification head of the language model's text-classification phase (csrc/text_cls.hip):
+ * encoders/lm_encoders.py:362-373 (tf.layers.Dense on the last layer's final state h, or concat([h, c], axis=1)
+ * with use_cell_state, h first) and losses/cross_entropy_loss.py (tf.losses.softmax_cross_entropy).
+ *   logits[b,c] = bias[c] + sum_d s[b,d] w[c,d]      s[b] = hT[b] (cT NULL, D = H) or [hT[b], cT[b]] (D = 2H)
+ *   loss        = (1/B) sum_b sum_c labels[b,c] (logsumexp(logits[b]) - logits[b,c])
+ *   dlogits     = (softmax(logits[b]) * sum_c labels[b,c] - labels[b]) / B [* grad_scale_dev[0]]
+ *   dw[c,d] += sum_b dlogits[b,c] s[b,d],  dbias[c] += sum_b dlogits[b,c],  d s[b,d] = sum_c dlogits[b,c] w[c,d]
+ * hT / cT, logits, labels (dense: one-hot or soft), loss [1], dlogits, dw [C,D], dbias [C] (or NULL), dhT / dcT
+ * [B,H] are fp32; w [C,D] is bf16; bias may be NULL. The concatenated state is never formed. dlogits NULL: the loss
+ * alone. dw / dbias are accumulated into, dhT / dcT written (dcT NULL exactly when cT is); they feed
+ * os2s_lnlstm_layer_bwd_state. One launch per entry, sums over the batch in a fixed order without atomics:
+ * bit-identical on a rerun, with or without os2s_set_deterministic.
+ * B >= 1, H % 8 == 0, 8 <= H <= 2048, 2 <= C <= 16, else OS2S_ERR_UNSUPPORTED.
+ * ---------------------------------------------------------------------- */
+int os2s_text_cls_fwd(os2s_stream_t stream, const float* hT, const float* cT, const uint16_t* w, const float* bias,
+                      int B, int H, int C, float* logits);
+int os2s_softmax_xent_dense(os2s_stream_t stream, const float* logits, const float* labels, int B, int C,
+                            const float* grad_scale_dev, float* loss, float* dlogits);
+int os2s_text_cls_bwd(os2s_stream_t stream, const float* hT, const float* cT, const uint16_t* w, const float* dlogits,
+                      int B, int H, int C, float* dw, float* dbias, float* dhT, float* dcT);
 
 /* ------------------------------------------------------------------------
  * Attention-RNN decoder loop: the AttentionWrapper cell that tf.contrib.seq2seq.dynamic_decode

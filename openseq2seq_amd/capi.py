@@ -1731,6 +1731,72 @@ def lnlstm_layer_bwd(whT, ln, lens, dy, xhat, s_hat, rstd, H, forget_bias=1.0, k
   return dgx, dln
 
 
+def lnlstm_layer_bwd_state(whT, ln, lens, dy, dhT, dcT, xhat, s_hat, rstd, H, forget_bias=1.0, keep_prob=1.0, seed=0,
+                           c0=None):
+  """os2s_lnlstm_layer_bwd_state: lnlstm_layer_bwd with the gradients dhT / dcT [B,H] fp32 | None of the forward's
+  final state; dy [B,T,H] bf16 | None (zero). Returns (dgx, dln)."""
+  B, T, _ = xhat.shape
+  dev = xhat.device
+  assert dy is None or (tuple(dy.shape) == (B, T, H) and dy.stride(2) == 1 and dy.stride(0) == T * dy.stride(1))
+  assert tuple(whT.shape) == (H, 4 * H) and whT.is_contiguous() and tuple(ln.shape) == (10, H)
+  assert tuple(xhat.shape) == (B, T, 4 * H) and tuple(s_hat.shape) == (B, T, H) and tuple(rstd.shape) == (B, T, 5)
+  for s0 in (c0, dhT, dcT):
+    assert s0 is None or (tuple(s0.shape) == (B, H) and s0.is_contiguous())
+  dgx = torch.empty((B, T, 4 * H), dtype=torch.bfloat16, device=dev)
+  dln = torch.empty((10, H), dtype=torch.float32, device=dev)
+  n = int(_lib.C.os2s_lnlstm_bwd_workspace_bytes(B, H))
+  ws = torch.empty((n,), dtype=torch.uint8, device=dev)
+  _lib.C.os2s_lnlstm_layer_bwd_state(_stream(), _ptr(whT, torch.bfloat16), _ptr(ln, torch.float32),
+                                     _ptr(lens, torch.int32, True), _addr(dy), dy.stride(1) if dy is not None else 0,
+                                     _ptr(dhT, torch.float32, True), _ptr(dcT, torch.float32, True),
+                                     _ptr(xhat, torch.bfloat16), _ptr(s_hat, torch.float32), _ptr(rstd, torch.float32),
+                                     _ptr(c0, torch.float32, True), B, T, H, float(forget_bias), float(keep_prob),
+                                     int(seed) & (2**64 - 1), dgx.data_ptr(), _ptr(dln, torch.float32), _ptr(ws), n)
+  return dgx, dln
+
+
+# --------------------------------------------------------------------------
+# final-state classification head (csrc/text_cls.hip)
+# --------------------------------------------------------------------------
+def text_cls_fwd(hT, cT, w, bias):
+  """os2s_text_cls_fwd: hT [B,H] fp32, cT [B,H] fp32 | None, w [C,D] bf16 (D = H or 2H), bias [C] fp32 | None ->
+  logits [B,C] fp32."""
+  B, H = hT.shape
+  C, D = w.shape
+  assert D == (H if cT is None else 2 * H) and (cT is None or tuple(cT.shape) == (B, H))
+  assert bias is None or tuple(bias.shape) == (C,)
+  logits = torch.empty((B, C), dtype=torch.float32, device=hT.device)
+  _lib.C.os2s_text_cls_fwd(_stream(), _ptr(hT, torch.float32), _ptr(cT, torch.float32, True), _ptr(w, torch.bfloat16),
+                           _ptr(bias, torch.float32, True), B, H, C, _ptr(logits))
+  return logits
+
+
+def softmax_xent_dense(logits, labels, grad_scale_dev=None, want_grad=True):
+  """os2s_softmax_xent_dense: logits, labels [B,C] fp32 -> (loss [1] fp32, dlogits [B,C] fp32 | None)."""
+  B, C = logits.shape
+  assert tuple(labels.shape) == (B, C)
+  loss = torch.empty(1, dtype=torch.float32, device=logits.device)
+  dl = torch.empty_like(logits) if want_grad else None
+  _lib.C.os2s_softmax_xent_dense(_stream(), _ptr(logits, torch.float32), _ptr(labels, torch.float32), B, C,
+                                 _ptr(grad_scale_dev, torch.float32, True), _ptr(loss), _ptr(dl, torch.float32, True))
+  return loss, dl
+
+
+def text_cls_bwd(hT, cT, w, dlogits, dw, dbias):
+  """os2s_text_cls_bwd: dw [C,D] / dbias [C] | None fp32 are accumulated into; returns (dhT, dcT | None) fp32
+  [B,H]."""
+  B, H = hT.shape
+  C, D = w.shape
+  assert D == (H if cT is None else 2 * H) and tuple(dlogits.shape) == (B, C) and tuple(dw.shape) == (C, D)
+  assert dbias is None or tuple(dbias.shape) == (C,)
+  dhT = torch.empty_like(hT)
+  dcT = torch.empty_like(cT) if cT is not None else None
+  _lib.C.os2s_text_cls_bwd(_stream(), _ptr(hT, torch.float32), _ptr(cT, torch.float32, True), _ptr(w, torch.bfloat16),
+                           _ptr(dlogits, torch.float32), B, H, C, _ptr(dw, torch.float32),
+                           _ptr(dbias, torch.float32, True), _ptr(dhT), _ptr(dcT, torch.float32, True))
+  return dhT, dcT
+
+
 # --------------------------------------------------------------------------
 # conv2d via banded channel mixing (DS2)
 # --------------------------------------------------------------------------

@@ -270,7 +270,7 @@ __global__ __launch_bounds__(64 * kLnWaves) void lnlstm_prod_bwd_kernel(LnProdBw
 }
 
 struct LnCellBwdArgs {
-  const bf16_t* dy; long long lddy;
+  const bf16_t* dy; long long lddy;   // null: no gradient on y (zero)
   const float* dhp;     // [B,H] or null at the last step (nothing follows it)
   const bf16_t* xhat;   // [B,T,4H]
   const float* shat;    // [B,T,H]
@@ -284,9 +284,15 @@ struct LnCellBwdArgs {
   int B, T, H, step;
   float forget_bias, keep;
   unsigned long long seed;
+  const float* dhT;     // [B,H] or null: the gradient of the final h, entering at the sample's last live step (ST)
 };
 
-template <int NCH>
+// ST: the instance for a call without dy or with dhT (os2s_lnlstm_layer_bwd_state). ST = false is the code of the
+// plain backward: no test in front of the dy load, which would put one more memory round trip on every step of the
+// language model's chain of dependent launches (0.9 us per launch at H = 896). The two instances contract their
+// multiply-adds differently, so a state call that needs neither (dy given, no dhT) runs the plain one: its result is
+// os2s_lnlstm_layer_bwd's bit for bit.
+template <int NCH, bool ST>
 __global__ __launch_bounds__(64) void lnlstm_cell_bwd_kernel(LnCellBwdArgs p) {
   const int b = blockIdx.x, lane = threadIdx.x;
   const int H = p.H, nchunk = H >> 3;
@@ -309,12 +315,18 @@ __global__ __launch_bounds__(64) void lnlstm_cell_bwd_kernel(LnCellBwdArgs p) {
     if (ch < nchunk) {
       float gm[8], bt[8], dyv[8], dh[8], dcarry[8], pg[8];
       float* pgb = p.pgrad + (long long)b * (10 * H) + ch * 8;
-      ld8bf(p.dy + row * p.lddy + ch * 8, dyv);
 #pragma unroll
-      for (int e = 0; e < 8; ++e) dh[e] = 0.f;
+      for (int e = 0; e < 8; ++e) dh[e] = dyv[e] = 0.f;
+      if (!ST || p.dy) ld8bf(p.dy + row * p.lddy + ch * 8, dyv);
       if (p.dhp) ld8(p.dhp + (long long)b * H + ch * 8, dh);
 #pragma unroll
       for (int e = 0; e < 8; ++e) dh[e] += dyv[e];
+      if (ST && p.dhT && t == len - 1) {    // wave-uniform. dhp of this step is zero for the sample (dgx[t + 1] is a dead row)
+        float dT[8];
+        ld8(p.dhT + (long long)b * H + ch * 8, dT);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) dh[e] += dT[e];
+      }
       ld8(p.dcc + (long long)b * H + ch * 8, dcarry);
       ld8(p.shat + row * H + ch * 8, sh[c]);
       ld8(p.ln + (long long)8 * H + ch * 8, gm);
@@ -560,15 +572,21 @@ extern "C" size_t os2s_lnlstm_bwd_workspace_bytes(int B, int H) {
   return 2 * align256(bh * 4) + align256(bh * 40);
 }
 
-extern "C" int os2s_lnlstm_layer_bwd(os2s_stream_t stream_, const uint16_t* whT, const float* ln, const int32_t* lens,
-                                     const uint16_t* dy, long long lddy, const uint16_t* xhat, const float* s_hat,
-                                     const float* rstd, const float* c0, int B, int T, int H, float forget_bias,
-                                     float keep_prob, unsigned long long seed, uint16_t* dgx, float* dln,
-                                     void* workspace, size_t workspace_bytes) {
-  OS2S_REQUIRE(whT && ln && dy && xhat && s_hat && rstd && dgx && dln && workspace && B >= 1 && T >= 1 && H >= 1);
+// Both backward entries; state: the call of os2s_lnlstm_layer_bwd_state, where dy may be null; dhT / dcT [B,H] fp32 or null: the gradients of the forward's hT / cT.
+// cT[b] is the carried (normalised) state after the sample's last live step, so dcT is the initial value of the dcc
+// carry, which the dead steps before it leave alone; hT[b] is that step's h, so the cell kernel adds dhT there.
+static int lnlstm_layer_bwd_impl(os2s_stream_t stream_, const uint16_t* whT, const float* ln, const int32_t* lens,
+                                 const uint16_t* dy, long long lddy, bool state, const float* dhT,
+                                 const float* dcT, const uint16_t* xhat, const float* s_hat, const float* rstd,
+                                 const float* c0, int B, int T, int H, float forget_bias, float keep_prob,
+                                 unsigned long long seed, uint16_t* dgx, float* dln, void* workspace,
+                                 size_t workspace_bytes) {
+  OS2S_REQUIRE(state || (dy && !dhT && !dcT));
+  const bool st = !dy || dhT;       // dcT alone is the carry's initial value: no kernel support needed
+  OS2S_REQUIRE(whT && ln && xhat && s_hat && rstd && dgx && dln && workspace && B >= 1 && T >= 1 && H >= 1);
   OS2S_REQUIRE(keep_prob > 0.f && keep_prob <= 1.f);
   if (!lnlstm_shape_ok(B, T, H)) return OS2S_ERR_UNSUPPORTED;
-  OS2S_REQUIRE(lddy >= H && lddy % 8 == 0);
+  OS2S_REQUIRE(!dy || (lddy >= H && lddy % 8 == 0));
   const size_t need = os2s_lnlstm_bwd_workspace_bytes(B, H);
   if (workspace_bytes < need) return OS2S_ERR_WORKSPACE;
   hipStream_t stream = (hipStream_t)stream_;
@@ -578,12 +596,13 @@ extern "C" int os2s_lnlstm_layer_bwd(os2s_stream_t stream_, const uint16_t* whT,
   float* dcc = (float*)ws; ws += align256(bh * 4);
   float* pgrad = (float*)ws;
   if (hipMemsetAsync(workspace, 0, need, stream) != hipSuccess) return OS2S_ERR_LAUNCH;
+  if (dcT && hipMemcpyAsync(dcc, dcT, bh * 4, hipMemcpyDeviceToDevice, stream) != hipSuccess) return OS2S_ERR_LAUNCH;
   // gate gradients of frames past the sequence ends are zero (and are what the step before a sample's last reads)
   if (hipMemsetAsync(dgx, 0, (size_t)B * T * 4 * H * 2, stream) != hipSuccess) return OS2S_ERR_LAUNCH;
   LnProdBwdArgs pa;
   pa.whT = (const bf16_t*)whT; pa.ldg = (long long)T * 4 * H; pa.dhp = dhp; pa.B = B; pa.H = H;
   LnCellBwdArgs ca;
-  ca.dy = (const bf16_t*)dy; ca.lddy = lddy; ca.xhat = (const bf16_t*)xhat; ca.shat = s_hat; ca.rstd = rstd;
+  ca.dy = (const bf16_t*)dy; ca.lddy = lddy; ca.dhT = dhT; ca.xhat = (const bf16_t*)xhat; ca.shat = s_hat; ca.rstd = rstd;
   ca.c0 = c0; ca.ln = ln; ca.dcc = dcc; ca.pgrad = pgrad; ca.dgx = (bf16_t*)dgx; ca.lens = lens;
   ca.B = B; ca.T = T; ca.H = H; ca.forget_bias = forget_bias; ca.keep = keep_prob; ca.seed = seed;
   const bool rows8 = ceil_div(H, 32) * ceil_div(B, 32) < 128;
@@ -597,13 +616,38 @@ extern "C" int os2s_lnlstm_layer_bwd(os2s_stream_t stream_, const uint16_t* whT,
       if (rows8) { OS2S_LAUNCH(lnlstm_prod_bwd_kernel<8>, pgrid, dim3(64 * kLnWaves), 0, stream, pa); }
       else { OS2S_LAUNCH(lnlstm_prod_bwd_kernel<32>, pgrid, dim3(64 * kLnWaves), 0, stream, pa); }
     }
-    if (H <= 512) { OS2S_LAUNCH(lnlstm_cell_bwd_kernel<1>, dim3(B), dim3(64), 0, stream, ca); }
-    else if (H <= 1024) { OS2S_LAUNCH(lnlstm_cell_bwd_kernel<2>, dim3(B), dim3(64), 0, stream, ca); }
-    else { OS2S_LAUNCH(lnlstm_cell_bwd_kernel<4>, dim3(B), dim3(64), 0, stream, ca); }
+    if (st) {
+      if (H <= 512) { OS2S_LAUNCH((lnlstm_cell_bwd_kernel<1, true>), dim3(B), dim3(64), 0, stream, ca); }
+      else if (H <= 1024) { OS2S_LAUNCH((lnlstm_cell_bwd_kernel<2, true>), dim3(B), dim3(64), 0, stream, ca); }
+      else { OS2S_LAUNCH((lnlstm_cell_bwd_kernel<4, true>), dim3(B), dim3(64), 0, stream, ca); }
+    } else {
+      if (H <= 512) { OS2S_LAUNCH((lnlstm_cell_bwd_kernel<1, false>), dim3(B), dim3(64), 0, stream, ca); }
+      else if (H <= 1024) { OS2S_LAUNCH((lnlstm_cell_bwd_kernel<2, false>), dim3(B), dim3(64), 0, stream, ca); }
+      else { OS2S_LAUNCH((lnlstm_cell_bwd_kernel<4, false>), dim3(B), dim3(64), 0, stream, ca); }
+    }
   }
   OS2S_LAUNCH(lnlstm_param_sum_kernel, dim3(ceil_div(10 * H, 256)), dim3(256), 0, stream, (const float*)pgrad, dln, B,
               10 * H);
   return OS2S_OK;
+}
+
+extern "C" int os2s_lnlstm_layer_bwd(os2s_stream_t stream, const uint16_t* whT, const float* ln, const int32_t* lens,
+                                     const uint16_t* dy, long long lddy, const uint16_t* xhat, const float* s_hat,
+                                     const float* rstd, const float* c0, int B, int T, int H, float forget_bias,
+                                     float keep_prob, unsigned long long seed, uint16_t* dgx, float* dln,
+                                     void* workspace, size_t workspace_bytes) {
+  return lnlstm_layer_bwd_impl(stream, whT, ln, lens, dy, lddy, false, nullptr, nullptr, xhat, s_hat, rstd, c0, B, T, H,
+                               forget_bias, keep_prob, seed, dgx, dln, workspace, workspace_bytes);
+}
+
+extern "C" int os2s_lnlstm_layer_bwd_state(os2s_stream_t stream, const uint16_t* whT, const float* ln,
+                                           const int32_t* lens, const uint16_t* dy, long long lddy, const float* dhT,
+                                           const float* dcT, const uint16_t* xhat, const float* s_hat,
+                                           const float* rstd, const float* c0, int B, int T, int H, float forget_bias,
+                                           float keep_prob, unsigned long long seed, uint16_t* dgx, float* dln,
+                                           void* workspace, size_t workspace_bytes) {
+  return lnlstm_layer_bwd_impl(stream, whT, ln, lens, dy, lddy, true, dhT, dcT, xhat, s_hat, rstd, c0, B, T, H, forget_bias,
+                               keep_prob, seed, dgx, dln, workspace, workspace_bytes);
 }
 
 extern "C" int os2s_embed_wdrop_fwd(os2s_stream_t stream, const int32_t* ids, const uint16_t* table, int V, int D,

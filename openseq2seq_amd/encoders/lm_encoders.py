@@ -6,7 +6,12 @@ csrc/lnlstm.hip) with DropoutWrapper output dropout, and the tf.layers.Dense out
 and both gradients land in the one parameter. Layer widths are H, ..., H, and emb_size for the last layer when
 tied (:236-240). Infer (:404-434): one row per seed token, greedy decoding (argmax, re-embed) for up to
 num_tokens_gen steps, ended early once every row has emitted end_token (impute_finished=False), the state carried
-through h0 / c0 -> hT / cT, no dropout. use_cudnn_rnn runs the existing cuDNN-form LSTM kernels."""
+through h0 / c0 -> hT / cT, no dropout. use_cudnn_rnn runs the existing cuDNN-form LSTM kernels.
+
+LMClassifierEncoder is the same network in the text-classification phase (fc_dim = the data layer's num_classes !=
+vocab_size, :362-384): the Dense layer reads the LAST LAYER'S FINAL STATE (h, or [h, c] with use_cell_state), the
+state at step len_b - 1 of each sample, and gives [B, C] logits. LMEncoder itself refuses fc_dim / use_cell_state;
+LSTMLM builds the subclass when its data layer is a TextClassificationDataLayer."""
 from __future__ import absolute_import, division, print_function
 
 import math
@@ -78,10 +83,7 @@ class LMEncoder(Encoder):
   def _unsupported(self):
     """What this package does not build: each raises NotImplementedError naming the parameter."""
     p, training = self.params, self._mode == "train"
-    if not self._lm_phase:
-      raise NotImplementedError("fc_dim != vocab_size (the text-classification phase)")
-    if self._use_cell_state:
-      raise NotImplementedError("use_cell_state (the text-classification phase)")
+    self._unsupported_phase()
     if training and self._num_sampled < self._fc_dim:
       raise NotImplementedError("num_sampled < vocabulary (sampled softmax)")
     for key in ('input_weight_keep_prob', 'recurrent_weight_keep_prob', 'encoder_dp_input_keep_prob',
@@ -94,16 +96,19 @@ class LMEncoder(Encoder):
     if p.get('time_major', False):
       raise NotImplementedError("time_major layouts (batch-major [B,T,...] only)")
 
-  def build(self, store):
-    self._unsupported()
+  def _unsupported_phase(self):
+    if not self._lm_phase:
+      raise NotImplementedError("fc_dim != vocab_size (the text-classification phase: LMClassifierEncoder, which "
+                                "LSTMLM builds over an IMDBDataLayer / SSTDataLayer)")
+    if self._use_cell_state:
+      raise NotImplementedError("use_cell_state (the text-classification phase: LMClassifierEncoder)")
+
+  def _resolve_cells(self):
+    """Checks the cell configuration; sets self.cudnn and self.last (the width of the last layer)."""
     p = self.params
-    first = len(store.params)
-    scope = "ForwardPass/" + self._name
-    V, E = self._vocab_size, self._emb_size
-    self.Vpad = _round8(V)
+    E = self._emb_size
     cp = p['core_cell_params']
     H = int(cp['num_units'])
-    nl = int(p['encoder_layers'])
     self.cudnn = bool(p.get('use_cudnn_rnn', False))
     if self.cudnn:
       if 'CudnnLSTM' not in _token_name(p.get('cudnn_rnn_type')):
@@ -117,29 +122,28 @@ class LMEncoder(Encoder):
       self.last = E if self._weight_tied else H
     if self._weight_tied and self.last != E:
       raise ValueError("weight_tied needs a last layer of emb_size units")
-    last = self.last
-    # the reference wires the regularizer to the Dense kernel only (:228-234)
-    l2 = 0.0
+
+  def _l2_scale(self):
+    p = self.params
     if p.get('regularizer', None) is not None:
-      l2 = float((p.get('regularizer_params', {}) or {}).get('scale', 0.0))
+      return float((p.get('regularizer_params', {}) or {}).get('scale', 0.0))
+    return 0.0
 
-    def init(shape):   # tf.layers.Dense default: glorot_uniform; vocabulary padding rows stay zero
-      lim = math.sqrt(6.0 / (last + V))
-      w = (torch.rand(shape) * 2 - 1) * lim
-      w[:, V:, :] = 0.0
-      return w
+  def _add_embedding(self, store, scope):
+    V, E = self._vocab_size, self._emb_size
 
-    # variables in the reference's creation order: dense/kernel, dense/bias, [EncoderEmbeddingMatrix], the cells.
-    # With weight_tied the kernel's gradient is complete only after the embedding backward, the last closure to run.
-    self.proj = store.add(scope + "/dense/kernel", (1, self.Vpad, last), init, kind="conv", l2=l2, logical_out=V)
-    self.bias = store.add(scope + "/dense/bias", (self.Vpad,), torch.zeros(self.Vpad), kind="vector",
-                          logical_out=V) if p.get('fc_use_bias', True) else None
-    self.emb = None
-    if not self._weight_tied:
-      def init_e(shape):
-        lim = math.sqrt(6.0 / (V + E))
-        return (torch.rand(shape) * 2 - 1) * lim
-      self.emb = store.add(scope + "/EncoderEmbeddingMatrix", (V, E), init_e, kind="dense")
+    def init_e(shape):
+      lim = math.sqrt(6.0 / (V + E))
+      return (torch.rand(shape) * 2 - 1) * lim
+    return store.add(scope + "/EncoderEmbeddingMatrix", (V, E), init_e, kind="dense")
+
+  def _add_cells(self, store, scope, first):
+    """The recurrent layers, then the initializers of everything created since `first`."""
+    p = self.params
+    E, last = self._emb_size, self.last
+    cp = p['core_cell_params']
+    H = int(cp['num_units'])
+    nl = int(p['encoder_layers'])
     self.layers, self.stack = [], None
     if self.cudnn:
       self.stack = BiRNNStack(store, scope + "/cudnn_rnn", "lstm_cudnn", E, E, nl, bidirectional=False)
@@ -158,19 +162,62 @@ class LMEncoder(Encoder):
         val = 1.0 / math.sqrt(layer.H)
         for w in (layer.wx, layer.wh):
           store._inits[w.index] = (lambda shape, val=val: (torch.rand(shape) * 2 - 1) * val)
+
+  def build(self, store):
+    self._unsupported()
+    p = self.params
+    first = len(store.params)
+    scope = "ForwardPass/" + self._name
+    V = self._vocab_size
+    self.Vpad = _round8(V)
+    self._resolve_cells()
+    last = self.last
+    # the reference wires the regularizer to the Dense kernel only (:228-234)
+    l2 = self._l2_scale()
+
+    def init(shape):   # tf.layers.Dense default: glorot_uniform; vocabulary padding rows stay zero
+      lim = math.sqrt(6.0 / (last + V))
+      w = (torch.rand(shape) * 2 - 1) * lim
+      w[:, V:, :] = 0.0
+      return w
+
+    # variables in the reference's creation order: dense/kernel, dense/bias, [EncoderEmbeddingMatrix], the cells.
+    # With weight_tied the kernel's gradient is complete only after the embedding backward, the last closure to run.
+    self.proj = store.add(scope + "/dense/kernel", (1, self.Vpad, last), init, kind="conv", l2=l2, logical_out=V)
+    self.bias = store.add(scope + "/dense/bias", (self.Vpad,), torch.zeros(self.Vpad), kind="vector",
+                          logical_out=V) if p.get('fc_use_bias', True) else None
+    self.emb = None if self._weight_tied else self._add_embedding(store, scope)
+    self._add_cells(store, scope, first)
     self.output_dim = V
     return self
 
   # ---------------------------------------------------------------- pieces
   def _table16(self):
-    return self.proj.w16.view(self.Vpad, self.last) if self._weight_tied else self.emb.w16.view(self._vocab_size, -1)
+    return self.proj.w16.view(self.Vpad, self.last) if self.emb is None else self.emb.w16.view(self._vocab_size, -1)
 
   def _table_grad(self):
-    return self.proj.grad.view(self.Vpad, self.last) if self._weight_tied else self.emb.grad.view(self._vocab_size, -1)
+    return self.proj.grad.view(self.Vpad, self.last) if self.emb is None else self.emb.grad.view(self._vocab_size, -1)
 
   def _logits(self, feat2d):
     return capi.gemm(feat2d, self.proj.w16.view(self.Vpad, self.last),
                      bias=self.bias.master if self.bias is not None else None)
+
+  def _embed(self, ids, lens, emb_keep, emb_seed, tape):
+    """The lookup in the dropped matrix: Act [B,T,E]; its backward scatters into the table's gradient."""
+    B, T = ids.shape
+    E = self._emb_size
+    ids_flat = ids.reshape(-1).to(torch.int32).contiguous()
+    cur = Act(capi.embed_wdrop_fwd(ids_flat, self._table16(), emb_keep, emb_seed).view(B, T, E), lens)
+    if tape is not None:
+      enc, x0 = self, cur
+
+      def emb_backward():
+        if x0.grad is not None:
+          capi.embed_wdrop_bwd(ids_flat, x0.grad.reshape(B * T, E), enc._table_grad(), emb_keep, emb_seed)
+        x0.grad = None
+
+      tape.record(emb_backward, [self.emb if self.emb is not None else self.proj])
+    return cur
 
   # ---------------------------------------------------------------- train / eval
   def _encode(self, input_dict):
@@ -184,18 +231,7 @@ class LMEncoder(Encoder):
     seeds = input_dict.get('seeds') or SeedSeq(p['dropout_seed'])
     keep = (lambda k: p[k]) if training else (lambda k: 1.0)
     V, E, last = self._vocab_size, self._emb_size, self.last
-    ids_flat = ids.reshape(-1).to(torch.int32).contiguous()
-    emb_keep, emb_seed = keep('encoder_emb_keep_prob'), seeds.next()
-    cur = Act(capi.embed_wdrop_fwd(ids_flat, self._table16(), emb_keep, emb_seed).view(B, T, E), lens)
-    if tape is not None:
-      enc, x0 = self, cur
-
-      def emb_backward():
-        if x0.grad is not None:
-          capi.embed_wdrop_bwd(ids_flat, x0.grad.reshape(B * T, E), enc._table_grad(), emb_keep, emb_seed)
-        x0.grad = None
-
-      tape.record(emb_backward, [self.proj if self._weight_tied else self.emb])
+    cur = self._embed(ids, lens, keep('encoder_emb_keep_prob'), seeds.next(), tape)
     if self.cudnn:
       cur = self.stack.forward(cur, lens, tape)
     else:
@@ -272,3 +308,83 @@ class LMEncoder(Encoder):
   @property
   def emb_size(self):
     return self._emb_size
+
+
+class LMClassifierEncoder(LMEncoder):
+  """The text-classification phase (fc_dim != vocab_size). Variables in the reference's creation order: dense/kernel
+  [D, C] (D = last, or 2 last with use_cell_state; stored [C, D]), dense/bias [C], EncoderEmbeddingMatrix [V, E]
+  (always its own variable here, also with weight_tied, :255-262), the cells. DropoutWrapper drops OUTPUTS, so the
+  last layer's encoder_last_output_keep_prob never reaches the classifier; the lower layers' output dropout does.
+  The head is csrc/text_cls.hip: logits [B, C] fp32 from the two fp32 state pointers, and its backward hands dhT /
+  dcT to os2s_lnlstm_layer_bwd_state of the top layer, which gets no gradient on y. Train, eval and infer run the
+  same graph."""
+
+  def __init__(self, params, model, name="rnn_encoder_awd", mode='train'):
+    super(LMClassifierEncoder, self).__init__(params, model, name=name, mode=mode)
+    if 'fc_dim' not in self.params:
+      raise ValueError("LMClassifierEncoder needs fc_dim (the number of classes)")
+    self._lm_phase = False
+    self._batch_size = self.params['batch_size']
+
+  def _unsupported_phase(self):
+    if self.params.get('use_cudnn_rnn', False):
+      raise NotImplementedError("use_cudnn_rnn in the text-classification phase (the final state of the cuDNN-form "
+                                "kernels is not exposed)")
+    if not 2 <= self._fc_dim <= 16:
+      raise NotImplementedError("fc_dim %d (the classification head is built for 2 .. 16 classes)" % self._fc_dim)
+
+  def build(self, store):
+    self._unsupported()
+    p = self.params
+    first = len(store.params)
+    scope = "ForwardPass/" + self._name
+    self.Vpad = _round8(self._vocab_size)
+    self._resolve_cells()
+    C, D = self._fc_dim, (2 if self._use_cell_state else 1) * self.last
+
+    def init(shape):   # tf.layers.Dense default: glorot_uniform
+      return (torch.rand(shape) * 2 - 1) * math.sqrt(6.0 / (D + C))
+
+    self.proj = store.add(scope + "/dense/kernel", (1, C, D), init, kind="conv", l2=self._l2_scale())
+    self.bias = store.add(scope + "/dense/bias", (C,), torch.zeros(C), kind="vector") \
+        if p.get('fc_use_bias', True) else None
+    self.emb = self._add_embedding(store, scope)
+    self._add_cells(store, scope, first)
+    self.output_dim = C
+    return self
+
+  def _encode(self, input_dict):
+    p = self.params
+    ids, lens = input_dict['source_tensors'][0], input_dict['source_tensors'][1]
+    training = self._mode == "train"
+    tape = input_dict.get('tape') if training else None
+    seeds = input_dict.get('seeds') or SeedSeq(p['dropout_seed'])
+    keep = (lambda k: p[k]) if training else (lambda k: 1.0)
+    lens = lens.to(torch.int32).contiguous()
+    cur = self._embed(ids, lens, keep('encoder_emb_keep_prob'), seeds.next(), tape)
+    nl = len(self.layers)
+    state_grad = {}
+    for k, layer in enumerate(self.layers):
+      if k < nl - 1:
+        y = layer.forward(cur, lens, tape, keep_prob=keep('recurrent_keep_prob'), seed=seeds.next())
+        cur = dropout_act(y, keep('encoder_dp_output_keep_prob'), seeds.next(), tape)
+      else:
+        _, hT, cT = layer.forward(cur, lens, tape, keep_prob=keep('recurrent_keep_prob'), seed=seeds.next(),
+                                  want_state=True, state_grad=state_grad)
+    if not self._use_cell_state:
+      cT = None
+    C = self._fc_dim
+    w16 = self.proj.w16.view(C, -1)
+    logits = Act(capi.text_cls_fwd(hT, cT, w16, self.bias.master if self.bias is not None else None))
+    if tape is not None:
+      enc = self
+
+      def backward():
+        dh, dc = capi.text_cls_bwd(hT, cT, w16, logits.grad, enc.proj.grad.view(C, -1),
+                                   enc.bias.grad if enc.bias is not None else None)
+        state_grad.update(dhT=dh, dcT=dc)
+        logits.grad = None
+
+      tape.record(backward, [self.proj] + ([self.bias] if self.bias is not None else []))
+    return {'logits': logits.data, 'logits_act': logits, 'outputs': [logits.data], 'src_lengths': lens,
+            'seeds': seeds}

@@ -261,9 +261,11 @@ class LNLSTMLayer(object):
   def params(self):
     return [self.wx, self.wh] + self.ln
 
-  def forward(self, x, lens, tape, keep_prob=1.0, seed=0, h0=None, c0=None, want_state=False):
+  def forward(self, x, lens, tape, keep_prob=1.0, seed=0, h0=None, c0=None, want_state=False, state_grad=None):
     """x: Act [B,T,In]; lens int32 [B] | None; h0 / c0 fp32 [B,H] | None. Returns Act [B,T,H], or (Act, hT, cT)
-    with want_state. keep_prob: recurrent_keep_prob (the caller passes 1.0 outside training)."""
+    with want_state. keep_prob: recurrent_keep_prob (the caller passes 1.0 outside training). state_grad: a dict
+    that the consumer of hT / cT fills with 'dhT' / 'dcT' (fp32 [B,H]) in its own backward closure, which runs
+    before this layer's; the backward is then os2s_lnlstm_layer_bwd_state and the gradient of y may be absent."""
     B, T, _ = x.data.shape
     H, GH = self.H, 4 * self.H
     x2 = x.data.reshape(B * T, -1)
@@ -276,9 +278,17 @@ class LNLSTMLayer(object):
       layer = self
 
       def backward():
-        assert out.grad is not None, "no gradient reached " + layer.wh.name
-        dgx, dln = capi.lnlstm_layer_bwd(layer.wh.wt16.view(H, GH), ln, lens, out.grad, r["xhat"], r["s_hat"],
-                                         r["rstd"], H, layer.forget_bias, keep_prob, seed, c0)
+        if state_grad is not None:
+          assert out.grad is not None or state_grad.get("dhT") is not None or state_grad.get("dcT") is not None, \
+              "no gradient reached " + layer.wh.name
+          dgx, dln = capi.lnlstm_layer_bwd_state(layer.wh.wt16.view(H, GH), ln, lens, out.grad, state_grad.get("dhT"),
+                                                 state_grad.get("dcT"), r["xhat"], r["s_hat"], r["rstd"], H,
+                                                 layer.forget_bias, keep_prob, seed, c0)
+          state_grad.clear()
+        else:
+          assert out.grad is not None, "no gradient reached " + layer.wh.name
+          dgx, dln = capi.lnlstm_layer_bwd(layer.wh.wt16.view(H, GH), ln, lens, out.grad, r["xhat"], r["s_hat"],
+                                           r["rstd"], H, layer.forget_bias, keep_prob, seed, c0)
         d2 = dgx.view(B * T, GH)
         if x.requires_grad:
           g = x.grad_buffer()

@@ -4,7 +4,9 @@
 --bench_start K] [--<nested/param>=value ...]`; under torchrun (one process per GPU) the
 data-parallel path runs over RCCL. The reference's own example_configs load unchanged.
 Modes: train / train_eval (incl. --benchmark; synthetic batches when the dataset files are
-absent), eval and infer (from the latest checkpoint in logdir). The hot loop mirrors
+absent), eval and infer (from the latest checkpoint in logdir, else in load_model). `load_model` (utils/funcs.py:
+113-140) starts a training whose logdir holds no checkpoint from another model's variables: those whose name AND shape
+match, never the step or the optimizer slots. The hot loop mirrors
 utils/funcs.py:172-218 (objects/sec accounting); checkpoints are written under the reference's
 variable names (openseq2seq_amd/utils/checkpoint.py)."""
 from __future__ import print_function
@@ -52,15 +54,7 @@ def _train(model, args):
   eval_steps = p.get('eval_steps', None)
   logdir = p.get('logdir', None)
   save_steps = p.get('save_checkpoint_steps', None)
-  first_step = 0
-  if logdir and (args.continue_learning or p.get('load_model')):
-    prefix = checkpoint.latest_checkpoint(p.get('load_model') or logdir)
-    if prefix is not None:
-      checkpoint.load(model, prefix, restore_optimizer=args.continue_learning)
-      if args.continue_learning:
-        first_step = checkpoint.read_step(prefix)
-      if rank == 0:
-        deco_print("Restored checkpoint %s (step %d)" % (prefix, first_step))
+  first_step = restore_for_training(model, args, rank)
   total_time, total_objects = 0.0, 0.0
   for step in range(first_step, max_steps):
     if batches is not None:
@@ -109,11 +103,55 @@ def run_eval(model, eval_model, rank, step=None):
   return res
 
 
-def restore_latest(model, rank):
-  logdir = model.params.get('load_model') or model.params.get('logdir')
-  prefix = checkpoint.latest_checkpoint(logdir) if logdir else None
+def restore_for_training(model, args, rank):
+  """What a training starts from; returns its first step. A checkpoint in logdir (under --continue_learning, or
+  when load_model is set) wins: its variables, and under --continue_learning its step and optimizer slots. Only a
+  logdir without one takes load_model's variables (load_partial), at step 0."""
+  p = model.params
+  logdir = p.get('logdir', None)
+  first_step = 0
+  if logdir and (args.continue_learning or p.get('load_model')):
+    own = checkpoint.latest_checkpoint(logdir)
+    if own is None and p.get('load_model'):
+      load_partial(model, p['load_model'], rank)
+    elif own is not None:
+      checkpoint.load(model, own, restore_optimizer=args.continue_learning)
+      if args.continue_learning:
+        first_step = checkpoint.read_step(own)
+      if rank == 0:
+        deco_print("Restored checkpoint %s (step %d)" % (own, first_step))
+  return first_step
+
+
+def load_partial(model, load_model_dir, rank):
+  """utils/funcs.py:113-140: the variables of load_model's latest checkpoint whose name and shape match this model's
+  are restored, the others keep their initial values; both lists are printed."""
+  prefix = checkpoint.latest_checkpoint(load_model_dir)
   if prefix is None:
-    raise IOError("no checkpoint found in %r (eval / infer need a trained model)" % (logdir,))
+    raise IOError("load_model: no checkpoint found in %r" % (load_model_dir,))
+  skipped = checkpoint.load(model, prefix, restore_optimizer=False, strict=False)
+  if rank == 0:
+    names = [v.name for v in model.store.params] + list(model.store.state)
+    deco_print("load_model %s" % prefix)
+    print('VARS_TO_LOAD:')
+    for n in names:
+      if n not in skipped:
+        print(n)
+    print('VARS_SKIPPED (not in the checkpoint, or another shape; initial values kept):')
+    for n in skipped:
+      print(n)
+
+
+def restore_latest(model, rank):
+  """eval / infer: the latest checkpoint of logdir; a model that was never trained here falls back to load_model."""
+  prefix = None
+  for logdir in (model.params.get('logdir'), model.params.get('load_model')):
+    prefix = checkpoint.latest_checkpoint(logdir) if logdir else None
+    if prefix is not None:
+      break
+  if prefix is None:
+    raise IOError("no checkpoint found in %r (eval / infer need a trained model)"
+                  % (model.params.get('logdir') or model.params.get('load_model'),))
   checkpoint.load(model, prefix, restore_optimizer=False)
   if rank == 0:
     deco_print("Restored checkpoint %s" % prefix)
