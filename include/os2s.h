@@ -831,8 +831,10 @@ int os2s_attention_bwd(os2s_stream_t stream, const uint16_t* q, const uint16_t* 
  * (softmax - soft_target). Pass grad_scale = 1/N for the token mean (Transformer) or
  * 1/batch_size with label_smoothing = 0 for BasicSequenceLoss (losses/sequence_loss.py:53-114:
  * sparse softmax xent summed over time, divided by the batch size).
- * logits/dlogits bf16 [N, ld], V % 8 == 0, V <= 40960; columns >= V_valid are vocabulary
- * padding (treated as -inf logits, zero gradient). */
+ * logits/dlogits bf16 [N, ld], V % 8 == 0; columns >= V_valid are vocabulary
+ * padding (treated as -inf logits, zero gradient). Up to V = 40960 a row stays in the registers of
+ * its workgroup; a longer row (the word-level vocabularies of the language models' eval) is
+ * streamed: online max / sum in one pass, the gradient in a second, the same arithmetic. */
 int os2s_xent_smooth(os2s_stream_t stream, const uint16_t* logits, const int32_t* labels,
                      long long N, int V, int V_valid, long long ld, float label_smoothing,
                      float grad_scale, const float* grad_scale_dev, float* row_loss,
@@ -1127,6 +1129,57 @@ int os2s_softmax_xent_dense(os2s_stream_t stream, const float* logits, const flo
                             const float* grad_scale_dev, float* loss, float* dlogits);
 int os2s_text_cls_bwd(os2s_stream_t stream, const float* hT, const float* cT, const uint16_t* w, const float* dlogits,
                       int B, int H, int C, float* dw, float* dbias, float* dhT, float* dcT);
+
+/* ------------------------------------------------------------------------
+ * Sampled softmax of the language model (csrc/sampled_softmax.hip): tf.nn.sampled_softmax_loss as
+ * losses/sequence_loss.py:391-396 calls it (num_true = 1, log-uniform candidate sampler, unique = True,
+ * remove_accidental_hits = True, subtract log Q), on the 'weights' / 'bias' / 'inputs' that
+ * encoders/lm_encoders.py:376-381 hands over in train mode with num_sampled < vocab_size. Rows n < N = B T, x [N,D]
+ * bf16 the last layer's output, l[n] the target, table [V,D] bf16 (the embedding matrix; with weight_tied the
+ * transposed dense/kernel: the same memory), bias [V] fp32, S = num_sampled, Spad = S rounded up to 8.
+ *   p(k) = log((k+2)/(k+1)) / log(V+1)        Q(k) = -expm1(num_tries log1p(-p(k)))
+ *   true[n]   = x[n] . table[l[n]] + bias[l[n]] - log Q(l[n])
+ *   samp[n,j] = x[n] . table[s[j]] + bias[s[j]] - log Q(s[j])      -inf where s[j] == l[n] (an accidental hit)
+ *   row_loss[n] = logsumexp([true[n], samp[n,:]]) - true[n]        loss = grad_scale * sum(row_loss)
+ * and gs = grad_scale * (*grad_scale_dev) multiplies every gradient, as in os2s_xent_smooth. No gradient to Q.
+ * _sample: the candidate sampler (tf.random.log_uniform_candidate_sampler, unique): ONE set of S distinct classes
+ *   per step. Try t = 0, 1, ... draws the uniform hash_u32(seed, t) (csrc/os2s_common.hpp) and maps it to the class
+ *   k with bounds[k-1] <= u < bounds[k], bounds[k] = floor(2^32 log(k+2) / log(V+1)) a HOST-built table of V uint32
+ *   (the last one counts as 2^32): integer compares only on the device. ids [Spad] int32 = the first S distinct
+ *   classes in try order (-1 in the padding), num_tries [1] = the index of the try that gave the S-th, plus one,
+ *   log_q [Spad] fp32 = log Q(ids[j]) (0 in the padding). After max_tries tries the remaining slots are the
+ *   smallest classes not yet drawn, ascending, and num_tries = max_tries. One workgroup, the seen-set a V-bit
+ *   bitmap in LDS; deterministic in (seed, V, S, max_tries). 2 <= V <= 2^20, 1 <= S <= V / 2, else
+ *   OS2S_ERR_UNSUPPORTED (all entries).
+ * _gather: w_s [Spad,D] bf16 = table[ids[j]], b_s [Spad] fp32 = bias[ids[j]] - log_q[j] (bias NULL: 0); padding
+ *   rows zero. samp = x w_s^T + b_s is then os2s_gemm_nt (or the K = 1 convolution) with b_s as its bias.
+ * _loss: logits [N, ld >= Spad] bf16 holds samp on entry. One workgroup per row: true[n] (D MACs, log Q(l[n]) from
+ *   *num_tries on the device), accidental hits and padding columns masked, the row streamed (any S), row_loss [N],
+ *   loss [1] (or NULL) summed in a fixed order, and with want_grad the logits are overwritten by dlogits =
+ *   gs softmax (exactly 0 at hits and padding) and dtrue [N] fp32 = gs (softmax_true - 1). Labels are clamped to
+ *   [0, V-1]; there is no mask (the sampled branch of the reference applies none).
+ * Backward: dX (+)= dlogits w_s and dw_s [Spad,D] fp32 = dlogits^T x are the GEMM entry points; db_s [Spad] the
+ *   column sums of dlogits.
+ * _scatter: dtable[ids[j]] += dw_s[j], dbias[ids[j]] += db_s[j] for j < S (distinct rows: plain adds; dbias / db_s
+ *   may be NULL).
+ * _true_bwd: dx[n] += dtrue[n] table[l[n]] (bf16, dx NULL: skipped), dtable[l[n]] += dtrue[n] x[n], dbias[l[n]] +=
+ *   dtrue[n] (NULL: skipped). Labels repeat: fp32 atomics over whole contiguous rows, or under
+ *   os2s_set_deterministic one thread per 8-column chunk walking the rows in order (bit-identical on a rerun).
+ * D % 8 == 0, the row strides ldx / lddx / ld multiples of 8; table and dtable are contiguous [V,D].
+ * ---------------------------------------------------------------------- */
+int os2s_sampled_softmax_sample(os2s_stream_t stream, const uint32_t* bounds, int V, int S, unsigned long long seed,
+                                int max_tries, int32_t* ids, int32_t* num_tries, float* log_q);
+int os2s_sampled_softmax_gather(os2s_stream_t stream, const int32_t* ids, const float* log_q, const uint16_t* table,
+                                const float* bias, int V, int S, int D, uint16_t* w_s, float* b_s);
+int os2s_sampled_softmax_loss(os2s_stream_t stream, const uint16_t* x, long long ldx, const uint16_t* table,
+                              const float* bias, const int32_t* labels, const int32_t* ids, const int32_t* num_tries,
+                              long long N, int V, int S, int D, uint16_t* logits, long long ld, float grad_scale,
+                              const float* grad_scale_dev, int want_grad, float* row_loss, float* loss, float* dtrue);
+int os2s_sampled_softmax_scatter(os2s_stream_t stream, const int32_t* ids, const float* dw_s, const float* db_s,
+                                 int V, int S, int D, float* dtable, float* dbias);
+int os2s_sampled_softmax_true_bwd(os2s_stream_t stream, const uint16_t* x, long long ldx, const uint16_t* table,
+                                  const int32_t* labels, const float* dtrue, long long N, int V, int D, uint16_t* dx,
+                                  long long lddx, float* dtable, float* dbias);
 
 /* ------------------------------------------------------------------------
  * Attention-RNN decoder loop: the AttentionWrapper cell that tf.contrib.seq2seq.dynamic_decode

@@ -1425,6 +1425,104 @@ def argmax_rows(x2d, v_valid=None):
 
 
 # --------------------------------------------------------------------------
+# Sampled softmax of the language model (csrc/sampled_softmax.hip)
+# --------------------------------------------------------------------------
+SAMPLED_SOFTMAX_MAX_VOCAB = 1 << 20
+
+
+def _check_sampled(V, S):
+  if not 2 <= int(V) <= SAMPLED_SOFTMAX_MAX_VOCAB:
+    raise ValueError("sampled softmax: vocab_size %d is outside 2 .. %d" % (V, SAMPLED_SOFTMAX_MAX_VOCAB))
+  if not 1 <= int(S) <= int(V) // 2:
+    raise ValueError("sampled softmax: num_sampled %d is outside 1 .. vocab_size / 2 = %d" % (S, int(V) // 2))
+
+
+def sampled_softmax_bounds(V):
+  """The host-built table of the candidate sampler: uint32 [V] (held as int32 bits), floor(2^32 log(k+2) /
+  log(V+1)) for class k; the device compares integers only. The last entry is never read (it counts as 2^32)."""
+  import numpy as np
+  b = np.floor(np.log(np.arange(2, int(V) + 2, dtype=np.float64)) / np.log(float(V) + 1.0) * 4294967296.0)
+  return torch.from_numpy(np.minimum(b, 4294967295.0).astype(np.uint32).view(np.int32))
+
+
+def sampled_softmax_sample(bounds, V, S, seed, max_tries=None):
+  """The candidate set of one step: (ids int32 [Spad], num_tries int32 [1], log_q fp32 [Spad]), all on the device
+  of `bounds` (sampled_softmax_bounds(V), uploaded once). max_tries: default 16 S + 64."""
+  _check_sampled(V, S)
+  Spad = -(-int(S) // 8) * 8
+  dev = bounds.device
+  ids = torch.empty(Spad, dtype=torch.int32, device=dev)
+  tries = torch.empty(1, dtype=torch.int32, device=dev)
+  log_q = torch.empty(Spad, dtype=torch.float32, device=dev)
+  _lib.C.os2s_sampled_softmax_sample(_stream(), _ptr(bounds, torch.int32), int(V), int(S), int(seed) & (2**64 - 1),
+                                     16 * int(S) + 64 if max_tries is None else int(max_tries), _ptr(ids),
+                                     _ptr(tries), _ptr(log_q))
+  return ids, tries, log_q
+
+
+def sampled_softmax_candidates(V, S, seed, max_tries=None, device="cuda"):
+  """Test hook: (ids [S], num_tries, log_q [S]) of one sampler launch as numpy arrays / an int."""
+  ids, tries, log_q = sampled_softmax_sample(sampled_softmax_bounds(V).to(device), V, S, seed, max_tries)
+  return ids[:S].cpu().numpy(), int(tries.cpu()[0]), log_q[:S].cpu().numpy()
+
+
+def sampled_softmax_gather(ids, log_q, table, bias, S, V=None):
+  """(w_s bf16 [Spad, D], b_s fp32 [Spad]): the sampled rows of table [>= V, D] and bias[ids] - log_q. V: the
+  logical vocabulary (default: the table's rows; a weight-tied table carries padding rows)."""
+  D = table.shape[1]
+  V = table.shape[0] if V is None else int(V)
+  _check_sampled(V, S)
+  Spad = ids.numel()
+  w_s = torch.empty((Spad, D), dtype=torch.bfloat16, device=table.device)
+  b_s = torch.empty(Spad, dtype=torch.float32, device=table.device)
+  _lib.C.os2s_sampled_softmax_gather(_stream(), _ptr(ids, torch.int32), _ptr(log_q, torch.float32),
+                                     _ptr(table, torch.bfloat16), _ptr(bias, torch.float32, True), V, int(S), D,
+                                     _ptr(w_s), _ptr(b_s))
+  return w_s, b_s
+
+
+def sampled_softmax_loss(x2d, table, bias, labels, ids, num_tries, S, logits, grad_scale, grad_scale_dev=None,
+                         want_grad=True, V=None):
+  """logits [N, Spad] bf16 = the sampled logits, overwritten by dlogits with want_grad. Returns (row_loss [N],
+  loss [1] = grad_scale * sum(row_loss), dtrue [N] | None)."""
+  N, D = x2d.shape
+  V = table.shape[0] if V is None else int(V)
+  _check_sampled(V, S)
+  dev = x2d.device
+  row_loss = torch.empty(N, dtype=torch.float32, device=dev)
+  loss = torch.empty(1, dtype=torch.float32, device=dev)
+  dtrue = torch.empty(N, dtype=torch.float32, device=dev) if want_grad else None
+  _lib.C.os2s_sampled_softmax_loss(_stream(), c_void_p(x2d.data_ptr()), x2d.stride(0), _ptr(table, torch.bfloat16),
+                                   _ptr(bias, torch.float32, True), _ptr(labels, torch.int32),
+                                   _ptr(ids, torch.int32), _ptr(num_tries, torch.int32), N, V, int(S), D,
+                                   c_void_p(logits.data_ptr()), logits.stride(0), float(grad_scale),
+                                   _ptr(grad_scale_dev, torch.float32, True), int(want_grad), _ptr(row_loss),
+                                   _ptr(loss), _ptr(dtrue, None, True))
+  return row_loss, loss, dtrue
+
+
+def sampled_softmax_scatter(ids, dw_s, db_s, S, dtable, dbias, V=None):
+  """dtable[ids[j]] += dw_s[j], dbias[ids[j]] += db_s[j] for j < S."""
+  D = dtable.shape[1]
+  V = dtable.shape[0] if V is None else int(V)
+  _lib.C.os2s_sampled_softmax_scatter(_stream(), _ptr(ids, torch.int32), _ptr(dw_s, torch.float32),
+                                      _ptr(db_s, torch.float32, True), V, int(S), D, _ptr(dtable, torch.float32),
+                                      _ptr(dbias, torch.float32, True))
+
+
+def sampled_softmax_true_bwd(x2d, table, labels, dtrue, dx2d, dtable, dbias, V=None):
+  """dx[n] += dtrue[n] table[l[n]], dtable[l[n]] += dtrue[n] x[n], dbias[l[n]] += dtrue[n]."""
+  N, D = x2d.shape
+  V = table.shape[0] if V is None else int(V)
+  _lib.C.os2s_sampled_softmax_true_bwd(_stream(), c_void_p(x2d.data_ptr()), x2d.stride(0),
+                                       _ptr(table, torch.bfloat16), _ptr(labels, torch.int32),
+                                       _ptr(dtrue, torch.float32), N, V, D,
+                                       c_void_p(dx2d.data_ptr()) if dx2d is not None else None,
+                                       dx2d.stride(0) if dx2d is not None else 0, _ptr(dtable, torch.float32),
+                                       _ptr(dbias, torch.float32, True))
+
+
+# --------------------------------------------------------------------------
 # Transformer beam search / incremental decoding
 # --------------------------------------------------------------------------
 class BeamState(object):

@@ -4,7 +4,7 @@ entries, Adam at a fixed learning rate), with the sizes as arguments."""
 from ..data.lm.lmdata import WKTDataLayer
 from ..decoders.fake_decoder import FakeDecoder
 from ..encoders.lm_encoders import LMEncoder
-from ..losses.sequence_loss import BasicSequenceLoss
+from ..losses.sequence_loss import BasicSampledSequenceLoss, BasicSequenceLoss
 from ..models.lstm_lm import LSTMLM
 from ..optimizers.lr_policies import fixed_lr
 from ..parts.rnns.weight_drop import WeightDropLayerNormBasicLSTMCell
@@ -12,9 +12,10 @@ from ..parts.rnns.weight_drop import WeightDropLayerNormBasicLSTMCell
 
 def lstm_lm_config(data_root, processed_data_folder, batch_size_per_gpu=160, bptt=96, layers=3, num_units=896,
                    emb_size=256, learning_rate=4e-4, dropout=True, seed_tokens="The", num_tokens_gen=10,
-                   logdir=None, max_steps=None):
+                   logdir=None, max_steps=None, num_sampled=None):
   """Returns (base_model, base_params, train_params, eval_params, infer_params). dropout: the wkt2 config's keep
-  probabilities (output 0.6, recurrent 0.7, embedding matrix 0.37), else 1.0 everywhere."""
+  probabilities (output 0.6, recurrent 0.7, embedding matrix 0.37), else 1.0 everywhere. num_sampled: train with the
+  sampled softmax of lstm-wkt103-mixed.py (BasicSampledSequenceLoss; eval stays the full softmax)."""
   keep = (lambda v: v) if dropout else (lambda v: 1.0)
   base_params = {
       "random_seed": 0, "use_horovod": False, "num_gpus": 1, "batch_size_per_gpu": batch_size_per_gpu,
@@ -40,6 +41,9 @@ def lstm_lm_config(data_root, processed_data_folder, batch_size_per_gpu=160, bpt
       "loss": BasicSequenceLoss,
       "loss_params": {"offset_target_by_one": False, "average_across_timestep": True, "do_mask": False},
   }
+  if num_sampled is not None:
+    base_params["encoder_params"]["num_sampled"] = int(num_sampled)
+    base_params["loss"] = BasicSampledSequenceLoss
   if logdir is not None:
     base_params["logdir"] = logdir
   if max_steps is not None:

@@ -548,6 +548,89 @@ __global__ __launch_bounds__(256) void xent_smooth_kernel(
   }
 }
 
+// The same loss for rows too long for the register-resident kernel (V > 40960: the word-level vocabularies of the
+// language models): the row is streamed, online max / sum of exponentials in one pass, the gradient in a second.
+__global__ __launch_bounds__(256) void xent_smooth_stream_kernel(
+    const bf16_t* __restrict__ logits, const int32_t* __restrict__ labels, int V, int v_valid,
+    long long ld, float confidence, float low_confidence, float normalizing, float grad_scale_host,
+    const float* __restrict__ grad_scale_dev, float* __restrict__ row_loss,
+    bf16_t* __restrict__ dlogits) {
+  __shared__ float red_m[4], red_s[4], red_x[4];
+  __shared__ float bc[2];
+  const long long row = blockIdx.x;
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  const int V8 = V >> 3;
+  const bf16_t* lr = logits + row * ld;
+  const int label = labels[row];
+  if (label < 0) {   // masked position: no loss, no gradient
+    if (threadIdx.x == 0 && row_loss) row_loss[row] = 0.f;
+    if (dlogits) {
+      const u32x4 z = {0u, 0u, 0u, 0u};
+      for (int i = threadIdx.x; i < V8; i += 256)
+        *reinterpret_cast<u32x4*>(dlogits + row * ld + (long long)i * 8) = z;
+    }
+    return;
+  }
+  float m = -INFINITY, s = 0.f, sx = 0.f;
+  for (int i = threadIdx.x; i < V8; i += 256) {
+    const u32x4 t = *reinterpret_cast<const u32x4*>(lr + (long long)i * 8);
+    float v[8] = {bflo(t[0]), bfhi(t[0]), bflo(t[1]), bfhi(t[1]), bflo(t[2]), bfhi(t[2]), bflo(t[3]), bfhi(t[3])};
+    float vm = -INFINITY;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      if (i * 8 + e >= v_valid) v[e] = -INFINITY;   // vocabulary padding columns
+      vm = fmaxf(vm, v[e]);
+      sx += v[e] > -INFINITY ? v[e] : 0.f;
+    }
+    if (vm > -INFINITY) {
+      const float mn = fmaxf(m, vm);
+      float add = 0.f;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) add += __expf(v[e] - mn);
+      s = s * __expf(m - mn) + add;
+      m = mn;
+    }
+  }
+  const float wm = wave_max(m);
+  s = wave_sum(m > -INFINITY ? s * __expf(m - wm) : 0.f);
+  sx = wave_sum(sx);
+  if (lane == 0) { red_m[wid] = wm; red_s[wid] = s; red_x[wid] = sx; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const float M = fmaxf(fmaxf(red_m[0], red_m[1]), fmaxf(red_m[2], red_m[3]));
+    float tot = 0.f;
+    for (int w = 0; w < 4; ++w) tot += red_m[w] > -INFINITY ? red_s[w] * __expf(red_m[w] - M) : 0.f;
+    bc[0] = M + __logf(tot);
+    bc[1] = (red_x[0] + red_x[1]) + (red_x[2] + red_x[3]);
+  }
+  __syncthreads();
+  const float lse = bc[0];
+  sx = bc[1];
+  const float x_label = bf2f(lr[label]);
+  const float sum_logp = sx - (float)v_valid * lse;
+  const float logp_label = x_label - lse;
+  const float xent = -(confidence * logp_label + low_confidence * (sum_logp - logp_label)) - normalizing;
+  if (threadIdx.x == 0 && row_loss) row_loss[row] = xent;
+  if (dlogits) {
+    const float gs = grad_scale_dev ? grad_scale_host * (*grad_scale_dev) : grad_scale_host;
+    bf16_t* dr = dlogits + row * ld;
+    for (int i = threadIdx.x; i < V8; i += 256) {
+      const u32x4 t = *reinterpret_cast<const u32x4*>(lr + (long long)i * 8);
+      u32x4 o;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const int c = i * 8 + 2 * e;
+        const float p0 = c < v_valid ? __expf(bflo(t[e]) - lse) : 0.f;
+        const float p1 = c + 1 < v_valid ? __expf(bfhi(t[e]) - lse) : 0.f;
+        const float t0 = (c == label) ? confidence : (c < v_valid ? low_confidence : 0.f);
+        const float t1 = (c + 1 == label) ? confidence : (c + 1 < v_valid ? low_confidence : 0.f);
+        o[e] = pack2bf((p0 - t0) * gs, (p1 - t1) * gs);
+      }
+      *reinterpret_cast<u32x4*>(dr + (long long)i * 8) = o;
+    }
+  }
+}
+
 // argmax over the first v_valid columns of each bf16 row (first maximum wins, as tf.argmax)
 __global__ __launch_bounds__(256) void argmax_rows_kernel(const bf16_t* __restrict__ x, long long N,
                                                           int v_valid, long long ld,
@@ -738,13 +821,17 @@ extern "C" int os2s_xent_smooth(os2s_stream_t stream, const uint16_t* logits, co
                                 uint16_t* dlogits) {
   OS2S_REQUIRE(logits && labels && N >= 1 && V >= 8 && V % 8 == 0 && ld % 8 == 0 && row_loss);
   OS2S_REQUIRE(V_valid >= 2 && V_valid <= V);
-  if (V > 256 * 8 * kXentMaxPerThread) return OS2S_ERR_UNSUPPORTED;
   const float confidence = 1.f - label_smoothing;
   const float low = (1.f - confidence) / (float)(V_valid - 1);
   const float normalizing =
       -(confidence * logf(confidence) + (float)(V_valid - 1) * low * logf(low + 1e-20f));
-  OS2S_LAUNCH(xent_smooth_kernel, dim3((unsigned)N), dim3(256), 0, (hipStream_t)stream, logits, labels,
-              V, V_valid, ld, confidence, low, normalizing, grad_scale, grad_scale_dev, row_loss, dlogits);
+  if (V > 256 * 8 * kXentMaxPerThread) {   // the row does not fit the registers of one workgroup: streamed
+    OS2S_LAUNCH(xent_smooth_stream_kernel, dim3((unsigned)N), dim3(256), 0, (hipStream_t)stream, logits, labels,
+                V, V_valid, ld, confidence, low, normalizing, grad_scale, grad_scale_dev, row_loss, dlogits);
+  } else {
+    OS2S_LAUNCH(xent_smooth_kernel, dim3((unsigned)N), dim3(256), 0, (hipStream_t)stream, logits, labels,
+                V, V_valid, ld, confidence, low, normalizing, grad_scale, grad_scale_dev, row_loss, dlogits);
+  }
   if (loss_mean) {
     OS2S_LAUNCH(sum_rows_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, row_loss, N,
                 grad_scale, loss_mean);

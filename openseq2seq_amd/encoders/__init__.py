@@ -5,4 +5,4 @@ from .ds2_encoder import DeepSpeech2Encoder
 from .rnn_encoders import (BidirectionalRNNEncoderWithEmbedding, UnidirectionalRNNEncoderWithEmbedding,
                            GNMTLikeEncoderWithEmbedding)
 from .tacotron2_encoder import Tacotron2Encoder
-from .lm_encoders import LMEncoder, LMClassifierEncoder
+from .lm_encoders import LMEncoder, LMClassifierEncoder, LMSampledEncoder

@@ -11,7 +11,11 @@ through h0 / c0 -> hT / cT, no dropout. use_cudnn_rnn runs the existing cuDNN-fo
 LMClassifierEncoder is the same network in the text-classification phase (fc_dim = the data layer's num_classes !=
 vocab_size, :362-384): the Dense layer reads the LAST LAYER'S FINAL STATE (h, or [h, c] with use_cell_state), the
 state at step len_b - 1 of each sample, and gives [B, C] logits. LMEncoder itself refuses fc_dim / use_cell_state;
-LSTMLM builds the subclass when its data layer is a TextClassificationDataLayer."""
+LSTMLM builds the subclass when its data layer is a TextClassificationDataLayer.
+
+LMSampledEncoder is the LM phase trained with num_sampled < vocab_size (:375-381, lstm-wkt103-mixed.py): in train
+mode it stops before the output layer and hands the table, the bias and the last layer's output to
+BasicSampledSequenceLoss (parts/sampled_softmax.py); LSTMLM builds it in place of LMEncoder for such a training."""
 from __future__ import absolute_import, division, print_function
 
 import math
@@ -21,8 +25,10 @@ import torch
 from .encoder import Encoder
 from .rnn_encoders import apply_scope_initializer, dropout_act
 from .. import capi
+from ..parts import sampled_softmax
 from ..parts.dense import SeedSeq, bias_grad_from_rows
 from ..parts.rnns.rnn_layers import BiRNNStack, LNLSTMLayer
+from ..parts.sampled_softmax import CandidateSampler
 from ..parts.streams import on_side_stream
 from ..parts.tape import Act
 
@@ -85,7 +91,8 @@ class LMEncoder(Encoder):
     p, training = self.params, self._mode == "train"
     self._unsupported_phase()
     if training and self._num_sampled < self._fc_dim:
-      raise NotImplementedError("num_sampled < vocabulary (sampled softmax)")
+      raise NotImplementedError("num_sampled < vocabulary (sampled softmax: LMSampledEncoder, which LSTMLM builds "
+                                "for training; not with use_cudnn_rnn)")
     for key in ('input_weight_keep_prob', 'recurrent_weight_keep_prob', 'encoder_dp_input_keep_prob',
                 'encoder_last_input_keep_prob'):
       if p[key] < 1.0:
@@ -387,4 +394,79 @@ class LMClassifierEncoder(LMEncoder):
 
       tape.record(backward, [self.proj] + ([self.bias] if self.bias is not None else []))
     return {'logits': logits.data, 'logits_act': logits, 'outputs': [logits.data], 'src_lengths': lens,
+            'seeds': seeds}
+
+
+class LMSampledEncoder(LMEncoder):
+  """The LM phase trained with num_sampled < vocab_size (:375-381): in train mode the output layer is not applied;
+  the encoder hands 'weights' (enc_emb_w, the undropped [V, E] table: the transposed dense/kernel with weight_tied,
+  else EncoderEmbeddingMatrix, which is then what sampled training updates), 'bias' (dense/bias), 'inputs' (the last
+  layer's output) and 'num_sampled' to BasicSampledSequenceLoss. 'sampled' carries what the loss needs beside
+  them: the candidate set of the step, drawn on the side stream before the recurrence is enqueued, and the hook
+  that receives the loss's state for the backward closure recorded here (parts/sampled_softmax.py). Eval and infer
+  are LMEncoder unchanged (the full softmax). use_cudnn_rnn keeps LMEncoder's refusal of num_sampled."""
+
+  def _unsupported(self):
+    if self._mode != "train" or self.params.get('use_cudnn_rnn', False) or not self._num_sampled < self._fc_dim:
+      return super(LMSampledEncoder, self)._unsupported()
+    mine, self._num_sampled = self._num_sampled, self._fc_dim
+    try:
+      super(LMSampledEncoder, self)._unsupported()
+    finally:
+      self._num_sampled = mine
+
+  @property
+  def sampled(self):
+    return self._mode == "train" and self._num_sampled < self._fc_dim
+
+  def build(self, store):
+    if self.sampled:
+      p, V, S = self.params, self._vocab_size, self._num_sampled
+      if not p.get('fc_use_bias', True):
+        raise ValueError("fc_use_bias: False with num_sampled < vocab_size (the sampled softmax reads dense/bias)")
+      if not self._weight_tied and int(p['core_cell_params']['num_units']) != self._emb_size:
+        raise ValueError("emb_size %d differs from the last layer's num_units %d and weight_tied is off: the sampled "
+                         "softmax multiplies the last layer's output with the embedding matrix"
+                         % (self._emb_size, int(p['core_cell_params']['num_units'])))
+      if not (2 <= V <= capi.SAMPLED_SOFTMAX_MAX_VOCAB and 1 <= S <= V // 2):
+        raise ValueError("num_sampled %d with vocab_size %d (1 <= num_sampled <= vocab_size / 2, vocab_size <= %d)"
+                         % (S, V, capi.SAMPLED_SOFTMAX_MAX_VOCAB))
+    super(LMSampledEncoder, self).build(store)
+    if self.sampled:
+      self.sampler = CandidateSampler(self._vocab_size, self._num_sampled)
+    return self
+
+  def _encode(self, input_dict):
+    if not self.sampled:
+      return super(LMSampledEncoder, self)._encode(input_dict)
+    p = self.params
+    ids, lens = input_dict['source_tensors'][0], input_dict['source_tensors'][1]
+    B, T = ids.shape
+    tape = input_dict.get('tape')
+    seeds = input_dict.get('seeds') or SeedSeq(p['dropout_seed'])
+    last = self.last
+    cand = self.sampler.draw(seeds.next(), ids.device)      # depends on its seed alone: hides under the recurrence
+    cur = self._embed(ids, lens, p['encoder_emb_keep_prob'], seeds.next(), tape)
+    nl = len(self.layers)
+    for k, layer in enumerate(self.layers):
+      y = layer.forward(cur, lens, tape, keep_prob=p['recurrent_keep_prob'], seed=seeds.next())
+      okeep = p['encoder_last_output_keep_prob' if k == nl - 1 else 'encoder_dp_output_keep_prob']
+      cur = dropout_act(y, okeep, seeds.next(), tape)
+    hook = {'candidates': cand, 'vocab_size': self._vocab_size, 'state': None}
+    if tape is not None:
+      enc, top = self, cur
+
+      def backward():
+        st = hook['state']
+        assert st is not None, "BasicSampledSequenceLoss left no gradient for the sampled softmax"
+        g = top.grad_buffer()
+        sampled_softmax.backward(st, g.view(B * T, last), top.grad_init, enc._table_grad(), enc.bias.grad)
+        top.grad_init = True
+        hook['state'] = None
+
+      # the table's gradient is complete only after the embedding backward; without weight_tied dense/kernel is not
+      # part of the sampled graph and is final (zero) here
+      tape.record(backward, [self.bias] + ([] if self._weight_tied else [self.proj]))
+    return {'weights': self._table16(), 'bias': self.bias.master, 'inputs': cur.data, 'logits': cur.data,
+            'outputs': [cur.data], 'num_sampled': self._num_sampled, 'sampled': hook, 'src_lengths': lens,
             'seeds': seeds}

@@ -99,23 +99,38 @@ class BasicSequenceLoss(Loss):
     return loss
 
 
-class BasicSampledSequenceLoss(Loss):
-  """Sampled softmax of the language model (losses/sequence_loss.py, `num_sampled` of lstm-wkt103-mixed.py): not
-  built. The class exists so that the config loads; LMEncoder raises the NotImplementedError that names
-  num_sampled when it is built for training, and so does constructing this loss."""
-
-  @staticmethod
-  def get_required_params():
-    return dict(Loss.get_required_params(), **{'tgt_vocab_size': int, 'batch_size': int})
+class BasicSampledSequenceLoss(BasicSequenceLoss):
+  """losses/sequence_loss.py:312-443, both branches of its _compute_loss. With 'weights' in the decoder output (the
+  LM trained with num_sampled < vocab_size, LMSampledEncoder): tf.nn.sampled_softmax_loss of every [B T] row against
+  the target reshaped (-1, 1) -- no mask and no target offset, as the reference's sampled branch -- averaged, or
+  summed and divided by the batch size (parts/sampled_softmax.py, csrc/sampled_softmax.hip). Otherwise exactly
+  BasicSequenceLoss's arithmetic on the logits: eval of such a model."""
 
   @staticmethod
   def get_optional_params():
-    return dict(Loss.get_optional_params(), **{
-        'offset_target_by_one': bool, 'average_across_timestep': bool, 'do_mask': bool, 'hid_dim': int,
-    })
+    return dict(BasicSequenceLoss.get_optional_params(), **{'hid_dim': int})
 
   def __init__(self, params, model, name="basic_sampled_sequence_loss"):
-    raise NotImplementedError("num_sampled < vocabulary (sampled softmax, BasicSampledSequenceLoss)")
+    super(BasicSampledSequenceLoss, self).__init__(params, model, name)
 
   def _compute_loss(self, input_dict):
-    raise NotImplementedError("num_sampled < vocabulary (sampled softmax, BasicSampledSequenceLoss)")
+    dec = input_dict["decoder_output"]
+    if 'weights' not in dec:
+      return super(BasicSampledSequenceLoss, self)._compute_loss(input_dict)
+    from ..parts import sampled_softmax
+    import torch
+    inputs, hook = dec['inputs'], dec['sampled']
+    D = inputs.shape[-1]
+    x2d = inputs.reshape(-1, D)
+    N = x2d.shape[0]
+    labels = input_dict['target_tensors'][0].reshape(-1).to(torch.int32).contiguous()
+    if labels.numel() != N:
+      raise ValueError("sampled softmax: %d target tokens for %d rows of inputs" % (labels.numel(), N))
+    scale = 1.0 / N if self._average_across_timestep else 1.0 / self._batch_size
+    want_grad = input_dict.get("want_grad", True)
+    loss, state = sampled_softmax.forward(x2d, dec['weights'], dec['bias'], labels, hook['candidates'],
+                                          dec['num_sampled'], hook['vocab_size'], scale,
+                                          input_dict.get("loss_scale_dev"), want_grad)
+    if want_grad:
+      hook['state'] = state
+    return loss

@@ -17,7 +17,7 @@ import numpy as np
 
 from .encoder_decoder import EncoderDecoderModel
 from ..data.lm.lmdata import TextClassificationDataLayer, WKTDataLayer
-from ..encoders.lm_encoders import LMClassifierEncoder, LMEncoder
+from ..encoders.lm_encoders import LMClassifierEncoder, LMEncoder, LMSampledEncoder
 from ..utils import metrics
 from ..parts.dense import SeedSeq
 from ..utils.utils import deco_print
@@ -77,6 +77,11 @@ class LSTMLM(EncoderDecoderModel):
     if not self._lm_phase and cls is LMEncoder:
       # the classification network is LMEncoder's subclass (LMEncoder itself refuses fc_dim / use_cell_state)
       return LMClassifierEncoder(params=self.params['encoder_params'], mode=self.mode, model=self)
+    ep = self.params['encoder_params']
+    if self._lm_phase and cls is LMEncoder and self.mode == 'train' and not ep.get('use_cudnn_rnn', False) and \
+        ep.get('num_sampled', ep['vocab_size']) < ep['vocab_size']:
+      # sampled softmax training (encoders/lm_encoders.py:375-381): the subclass that stops before the output layer
+      return LMSampledEncoder(params=ep, mode=self.mode, model=self)
     return super(LSTMLM, self)._create_encoder()
 
   def _forward(self, batch, tape, want_grad=True):
