@@ -809,15 +809,20 @@ int os2s_add_bf16(os2s_stream_t stream, const uint16_t* a, const uint16_t* b, lo
  * lower-triangular band (utils.py:57-79). lse [Nq, H] is saved for the backward, which
  * recomputes the probabilities. dh in {8, 16, 32, 64, 128} (64 is the tuned kernel family, the other four share
  * one family templated on the head dim; anything else: OS2S_ERR_UNSUPPORTED). The dropout mask is element
- * ((b*H + h)*64 + q)*64 + key whatever dh. Training (backward, attention dropout) is
- * implemented for max_len <= 64 (the length-filtered training sets of the configs); the
- * forward without dropout takes any max_len (eval / infer batches): one wave per 64-query
- * tile walks the key tiles with an online softmax. OS2S_ERR_UNSUPPORTED otherwise. */
+ * ((b*H + h)*Lp + q)*Lp + key of the generator behind os2s_dropout_mask whatever dh, with q and key counted from
+ * the start of the sequence, Lp = max_len rounded up to a multiple of 64, in 64-bit arithmetic: it depends on the
+ * launch's max_len, so forward and backward must be given the same one. Two kernel families, chosen by max_len:
+ *   max_len <= 64 (the length-filtered training sets of the configs): one-tile kernels, forward and backward
+ *     (os2s_attention_bwd), with or without attention dropout;
+ *   max_len > 64, at most 65536 (OS2S_ERR_INVALID_ARG beyond; B * H * ceil(max_len / 64) < 2^31): the forward
+ *     walks the key tiles with an online softmax, one wave per 64-query tile, with or without dropout; the
+ *     backward is os2s_attention_bwd_long. No sequence may be longer than max_len. */
 int os2s_attention_fwd(os2s_stream_t stream, const uint16_t* q, const uint16_t* k,
                        const uint16_t* v, uint16_t* o, float* lse, const int32_t* cu_q,
                        const int32_t* cu_k, int B, int H, int dh, int max_len,
                        long long ldq, long long ldk, long long ldv, long long ldo,
                        int causal, float scale, float keep_prob, unsigned long long seed);
+/* max_len <= 64 only (OS2S_ERR_UNSUPPORTED beyond: os2s_attention_bwd_long takes those). */
 int os2s_attention_bwd(os2s_stream_t stream, const uint16_t* q, const uint16_t* k,
                        const uint16_t* v, const uint16_t* d_o, const float* lse,
                        uint16_t* dq, uint16_t* dk, uint16_t* dv, const int32_t* cu_q,
@@ -825,6 +830,22 @@ int os2s_attention_bwd(os2s_stream_t stream, const uint16_t* q, const uint16_t* 
                        long long ldq, long long ldk, long long ldv, long long lddo,
                        long long lddq, long long lddk, long long lddv, int causal,
                        float scale, float keep_prob, unsigned long long seed);
+/* The backward of Attention.call (the gradient of the two tf.matmul, the softmax and the dropout of
+ * parts/transformer/attention_layer.py:152-213, which has no length limit) for max_len > 64 (max_len <= 64: OS2S_ERR_INVALID_ARG, that is os2s_attention_bwd). The arguments of
+ * os2s_attention_bwd plus a workspace delta [Nq, H] fp32, which receives delta[q][h] = sum_d dO[q][h*dh + d] *
+ * O[q][h*dh + d] of an UNROUNDED O: it is obtained as sum_key P (dPd o m / keep) in a first sweep over the key
+ * tiles, in fp32, so the forward's output is not an argument (taken from the bf16 o, delta costs the gradients of
+ * queries that attend to one or two keys their accuracy). Tile-walking: P is recomputed per 64 x 64 tile from
+ * (q, k, lse). Two launches — one workgroup per (batch, head, 64-query tile) owns dq (and computes delta), one per
+ * (batch, head, 64-key tile) owns dk and dv — with plain stores only: no float atomics, bitwise reproducible
+ * from run to run. */
+int os2s_attention_bwd_long(os2s_stream_t stream, const uint16_t* q, const uint16_t* k,
+                            const uint16_t* v, const uint16_t* d_o, const float* lse, float* delta,
+                            uint16_t* dq, uint16_t* dk, uint16_t* dv, const int32_t* cu_q,
+                            const int32_t* cu_k, int B, int H, int dh, int max_len, long long ldq,
+                            long long ldk, long long ldv, long long lddo, long long lddq,
+                            long long lddk, long long lddv, int causal, float scale,
+                            float keep_prob, unsigned long long seed);
 /* PaddedCrossEntropyLossWithSmoothing (losses/sequence_loss.py:257-309) over the N
  * non-pad target rows: row_loss[n] = xent(soft targets) - normalizing constant;
  * loss_mean = grad_scale * sum(row_loss); dlogits = grad_scale * (*grad_scale_dev) *

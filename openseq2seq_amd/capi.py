@@ -1362,6 +1362,7 @@ def add_bf16(a, b, out=None):
 
 
 ATTENTION_HEAD_DIMS = (8, 16, 32, 64, 128)
+ATTENTION_TILE = 64      # max_len up to here: the one-tile kernels; beyond: the tile-walking family
 
 
 def _check_head_dim(dh):
@@ -1388,8 +1389,21 @@ def attention_fwd(q, k, v, cu_q, cu_k, H, max_len, causal, scale, keep_prob=1.0,
 
 def attention_bwd(q, k, v, d_o, lse, dq, dk, dv, cu_q, cu_k, H, max_len, causal, scale,
                   keep_prob=1.0, seed=0, dh=64):
+  """Gradients of attention_fwd into dq / dk / dv (bf16 row-major views, any row stride). max_len, keep_prob and
+  seed as given to the forward. max_len <= ATTENTION_TILE launches the one-tile kernels; beyond it the
+  tile-walking backward (os2s_attention_bwd_long, with its [Nq, H] fp32 workspace)."""
   dh = _check_head_dim(dh)
   B = cu_q.numel() - 1
+  if int(max_len) > ATTENTION_TILE:
+    delta = torch.empty((q.shape[0], H), dtype=torch.float32, device=q.device)
+    _lib.C.os2s_attention_bwd_long(_stream(), c_void_p(q.data_ptr()), c_void_p(k.data_ptr()),
+                                   c_void_p(v.data_ptr()), _ptr(d_o, torch.bfloat16), _ptr(lse, torch.float32),
+                                   _ptr(delta), c_void_p(dq.data_ptr()), c_void_p(dk.data_ptr()),
+                                   c_void_p(dv.data_ptr()), _ptr(cu_q, torch.int32), _ptr(cu_k, torch.int32), B, H,
+                                   dh, int(max_len), q.stride(0), k.stride(0), v.stride(0), d_o.stride(0),
+                                   dq.stride(0), dk.stride(0), dv.stride(0), int(causal), float(scale),
+                                   float(keep_prob), int(seed) & (2**64 - 1))
+    return
   _lib.C.os2s_attention_bwd(_stream(), c_void_p(q.data_ptr()), c_void_p(k.data_ptr()), c_void_p(v.data_ptr()),
                             _ptr(d_o, torch.bfloat16), _ptr(lse, torch.float32), c_void_p(dq.data_ptr()),
                             c_void_p(dk.data_ptr()), c_void_p(dv.data_ptr()), _ptr(cu_q, torch.int32),

@@ -1,7 +1,10 @@
-// Multi-head scaled-dot-product attention (forward + backward) for short
-// sequences (Lq, Lk <= 64: the training regime of the Transformer configs,
-// max_length 56 in example_configs/text2text/en-de/transformer-big.py:104),
-// on PACKED token-major tensors, gfx950.
+// Multi-head scaled-dot-product attention (forward + backward) on PACKED token-major
+// tensors, gfx950. This file holds the kernels tuned for short sequences (Lq, Lk <= 64: the
+// training regime of the shipped Transformer configs, max_length 56 in
+// example_configs/text2text/en-de/transformer-big.py:104) at head dim 64, and the multi-tile
+// forward without dropout (eval / infer). attention_dh.hpp has the same for head dims 8, 16, 32
+// and 128, and the multi-tile forward WITH dropout at every head dim; attention_long.hpp has
+// the multi-tile backward (max_len > 64: two launches, no atomics) at every head dim.
 //
 // Reference: Attention.call (open_seq2seq/parts/transformer/attention_layer.py:104-220):
 //   q *= depth**-0.5; logits = q k^T (fp32 softmax when activations are half precision)
@@ -657,6 +660,7 @@ __global__ __launch_bounds__(kBwdThreads) void attn_bwd_kernel(AttnArgs p) {
 }  // namespace os2s
 
 #include "attention_dh.hpp"      // the same three kernels for head dims 8, 16, 32 and 128
+#include "attention_long.hpp"    // the multi-tile backward (max_len > 64), every head dim
 
 using namespace os2s;
 
@@ -688,13 +692,18 @@ extern "C" int os2s_attention_fwd(os2s_stream_t stream, const uint16_t* q, const
   a.q = q; a.k = k; a.v = v; a.o = o; a.lse = lse; a.cu_q = cu_q; a.cu_k = cu_k; a.B = B; a.H = H;
   a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.ldo = ldo; a.causal = causal; a.scale = scale;
   a.keep_prob = keep_prob; a.seed = seed;
+  if (max_len > kL && keep_prob < 1.f) {      // multi-tile forward with attention dropout (training)
+    OS2S_REQUIRE(ldq >= dh && ldk >= dh && ldv >= dh && ldo >= dh);
+    rc = attn_long_check(B, H, max_len);
+    if (rc != OS2S_OK) return rc;
+    return attn_fwd_dh((hipStream_t)stream, a, dh, max_len);
+  }
   if (dh != kDh) {
     OS2S_REQUIRE(ldq >= dh && ldk >= dh && ldv >= dh && ldo >= dh);
     return attn_fwd_dh((hipStream_t)stream, a, dh, max_len);
   }
   const size_t smem = (size_t)kFwdWaves * 16384;
-  if (max_len > kL) {      // multi-tile forward (inference); no attention dropout on this path
-    if (keep_prob < 1.f) return OS2S_ERR_UNSUPPORTED;
+  if (max_len > kL) {      // multi-tile forward without dropout (inference, or training with keep_prob 1)
     const int q_tiles = (max_len + kL - 1) / kL;
     OS2S_LAUNCH_LDS(attn_fwd_long_kernel, dim3(ceil_div((long long)B * H * q_tiles, kFwdWaves)),
                     dim3(kFwdWaves * 64), smem, (hipStream_t)stream, a, q_tiles);
@@ -710,6 +719,7 @@ extern "C" int os2s_attention_fwd(os2s_stream_t stream, const uint16_t* q, const
   return OS2S_OK;
 }
 
+// max_len <= 64: the one-tile backward (beyond: OS2S_ERR_UNSUPPORTED here, os2s_attention_bwd_long below)
 extern "C" int os2s_attention_bwd(os2s_stream_t stream, const uint16_t* q, const uint16_t* k,
                                   const uint16_t* v, const uint16_t* d_o, const float* lse,
                                   uint16_t* dq, uint16_t* dk, uint16_t* dv, const int32_t* cu_q,
@@ -741,4 +751,34 @@ extern "C" int os2s_attention_bwd(os2s_stream_t stream, const uint16_t* q, const
   else
     OS2S_LAUNCH(attn_bwd_kernel<false>, dim3((unsigned)((long long)B * H)), dim3(kBwdThreads), smem, (hipStream_t)stream, a);
   return OS2S_OK;
+}
+
+// max_len > 64: the two-launch backward of attention_long.hpp; `delta` is its [Nq, H] fp32 workspace
+extern "C" int os2s_attention_bwd_long(os2s_stream_t stream, const uint16_t* q, const uint16_t* k,
+                                       const uint16_t* v, const uint16_t* d_o, const float* lse, float* delta,
+                                       uint16_t* dq, uint16_t* dk, uint16_t* dv, const int32_t* cu_q,
+                                       const int32_t* cu_k, int B, int H, int dh, int max_len, long long ldq,
+                                       long long ldk, long long ldv, long long lddo, long long lddq,
+                                       long long lddk, long long lddv, int causal, float scale,
+                                       float keep_prob, unsigned long long seed) {
+  OS2S_REQUIRE(q && k && v && d_o && lse && delta && dq && dk && dv);
+  int rc = attn_check(cu_q, cu_k, B, H, dh, kL);
+  if (rc != OS2S_OK) return rc;
+  OS2S_REQUIRE(max_len > kL);      // one tile: os2s_attention_bwd
+  rc = attn_long_check(B, H, max_len);
+  if (rc != OS2S_OK) return rc;
+  OS2S_REQUIRE(ldq % 8 == 0 && ldk % 8 == 0 && ldv % 8 == 0 && lddo % 8 == 0);
+  OS2S_REQUIRE(lddq % 8 == 0 && lddk % 8 == 0 && lddv % 8 == 0);
+  OS2S_REQUIRE(ldq < kMaxLd && ldk < kMaxLd && ldv < kMaxLd && lddo < kMaxLd);
+  OS2S_REQUIRE(lddq < kMaxLd && lddk < kMaxLd && lddv < kMaxLd);
+  OS2S_REQUIRE(ldq >= dh && ldk >= dh && ldv >= dh && lddo >= dh && lddq >= dh && lddk >= dh && lddv >= dh);
+  OS2S_REQUIRE(((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)d_o | (uintptr_t)dq | (uintptr_t)dk |
+                (uintptr_t)dv) % 16 == 0);
+  OS2S_REQUIRE(keep_prob > 0.f && keep_prob <= 1.f);
+  AttnArgs a = {};
+  a.q = q; a.k = k; a.v = v; a.lse = const_cast<float*>(lse);
+  a.cu_q = cu_q; a.cu_k = cu_k; a.B = B; a.H = H; a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.causal = causal;
+  a.scale = scale; a.keep_prob = keep_prob; a.seed = seed; a.d_o = d_o; a.dq = dq; a.dk = dk; a.dv = dv;
+  a.lddo = lddo; a.lddq = lddq; a.lddk = lddk; a.lddv = lddv;
+  return attn_bwd_long((hipStream_t)stream, a, delta, dh, max_len);
 }

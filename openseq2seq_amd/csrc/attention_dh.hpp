@@ -1,5 +1,6 @@
 // The attention kernels of attention.hip for head dims 8, 16, 32 and 128 (included by attention.hip after the
-// tuned dh = 64 kernels, whose LDS images, lane maps and dropout indexing these share). Same contract: packed
+// tuned dh = 64 kernels, whose LDS images, lane maps and dropout indexing these share). The multi-tile forward
+// WITH dropout has no tuned twin and is this family's at dh = 64 too. Same contract: packed
 // token-major q / k / v with arbitrary row strides, lse [Nq, H] fp32, fp32 accumulation and softmax, the
 // dropout mask indexed ((b*H + h)*64 + q)*64 + key whatever the head dim.
 //
@@ -16,7 +17,8 @@ namespace os2s {
 
 template <int DH>
 struct HeadDim {
-  static_assert(DH == 8 || DH == 16 || DH == 32 || DH == 128, "head dims next to the tuned 64");
+  static_assert(DH == 8 || DH == 16 || DH == 32 || DH == 64 || DH == 128,
+                "head dims next to the tuned 64, and 64 itself for the kernels that have no tuned twin");
   static constexpr int kImgs = (DH + 63) / 64;      // 64-channel LDS images per [64 rows][DH] operand
   static constexpr int kSteps = (DH + 15) / 16;     // 16-deep MFMA steps of a reduction over the channels
   static constexpr int kDBlocks = (DH + 31) / 32;   // 32-row blocks of a [d][*] result
@@ -229,10 +231,20 @@ __global__ __launch_bounds__(kFwdWaves * 64) void attn_fwd_dh_kernel(AttnArgs p)
 
 // ---------------------------------------------------------------------------
 // forward for sequences longer than one tile: attn_fwd_long_kernel's structure (online softmax over the
-// key tiles, P through an LDS image); no dropout
+// key tiles, P through an LDS image). kDrop (training; at every head dim, 64 included): the running sum is of the
+// UNDROPPED probabilities, so lse is what the forward without dropout stores; the mask, element
+// ((b*H + h)*Lp + q)*Lp + key (long_drop_z), zeroes P on its way into the image and 1 / keep goes into the final
+// normalisation.
 // ---------------------------------------------------------------------------
-template <int DH>
-__global__ __launch_bounds__(kFwdWaves * 64) void attn_fwd_long_dh_kernel(AttnArgs p, int q_tiles) {
+// z of dropout_bits4_z for the four keys key4 * 4 .. + 3 of query q, both counted from the start of the sequence;
+// Lp = max_len rounded up to 64 (at Lp = 64: the index of the one-tile kernels)
+__device__ __forceinline__ unsigned long long long_drop_z(long long bh, int Lp, int q, int key4,
+                                                          unsigned long long seed) {
+  return (unsigned long long)((bh * Lp + q) * (long long)(Lp >> 2) + key4) * kDropGolden + seed;
+}
+
+template <int DH, bool kDrop>
+__global__ __launch_bounds__(kFwdWaves * 64) void attn_fwd_long_dh_kernel(AttnArgs p, int q_tiles, int Lp) {
   using HD = HeadDim<DH>;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
@@ -250,6 +262,7 @@ __global__ __launch_bounds__(kFwdWaves * 64) void attn_fwd_long_dh_kernel(AttnAr
   char* pm = smem + wid * ((1 + HD::kImgs) * 8192);   // P[q][key]  (kc image)
   char* vt = pm + 8192;                               // V[key][d]  (tr images)
   const bf16_t* qb = p.q + (long long)(q0 + qs) * p.ldq + h * DH;
+  const uint32_t thr = (uint32_t)(p.keep_prob * 65536.0f);
   float m_run[2] = {-INFINITY, -INFINITY}, l_run[2] = {0.f, 0.f};
   f32x16 o[HD::kDBlocks][2];
 #pragma unroll
@@ -319,14 +332,21 @@ __global__ __launch_bounds__(kFwdWaves * 64) void attn_fwd_long_dh_kernel(AttnAr
       for (int i = 0; i < HD::kDBlocks; ++i)
 #pragma unroll
         for (int e = 0; e < 16; ++e) o[i][j][e] *= corr;
+      // keys ks + 4*lhi + (i*32 + 8g) .. + 3 of query qs + q: draw (ks >> 2) + lhi + i*8 + 2g
+      const unsigned long long zq = kDrop ? long_drop_z(bh, Lp, qs + q, (ks >> 2) + lhi, p.seed) : 0ull;
 #pragma unroll
       for (int i = 0; i < 2; ++i)
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
           const int key0 = i * 32 + 8 * g + 4 * lhi;
+          uint32_t keep = 0xfu;
+          if (kDrop) keep = dropout_bits4_z(zq + attn_drop_step(i * 8 + 2 * g), thr);
+          float w[4];
+#pragma unroll
+          for (int e = 0; e < 4; ++e) w[e] = ((keep >> e) & 1u) ? s[i][j][4 * g + e] : 0.f;
           u32x2 pk;
-          pk[0] = pack2bf(s[i][j][4 * g], s[i][j][4 * g + 1]);
-          pk[1] = pack2bf(s[i][j][4 * g + 2], s[i][j][4 * g + 3]);
+          pk[0] = pack2bf(w[0], w[1]);
+          pk[1] = pack2bf(w[2], w[3]);
           *reinterpret_cast<u32x2*>(pm + kc_off(q, key0)) = pk;
         }
     }
@@ -351,7 +371,7 @@ __global__ __launch_bounds__(kFwdWaves * 64) void attn_fwd_long_dh_kernel(AttnAr
   for (int j = 0; j < 2; ++j) {
     const int q = j * 32 + l31;
     if (q < Lq) {
-      const float inv = l_run[j] > 0.f ? 1.f / l_run[j] : 0.f;
+      const float inv = l_run[j] > 0.f ? (kDrop ? 1.f / p.keep_prob : 1.f) / l_run[j] : 0.f;
       if (lhi == 0 && p.lse)
         p.lse[(long long)(q0 + qs + q) * p.H + h] = (m_run[j] == -INFINITY ? 0.f : m_run[j]) + __logf(l_run[j]);
 #pragma unroll
@@ -549,12 +569,15 @@ template <int DH>
 static int attn_fwd_dh_launch(hipStream_t st, const AttnArgs& a, int max_len) {
   using HD = HeadDim<DH>;
   const int B = a.B, H = a.H;
-  if (max_len > kL) {      // multi-tile forward (inference); no attention dropout on this path
-    if (a.keep_prob < 1.f) return OS2S_ERR_UNSUPPORTED;
+  if (max_len > kL) {      // multi-tile forward; DH = 64 comes here with dropout only
     const size_t smem = (size_t)kFwdWaves * (1 + HD::kImgs) * 8192;       // 64 KB, 96 KB at DH = 128
     const int q_tiles = (max_len + kL - 1) / kL;
-    OS2S_LAUNCH_LDS(attn_fwd_long_dh_kernel<DH>, dim3(ceil_div((long long)B * H * q_tiles, kFwdWaves)),
-                    dim3(kFwdWaves * 64), smem, st, a, q_tiles);
+    const dim3 grid(ceil_div((long long)B * H * q_tiles, kFwdWaves)), block(kFwdWaves * 64);
+    if (a.keep_prob < 1.f) {
+      OS2S_LAUNCH_LDS((attn_fwd_long_dh_kernel<DH, true>), grid, block, smem, st, a, q_tiles, q_tiles * kL);
+    } else {
+      OS2S_LAUNCH_LDS((attn_fwd_long_dh_kernel<DH, false>), grid, block, smem, st, a, q_tiles, q_tiles * kL);
+    }
     return OS2S_OK;
   }
   const size_t smem = (size_t)kFwdWaves * HD::kImgs * 8192;               // 32 KB, 64 KB at DH = 128
@@ -585,6 +608,7 @@ static int attn_fwd_dh(hipStream_t st, const AttnArgs& a, int dh, int max_len) {
     case 8: return attn_fwd_dh_launch<8>(st, a, max_len);
     case 16: return attn_fwd_dh_launch<16>(st, a, max_len);
     case 32: return attn_fwd_dh_launch<32>(st, a, max_len);
+    case 64: return attn_fwd_dh_launch<64>(st, a, max_len);      // max_len > 64 with dropout only (attention.hip)
     case 128: return attn_fwd_dh_launch<128>(st, a, max_len);
   }
   return OS2S_ERR_UNSUPPORTED;
