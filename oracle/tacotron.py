@@ -127,7 +127,7 @@ def decoder_infer(P, enc_out, src_len, max_steps=None, prenet_masks=None, mask_d
   round_frames_bf16: frames, stop logits and pre-net outputs are bf16 tensors on the device; rounding
   them here keeps a long free-running trajectory comparable.
   Returns dict(mel [B,steps,n_mel], stop [B,steps] logits, align [B,steps,S], lengths [B], steps)."""
-  rb = (lambda x: x.to(torch.bfloat16).float()) if round_frames_bf16 else (lambda x: x)
+  rb = (lambda x: x.to(torch.bfloat16).to(x.dtype)) if round_frames_bf16 else (lambda x: x)   # fp32 or fp64 inputs
   B, S, M = enc_out.shape
   c = P["cell"]
   L = len(c["wcat"])

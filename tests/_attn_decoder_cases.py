@@ -20,6 +20,8 @@ ad_score_vec_grads; every location case also: ad_fold_location, ad_unfold_locati
   loc_b32_fast, loc_b1_s1, loc_s31, loc_s32
       ti_lstm, ad_loc_scores_mfma, ad_loc_context | ad_loc_dalign, ad_loc_score_bwd_mfma,
       ad_cell_bwd_split, ad_dattn_split
+  loc_k2112, loc_k2624
+      the same as loc_b32_fast, with ti_lstm in its 9 x 4 / two-round 8 x 5 geometry for layer 0
   bahd_u256_l2, gnmt_u256_l2, luong_h256_l2
       ad_cell_fwd, ad_attn_fwd | ad_attn_bwd<false>, ad_cell_bwd (both layers: dgA / wAT below the top),
       ad_dattn
@@ -58,6 +60,10 @@ CASES = {
     "loc_m96": (4, 2, 21, 1, 72, 96, 128, 2, 5, 4, False, 1.0, 1.0, False),
     "loc_m80": (4, 2, 21, 1, 72, 80, 128, 2, 5, 4, False, 1.0, 1.0, False),
     "loc_m72": (4, 2, 21, 1, 72, 72, 128, 2, 5, 4, False, 1.0, 1.0, False),
+    # ad_launch_fast_cell (gx, saved gates, output dropout) at ti_geom()'s wider classes: Kc = M + H = 2112 is 33
+    # chunks (9 x 4 with three dead slots), 2624 is 41 (8 x 5, a second round holding one live chunk)
+    "loc_k2112": (17, 2, 9, 2, 64, 2048, 128, 2, 5, 4, False, 1.0, 0.9, False),
+    "loc_k2624": (17, 2, 9, 2, 64, 2560, 128, 2, 5, 4, False, 1.0, 1.0, False),
     "bahd_u256_l2": (33, 3, 13, 2, 64, 64, 256, 0, 0, 0, False, 1.0, 0.9, False),
     "gnmt_u256_l2": (5, 4, 13, 2, 64, 128, 256, 1, 0, 0, False, 0.8, 1.0, True),
     "luong_h256_l2": (4, 3, 10, 2, 256, 64, 256, 3, 0, 0, False, 1.0, 1.0, True),
@@ -75,11 +81,12 @@ SEED = {}                              # per-case seed override (default: sum of
 # attention vector scale (default 1.0): lowered until the largest alignment weight of R is below 0.99, so
 # that the softmax backward is exercised (33 samples with two-position sources saturate at unit scale)
 V_SCALE = {"loc_ragged": 0.5, "loc_ragged_t1": 0.5, "loc_b33": 0.1, "loc_b32_fast": 0.2, "loc_s31": 0.5,
-           "loc_m96": 0.5, "loc_m80": 0.2, "bahd_u256_l2": 0.07}
+           "loc_m96": 0.5, "loc_m80": 0.2, "bahd_u256_l2": 0.07, "loc_k2112": 0.1, "loc_k2624": 0.1}
 MODES = {0: "bahdanau", 1: "bahdanau_norm", 2: "location", 3: "luong"}
 STRIDED = tuple(n for n in CASES if n.startswith("loc_")) + ("bahd_u256_l2",)
 ISOLATION = ("loc_b33", "bahd_u256_l2")
-TIGHT = tuple(n for n in CASES if CASES[n][1] <= 2 and n not in UNSUPPORTED)      # T <= 2: the forward is also held to R_b
+# T <= 2 and no dropout: the forward is also held to R_b
+TIGHT = tuple(n for n in CASES if CASES[n][1] <= 2 and CASES[n][11] == 1.0 and CASES[n][12] == 1.0 and n not in UNSUPPORTED)
 ATTN_IN_SEED, OUT_SEEDS = 77, (101, 202)
 SENTINEL = -7.0                        # fill of the wider [B, T, 8 + H + M + 8] tensor of the strided runs
 GUARD = 8

@@ -6,6 +6,9 @@ tiles. tests/_attn_decoder_cases.py holds the smallest shapes that reach each cl
   loc_ragged, loc_ragged_t1     location attention with finished samples (tgt_len), T = 1 with lengths
   loc_b33                       second batch tile in mode 2, the non-fast kernels at H % 64 == 0
   loc_b32_fast                  the MFMA fast path at its B limit, S = 32 + 1
+  loc_k2112, loc_k2624          the fast cell launch (gx, saved gates, output dropout on the first) at M + H = 33
+                                and 41 k-chunks: ti_lstm_kernel's 9 x 4 geometry with dead slots and the second
+                                round of 8 x 5; the backward kernels accept both widths
   loc_b1_s1                     one sample, one position, one tap, one filter
   loc_s31, loc_s32              S padding edges of both MFMA score kernels, even filter width (K = 2)
   loc_m96 / m80 / m72           ctx_parts 4 / 2 / 1, H = 72 (no multiple of 32 or 64)
