@@ -1246,28 +1246,38 @@ def embed_wdrop_bwd(ids, dout, dtable, keep_prob, seed):
                               float(keep_prob), int(seed) & (2**64 - 1), _ptr(dtable, torch.float32))
 
 
-def layernorm_fwd(x, gamma, beta, eps=1e-6, save=True):
+def _layernorm_fwd(entry, x, gamma, beta, eps, save):
   N, D = x.shape
   y = torch.empty_like(x)
   mean = torch.empty(N, dtype=torch.float32, device=x.device) if save else None
-  rstd = torch.empty(N, dtype=torch.float32, device=x.device) if save else None
-  _lib.C.os2s_layernorm_fwd(_stream(), _ptr(x, torch.bfloat16), _ptr(gamma, torch.float32),
-                            _ptr(beta, torch.float32), float(eps), N, D, _ptr(y),
-                            _ptr(mean, None, True), _ptr(rstd, None, True))
-  return y, mean, rstd
+  rsave = torch.empty(N, dtype=torch.float32, device=x.device) if save else None
+  entry(_stream(), _ptr(x, torch.bfloat16), _ptr(gamma, torch.float32), _ptr(beta, torch.float32), float(eps),
+        N, D, _ptr(y), _ptr(mean, None, True), _ptr(rsave, None, True))
+  return y, mean, rsave
+
+
+def _layernorm_bwd(entry, num_parts, dy, x, gamma, mean, rsave, dres):
+  """(dx, partial): dx = dres + LN'(dy); partial [nparts, 2, D] = {sum dy, sum dy*xhat}."""
+  N, D = x.shape
+  dx = torch.empty_like(x)
+  partial = torch.empty((int(num_parts(N)), 2, D), dtype=torch.float32, device=x.device)
+  entry(_stream(), _ptr(dy, torch.bfloat16), _ptr(x, torch.bfloat16), _ptr(gamma, torch.float32),
+        _ptr(mean, torch.float32), _ptr(rsave, torch.float32), _ptr(dres, torch.bfloat16, True), N, D, _ptr(dx),
+        _ptr(partial))
+  return dx, partial
+
+
+def layernorm_fwd(x, gamma, beta, eps=1e-6, save=True):
+  """'layernorm_L2': returns (y, mean, rstd)."""
+  return _layernorm_fwd(_lib.C.os2s_layernorm_fwd, x, gamma, beta, eps, save)
 
 
 def layernorm_bwd(dy, x, gamma, mean, rstd, dres, dgamma, dbeta, defer_param_grads=False):
   """Returns dx (= dres + LN'(dy)); accumulates dgamma/dbeta — or, with defer_param_grads, returns
-  (dx, finish) where finish() reduces the partials into dgamma/dbeta (the caller may run it on
+  (dx, finish, partial) where finish() reduces the partials into dgamma/dbeta (the caller may run it on
   another stream: nothing in the rest of backward reads a parameter gradient)."""
-  N, D = x.shape
-  dx = torch.empty_like(x)
-  nparts = int(_lib.C.os2s_layernorm_bwd_num_parts(N))
-  partial = torch.empty((nparts, 2, D), dtype=torch.float32, device=x.device)
-  _lib.C.os2s_layernorm_bwd(_stream(), _ptr(dy, torch.bfloat16), _ptr(x, torch.bfloat16),
-                            _ptr(gamma, torch.float32), _ptr(mean, torch.float32), _ptr(rstd, torch.float32),
-                            _ptr(dres, torch.bfloat16, True), N, D, _ptr(dx), _ptr(partial))
+  dx, partial = _layernorm_bwd(_lib.C.os2s_layernorm_bwd, _lib.C.os2s_layernorm_bwd_num_parts, dy, x, gamma, mean,
+                               rstd, dres)
   def finish():
     colsum_finalize(partial, dgamma, dbeta)
   if defer_param_grads:
@@ -1278,27 +1288,14 @@ def layernorm_bwd(dy, x, gamma, mean, rstd, dres, dgamma, dbeta, defer_param_gra
 
 def layernorm_l1_fwd(x, gamma, beta, eps=1e-6, save=True):
   """'layernorm_L1': returns (y, mean, rinv) — rinv = 1 / (mean|x - mean| + eps) per row."""
-  N, D = x.shape
-  y = torch.empty_like(x)
-  mean = torch.empty(N, dtype=torch.float32, device=x.device) if save else None
-  rinv = torch.empty(N, dtype=torch.float32, device=x.device) if save else None
-  _lib.C.os2s_layernorm_l1_fwd(_stream(), _ptr(x, torch.bfloat16), _ptr(gamma, torch.float32),
-                               _ptr(beta, torch.float32), float(eps), N, D, _ptr(y),
-                               _ptr(mean, None, True), _ptr(rinv, None, True))
-  return y, mean, rinv
+  return _layernorm_fwd(_lib.C.os2s_layernorm_l1_fwd, x, gamma, beta, eps, save)
 
 
 def layernorm_l1_bwd(dy, x, gamma, mean, rinv, dres):
   """Returns (dx, partial): dx = dres + L1'(dy); partial [nparts, 2, D] = {sum dy, sum dy*xhat} for
   bn_bwd_finalize(partial, 1, ...) -> dgamma, dbeta (the caller picks the stream)."""
-  N, D = x.shape
-  dx = torch.empty_like(x)
-  nparts = int(_lib.C.os2s_layernorm_l1_bwd_num_parts(N))
-  partial = torch.empty((nparts, 2, D), dtype=torch.float32, device=x.device)
-  _lib.C.os2s_layernorm_l1_bwd(_stream(), _ptr(dy, torch.bfloat16), _ptr(x, torch.bfloat16),
-                               _ptr(gamma, torch.float32), _ptr(mean, torch.float32), _ptr(rinv, torch.float32),
-                               _ptr(dres, torch.bfloat16, True), N, D, _ptr(dx), _ptr(partial))
-  return dx, partial
+  return _layernorm_bwd(_lib.C.os2s_layernorm_l1_bwd, _lib.C.os2s_layernorm_l1_bwd_num_parts, dy, x, gamma, mean,
+                        rinv, dres)
 
 
 def token_bn_apply(x, scale, shift):

@@ -280,18 +280,6 @@ __device__ __forceinline__ void row_store(__amdgpu_buffer_rsrc_t rs, int off, u3
   __builtin_amdgcn_raw_buffer_store_b128(v, rs, off, 0, 0);
 }
 
-__device__ __forceinline__ void unpack8(const u32x4& v, float (&o)[8]) {
-  o[0] = bflo(v[0]); o[1] = bfhi(v[0]); o[2] = bflo(v[1]); o[3] = bfhi(v[1]);
-  o[4] = bflo(v[2]); o[5] = bfhi(v[2]); o[6] = bflo(v[3]); o[7] = bfhi(v[3]);
-}
-
-__device__ __forceinline__ u32x4 pack8(const float (&v)[8]) {
-  u32x4 o;
-  o[0] = pack2bf(v[0], v[1]); o[1] = pack2bf(v[2], v[3]);
-  o[2] = pack2bf(v[4], v[5]); o[3] = pack2bf(v[6], v[7]);
-  return o;
-}
-
 // The forward apply keeps the incremental (b, t) cursor: one tensor in, one out, four loads in flight
 // were enough (the BlockRows version measured the same at 64 rows and slower at 32).
 struct RowCursor {

@@ -51,11 +51,6 @@ __device__ __forceinline__ float sum8_dpp(float x) {     // sum over aligned gro
   return x;
 }
 
-__device__ __forceinline__ void unpack8(const u32x4& v, float (&f)[8]) {
-#pragma unroll
-  for (int w = 0; w < 4; ++w) { f[2 * w] = bflo(v[w]); f[2 * w + 1] = bfhi(v[w]); }
-}
-
 // One wave per (beam row, head). Lane = (key group g = lane >> 3, 16-byte channel chunk
 // c = lane & 7): a wave load covers 8 whole 128-byte key (or value) rows. Each group runs an
 // online softmax over its keys (j = 8*it + g); the 8 groups are merged at the end.

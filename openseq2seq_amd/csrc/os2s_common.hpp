@@ -132,6 +132,23 @@ __device__ __forceinline__ float bflo(uint32_t p) {
 __device__ __forceinline__ float bfhi(uint32_t p) {
   return __builtin_bit_cast(float, p & 0xffff0000u);
 }
+// eight bf16 of one 16-byte vector <-> eight floats
+__device__ __forceinline__ void unpack8(const u32x4& t, float (&f)[8]) {
+#pragma unroll
+  for (int w = 0; w < 4; ++w) { f[2 * w] = bflo(t[w]); f[2 * w + 1] = bfhi(t[w]); }
+}
+__device__ __forceinline__ u32x4 pack8(const float (&f)[8]) {
+  u32x4 o;
+#pragma unroll
+  for (int w = 0; w < 4; ++w) o[w] = pack2bf(f[2 * w], f[2 * w + 1]);
+  return o;
+}
+// eight consecutive fp32 per-column values (c0 a multiple of 8: 32-byte aligned in a torch allocation)
+__device__ __forceinline__ void load8(const float* p, float (&v)[8]) {
+  const f32x4 a = *reinterpret_cast<const f32x4*>(p), b = *reinterpret_cast<const f32x4*>(p + 4);
+#pragma unroll
+  for (int e = 0; e < 4; ++e) { v[e] = a[e]; v[4 + e] = b[e]; }
+}
 
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll

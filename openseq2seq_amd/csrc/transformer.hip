@@ -5,16 +5,12 @@
 //     parts/transformer/utils.py:28-54, encoders/transformer_encoder.py:150-161,
 //     decoders/transformer_decoder.py:197-213 — the decoder's shift-right is an index
 //     remap done by the caller: ids of the previous position, 0 for the first);
-//   * LayerNormalization (fp32 statistics, eps 1e-6; parts/transformer/common.py:41-68)
-//     forward / backward (the backward also adds the residual-branch gradient of the
-//     pre-norm wrapper, common.py:99-106);
-//   * dropout / relu-dropout backward helpers;
+//   * dropout / relu-dropout backward helpers, the epilogue of a Dense layer;
 //   * PaddedCrossEntropyLossWithSmoothing (losses/sequence_loss.py:257-309) fused with
 //     its gradient: one read of the [N, V] logits, one write of dlogits.
+// (LayerNormalization: layernorm.hip; Transformer_BatchNorm: transformer_norm.hip.)
 #include <cstdlib>
 #include "os2s_common.hpp"
-#include "ln_rows.hpp"
-#include "ln_any.hpp"
 
 namespace os2s {
 
@@ -41,9 +37,7 @@ __global__ __launch_bounds__(256) void embed_fwd_kernel(
 #pragma unroll
     for (int e = 0; e < 8; ++e) v[e] = 0.f;
     if (id != 0 || plain) {   // padding embeddings are zeroed (:79-87); plain = tf.nn.embedding_lookup
-      const u32x4 t = *reinterpret_cast<const u32x4*>(table + (long long)id * D + c0);
-      v[0] = bflo(t[0]); v[1] = bfhi(t[0]); v[2] = bflo(t[1]); v[3] = bfhi(t[1]);
-      v[4] = bflo(t[2]); v[5] = bfhi(t[2]); v[6] = bflo(t[3]); v[7] = bfhi(t[3]);
+      unpack8(*reinterpret_cast<const u32x4*>(table + (long long)id * D + c0), v);
 #pragma unroll
       for (int e = 0; e < 8; ++e) v[e] *= emb_scale;
     }
@@ -59,10 +53,7 @@ __global__ __launch_bounds__(256) void embed_fwd_kernel(
       if (keep_prob < 1.f) val = ((keep >> e) & 1u) ? val * ik : 0.f;
       v[e] = val;
     }
-    u32x4 o;
-    o[0] = pack2bf(v[0], v[1]); o[1] = pack2bf(v[2], v[3]);
-    o[2] = pack2bf(v[4], v[5]); o[3] = pack2bf(v[6], v[7]);
-    *reinterpret_cast<u32x4*>(out + n * D + c0) = o;
+    *reinterpret_cast<u32x4*>(out + n * D + c0) = pack8(v);
   }
 }
 
@@ -80,9 +71,8 @@ __global__ __launch_bounds__(256) void embed_bwd_kernel(
     int id = ids[n];
     if (id > V - 1 || id < 0) id = 0;
     if (id == 0 && !plain) continue;
-    const u32x4 t = *reinterpret_cast<const u32x4*>(dout + n * D + c0);
-    float g[8] = {bflo(t[0]), bfhi(t[0]), bflo(t[1]), bfhi(t[1]),
-                  bflo(t[2]), bfhi(t[2]), bflo(t[3]), bfhi(t[3])};
+    float g[8];
+    unpack8(*reinterpret_cast<const u32x4*>(dout + n * D + c0), g);
     uint32_t keep = 0xffu;
     if (keep_prob < 1.f) keep = dropout_bits8(seed, (unsigned long long)i, keep_prob);
 #pragma unroll
@@ -112,9 +102,8 @@ __global__ __launch_bounds__(256) void embed_bwd_det_kernel(
     if (id > V - 1 || id < 0) id = 0;
     if (id == 0 && !plain) continue;
     const long long i = n * D8 + col;
-    const u32x4 t = *reinterpret_cast<const u32x4*>(dout + n * D + c0);
-    float g[8] = {bflo(t[0]), bfhi(t[0]), bflo(t[1]), bfhi(t[1]),
-                  bflo(t[2]), bfhi(t[2]), bflo(t[3]), bfhi(t[3])};
+    float g[8];
+    unpack8(*reinterpret_cast<const u32x4*>(dout + n * D + c0), g);
     uint32_t keep = 0xffu;
     if (keep_prob < 1.f) keep = dropout_bits8(seed, (unsigned long long)i, keep_prob);
     float* const row = dtable + (long long)id * D + c0;
@@ -128,177 +117,26 @@ __global__ __launch_bounds__(256) void embed_bwd_det_kernel(
 }
 
 // ---------------------------------------------------------------------------
-// LayerNorm: one wave per row
-// ---------------------------------------------------------------------------
-template <int VPL>  // 16-byte vectors per lane: D = 64 * 8 * VPL
-__global__ __launch_bounds__(256) void layernorm_fwd_kernel(
-    const bf16_t* __restrict__ x, const float* __restrict__ gamma, const float* __restrict__ beta,
-    float eps, long long N, bf16_t* __restrict__ y, float* __restrict__ mean_out,
-    float* __restrict__ rstd_out) {
-  constexpr int D = 64 * 8 * VPL;
-  const int lane = threadIdx.x & 63;
-  const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (row >= N) return;
-  float v[VPL][8];
-  float s = 0.f;
-#pragma unroll
-  for (int u = 0; u < VPL; ++u) {
-    const u32x4 t = *reinterpret_cast<const u32x4*>(x + row * D + (u * 64 + lane) * 8);
-    v[u][0] = bflo(t[0]); v[u][1] = bfhi(t[0]); v[u][2] = bflo(t[1]); v[u][3] = bfhi(t[1]);
-    v[u][4] = bflo(t[2]); v[u][5] = bfhi(t[2]); v[u][6] = bflo(t[3]); v[u][7] = bfhi(t[3]);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) s += v[u][e];
-  }
-  const float mean = wave_sum(s) * (1.f / D);
-  float q = 0.f;
-#pragma unroll
-  for (int u = 0; u < VPL; ++u)
-#pragma unroll
-    for (int e = 0; e < 8; ++e) { const float d = v[u][e] - mean; q += d * d; }
-  const float rstd = rsqrtf(wave_sum(q) * (1.f / D) + eps);
-#pragma unroll
-  for (int u = 0; u < VPL; ++u) {
-    const int c0 = (u * 64 + lane) * 8;
-    float r[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) r[e] = (v[u][e] - mean) * rstd * gamma[c0 + e] + beta[c0 + e];
-    u32x4 o;
-    o[0] = pack2bf(r[0], r[1]); o[1] = pack2bf(r[2], r[3]);
-    o[2] = pack2bf(r[4], r[5]); o[3] = pack2bf(r[6], r[7]);
-    *reinterpret_cast<u32x4*>(y + row * D + c0) = o;
-  }
-  if (lane == 0) {
-    if (mean_out) mean_out[row] = mean;
-    if (rstd_out) rstd_out[row] = rstd;
-  }
-}
-
-// dx = dres + rstd * (g*dy - mean_D(g*dy) - xhat * mean_D(g*dy*xhat));
-// per-block partial sums of dbeta = sum dy, dgamma = sum dy*xhat -> partial[blk][2][D]
-//
-// One wave per row, kLnWaves rows of a workgroup's block at a time. A row is two dependent steps (two
-// wave reductions between its loads and its stores), so the kernel is a latency chain per wave:
-// the first version (4 waves x 8 rows, loads of a row issued after the stores of the previous one,
-// the residual gradient loaded after the reductions) ran at 1.1 TB/s. Now every load of row i + kLnWaves
-// (dy, x, dres, mean, rstd) is issued before row i is reduced — through buffer descriptors over the
-// block's rows, so the prefetch past the last row needs no branch: it is out of range, returns zeros
-// and costs no memory request — and a workgroup has 8 waves.
-constexpr int kLnWaves = 8;
-
-template <int VPL>
-__global__ __launch_bounds__(64 * kLnWaves) void layernorm_bwd_kernel(
-    const bf16_t* __restrict__ dy, const bf16_t* __restrict__ x, const float* __restrict__ gamma,
-    const float* __restrict__ mean, const float* __restrict__ rstd,
-    const bf16_t* __restrict__ dres, long long N, int rows_per_block, bf16_t* __restrict__ dx,
-    float* __restrict__ partial) {
-  constexpr int D = 64 * 8 * VPL;
-  constexpr int kOob = 0x7fffffff;
-  __shared__ float red[kLnWaves][D];
-  const int lane = threadIdx.x & 63;
-  const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  float gb[VPL][8], gg[VPL][8], gm[VPL][8];
-#pragma unroll
-  for (int u = 0; u < VPL; ++u) {
-    const f32x4 g0 = *reinterpret_cast<const f32x4*>(gamma + (u * 64 + lane) * 8);
-    const f32x4 g1 = *reinterpret_cast<const f32x4*>(gamma + (u * 64 + lane) * 8 + 4);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) { gm[u][e] = g0[e]; gm[u][4 + e] = g1[e]; }
-#pragma unroll
-    for (int e = 0; e < 8; ++e) { gb[u][e] = 0.f; gg[u][e] = 0.f; }
-  }
-  const long long r0 = (long long)blockIdx.x * rows_per_block;
-  const long long left = N - r0;
-  const int n = (int)(left < rows_per_block ? left : rows_per_block);
-  const __amdgpu_buffer_rsrc_t dyr = ln_rows_rsrc(dy, r0, n, D);
-  const __amdgpu_buffer_rsrc_t xr = ln_rows_rsrc(x, r0, n, D);
-  const __amdgpu_buffer_rsrc_t drr = ln_rows_rsrc(dres, r0, n, D);
-  const __amdgpu_buffer_rsrc_t dxr = ln_rows_rsrc(dx, r0, n, D);
-  auto fetch = [&](int i, LnRow<VPL>& R) {
-    const bool in = i < n;
-#pragma unroll
-    for (int u = 0; u < VPL; ++u) {
-      const int off = in ? i * (D * 2) + (u * 64 + lane) * 16 : kOob;
-      R.a[u] = __builtin_amdgcn_raw_buffer_load_b128(dyr, off, 0, 0);
-      R.t[u] = __builtin_amdgcn_raw_buffer_load_b128(xr, off, 0, 0);
-      R.r[u] = __builtin_amdgcn_raw_buffer_load_b128(drr, off, 0, 0);
-    }
-    const long long gr = r0 + (in ? i : 0);
-    R.mu = mean[gr];
-    R.rs = rstd[gr];
-  };
-  auto process = [&](int i, const LnRow<VPL>& cur) {
-    const float mu = cur.mu, rs = cur.rs;
-    float dyv[VPL][8], xh[VPL][8];
-    float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-    for (int u = 0; u < VPL; ++u) {
-      const u32x4 a = cur.a[u], t = cur.t[u];
-      dyv[u][0] = bflo(a[0]); dyv[u][1] = bfhi(a[0]); dyv[u][2] = bflo(a[1]); dyv[u][3] = bfhi(a[1]);
-      dyv[u][4] = bflo(a[2]); dyv[u][5] = bfhi(a[2]); dyv[u][6] = bflo(a[3]); dyv[u][7] = bfhi(a[3]);
-      xh[u][0] = bflo(t[0]); xh[u][1] = bfhi(t[0]); xh[u][2] = bflo(t[1]); xh[u][3] = bfhi(t[1]);
-      xh[u][4] = bflo(t[2]); xh[u][5] = bfhi(t[2]); xh[u][6] = bflo(t[3]); xh[u][7] = bfhi(t[3]);
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        xh[u][e] = (xh[u][e] - mu) * rs;
-        gb[u][e] += dyv[u][e];
-        gg[u][e] += dyv[u][e] * xh[u][e];
-        const float gd = gm[u][e] * dyv[u][e];
-        s1 += gd;
-        s2 += gd * xh[u][e];
-      }
-    }
-    s1 = wave_sum_dpp(s1) * (1.f / D);
-    s2 = wave_sum_dpp(s2) * (1.f / D);
-#pragma unroll
-    for (int u = 0; u < VPL; ++u) {
-      float r[8];
-#pragma unroll
-      for (int e = 0; e < 8; ++e) r[e] = rs * (gm[u][e] * dyv[u][e] - s1 - xh[u][e] * s2);
-      const u32x4 t = cur.r[u];            // zeros without a residual gradient
-      r[0] += bflo(t[0]); r[1] += bfhi(t[0]); r[2] += bflo(t[1]); r[3] += bfhi(t[1]);
-      r[4] += bflo(t[2]); r[5] += bfhi(t[2]); r[6] += bflo(t[3]); r[7] += bfhi(t[3]);
-      u32x4 o;
-      o[0] = pack2bf(r[0], r[1]); o[1] = pack2bf(r[2], r[3]);
-      o[2] = pack2bf(r[4], r[5]); o[3] = pack2bf(r[6], r[7]);
-      __builtin_amdgcn_raw_buffer_store_b128(o, dxr, i * (D * 2) + (u * 64 + lane) * 16, 0, 0);
-    }
-  };
-  // two row buffers, used alternately (a register copy `cur = next` would have to wait for the prefetch);
-  // sched_barrier: the prefetch is issued where it stands, not where hipcc would sink it to
-  LnRow<VPL> ra, rb;
-  fetch(wid, ra);
-  for (int i = wid; i < n; i += 2 * kLnWaves) {
-    fetch(i + kLnWaves, rb);
-    __builtin_amdgcn_sched_barrier(0);
-    process(i, ra);
-    if (i + kLnWaves >= n) break;
-    fetch(i + 2 * kLnWaves, ra);
-    __builtin_amdgcn_sched_barrier(0);
-    process(i + kLnWaves, rb);
-  }
-  // block reduce the parameter-gradient partials over the waves (fixed order)
-  for (int pass = 0; pass < 2; ++pass) {
-    __syncthreads();
-#pragma unroll
-    for (int u = 0; u < VPL; ++u)
-#pragma unroll
-      for (int e = 0; e < 8; ++e)
-        red[wid][(u * 64 + lane) * 8 + e] = pass == 0 ? gb[u][e] : gg[u][e];
-    __syncthreads();
-    for (int c = threadIdx.x; c < D; c += 64 * kLnWaves) {
-      float acc = 0.f;
-#pragma unroll
-      for (int w = 0; w < kLnWaves; ++w) acc += red[w][c];
-      partial[((long long)blockIdx.x * 2 + pass) * D + c] = acc;
-    }
-  }
-}
-
-// ---------------------------------------------------------------------------
 // dropout backward helpers
 // ---------------------------------------------------------------------------
 // mode 0: d = dout * keepmask/keep (mask from the hash);  mode 1: d = dout * (out > 0)/keep;
 // mode 2: d = dout * (0 < out < bf16(20/keep))/keep — out = dropout(min(relu(.), 20)), the clipped ReLU
+// the eight gradients of the i-th 16-byte vector, masked in place (ik = 1 / keep)
+__device__ __forceinline__ void dropout_bwd_mask8(float (&g)[8], const bf16_t* __restrict__ out, int mode,
+                                                  float keep_prob, float ik, unsigned long long seed, long long i) {
+  if (mode == 0) {
+    const uint32_t keep = dropout_bits8(seed, (unsigned long long)i, keep_prob);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) g[e] = ((keep >> e) & 1u) ? g[e] * ik : 0.f;
+  } else {
+    float ov[8];
+    unpack8(reinterpret_cast<const u32x4*>(out)[i], ov);
+    const float cap = mode == 2 ? bflo(pack2bf(20.f * ik, 0.f)) : __builtin_inff();
+#pragma unroll
+    for (int e = 0; e < 8; ++e) g[e] = (ov[e] > 0.f && ov[e] < cap) ? g[e] * ik : 0.f;
+  }
+}
+
 __global__ __launch_bounds__(256) void dropout_bwd_kernel(const bf16_t* __restrict__ dout,
                                                           const bf16_t* __restrict__ out, int mode,
                                                           float keep_prob, unsigned long long seed,
@@ -306,25 +144,10 @@ __global__ __launch_bounds__(256) void dropout_bwd_kernel(const bf16_t* __restri
   const float ik = 1.f / keep_prob;
   for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n8;
        i += (long long)gridDim.x * 256) {
-    const u32x4 t = reinterpret_cast<const u32x4*>(dout)[i];
-    float g[8] = {bflo(t[0]), bfhi(t[0]), bflo(t[1]), bfhi(t[1]),
-                  bflo(t[2]), bfhi(t[2]), bflo(t[3]), bfhi(t[3])};
-    if (mode == 0) {
-      const uint32_t keep = dropout_bits8(seed, (unsigned long long)i, keep_prob);
-#pragma unroll
-      for (int e = 0; e < 8; ++e) g[e] = ((keep >> e) & 1u) ? g[e] * ik : 0.f;
-    } else {
-      const u32x4 o = reinterpret_cast<const u32x4*>(out)[i];
-      const float ov[8] = {bflo(o[0]), bfhi(o[0]), bflo(o[1]), bfhi(o[1]),
-                           bflo(o[2]), bfhi(o[2]), bflo(o[3]), bfhi(o[3])};
-      const float cap = mode == 2 ? bflo(pack2bf(20.f * ik, 0.f)) : __builtin_inff();
-#pragma unroll
-      for (int e = 0; e < 8; ++e) g[e] = (ov[e] > 0.f && ov[e] < cap) ? g[e] * ik : 0.f;
-    }
-    u32x4 r;
-    r[0] = pack2bf(g[0], g[1]); r[1] = pack2bf(g[2], g[3]);
-    r[2] = pack2bf(g[4], g[5]); r[3] = pack2bf(g[6], g[7]);
-    reinterpret_cast<u32x4*>(d)[i] = r;
+    float g[8];
+    unpack8(reinterpret_cast<const u32x4*>(dout)[i], g);
+    dropout_bwd_mask8(g, out, mode, keep_prob, ik, seed, i);
+    reinterpret_cast<u32x4*>(d)[i] = pack8(g);
   }
 }
 
@@ -350,28 +173,15 @@ __global__ __launch_bounds__(256) void dropout_bwd_colsum_kernel(const bf16_t* _
   if (cg < c8n && rp < nrp) {
     for (long long r = r0 + rp; r < r1; r += nrp) {
       const long long i = r * c8n + cg;
-      const u32x4 t = reinterpret_cast<const u32x4*>(dout)[i];
-      float g[8] = {bflo(t[0]), bfhi(t[0]), bflo(t[1]), bfhi(t[1]),
-                    bflo(t[2]), bfhi(t[2]), bflo(t[3]), bfhi(t[3])};
-      if (mode == 0) {
-        const uint32_t keep = dropout_bits8(seed, (unsigned long long)i, keep_prob);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) g[e] = ((keep >> e) & 1u) ? g[e] * ik : 0.f;
-      } else {
-        const u32x4 o = reinterpret_cast<const u32x4*>(out)[i];
-        const float ov[8] = {bflo(o[0]), bfhi(o[0]), bflo(o[1]), bfhi(o[1]),
-                             bflo(o[2]), bfhi(o[2]), bflo(o[3]), bfhi(o[3])};
-        const float cap = mode == 2 ? bflo(pack2bf(20.f * ik, 0.f)) : __builtin_inff();
-#pragma unroll
-        for (int e = 0; e < 8; ++e) g[e] = (ov[e] > 0.f && ov[e] < cap) ? g[e] * ik : 0.f;
-      }
-      u32x4 rr;
-      rr[0] = pack2bf(g[0], g[1]); rr[1] = pack2bf(g[2], g[3]);
-      rr[2] = pack2bf(g[4], g[5]); rr[3] = pack2bf(g[6], g[7]);
+      float g[8];
+      unpack8(reinterpret_cast<const u32x4*>(dout)[i], g);
+      dropout_bwd_mask8(g, out, mode, keep_prob, ik, seed, i);
+      const u32x4 rr = pack8(g);
       reinterpret_cast<u32x4*>(d)[i] = rr;
       // the sums are those of the ROUNDED values the weight-gradient GEMM will read
+      unpack8(rr, g);
 #pragma unroll
-      for (int e = 0; e < 4; ++e) { acc[2 * e] += bflo(rr[e]); acc[2 * e + 1] += bfhi(rr[e]); }
+      for (int e = 0; e < 8; ++e) acc[e] += g[e];
     }
   }
 #pragma unroll
@@ -402,15 +212,13 @@ __global__ __launch_bounds__(256) void dense_epilogue_kernel(bf16_t* __restrict_
   const int c8 = C >> 3;
   for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n8;
        i += (long long)gridDim.x * 256) {
-    const u32x4 t = reinterpret_cast<const u32x4*>(y)[i];
-    float g[8] = {bflo(t[0]), bfhi(t[0]), bflo(t[1]), bfhi(t[1]),
-                  bflo(t[2]), bfhi(t[2]), bflo(t[3]), bfhi(t[3])};
+    float g[8];
+    unpack8(reinterpret_cast<const u32x4*>(y)[i], g);
     if (bias) {
-      const int c0 = (int)(i % c8) * 8;
-      const f32x4 b0 = *reinterpret_cast<const f32x4*>(bias + c0);
-      const f32x4 b1 = *reinterpret_cast<const f32x4*>(bias + c0 + 4);
+      float b[8];
+      load8(bias + (int)(i % c8) * 8, b);
 #pragma unroll
-      for (int e = 0; e < 4; ++e) { g[e] += b0[e]; g[4 + e] += b1[e]; }
+      for (int e = 0; e < 8; ++e) g[e] += b[e];
     }
     if (act == 1) {
 #pragma unroll
@@ -422,14 +230,12 @@ __global__ __launch_bounds__(256) void dense_epilogue_kernel(bf16_t* __restrict_
       for (int e = 0; e < 8; ++e) g[e] = ((keep >> e) & 1u) ? g[e] * ik : 0.f;
     }
     if (residual) {
-      const u32x4 r = reinterpret_cast<const u32x4*>(residual)[i];
-      g[0] += bflo(r[0]); g[1] += bfhi(r[0]); g[2] += bflo(r[1]); g[3] += bfhi(r[1]);
-      g[4] += bflo(r[2]); g[5] += bfhi(r[2]); g[6] += bflo(r[3]); g[7] += bfhi(r[3]);
+      float r[8];
+      unpack8(reinterpret_cast<const u32x4*>(residual)[i], r);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) g[e] += r[e];
     }
-    u32x4 o;
-    o[0] = pack2bf(g[0], g[1]); o[1] = pack2bf(g[2], g[3]);
-    o[2] = pack2bf(g[4], g[5]); o[3] = pack2bf(g[6], g[7]);
-    reinterpret_cast<u32x4*>(y)[i] = o;
+    reinterpret_cast<u32x4*>(y)[i] = pack8(g);
   }
 }
 
@@ -573,8 +379,8 @@ __global__ __launch_bounds__(256) void xent_smooth_stream_kernel(
   }
   float m = -INFINITY, s = 0.f, sx = 0.f;
   for (int i = threadIdx.x; i < V8; i += 256) {
-    const u32x4 t = *reinterpret_cast<const u32x4*>(lr + (long long)i * 8);
-    float v[8] = {bflo(t[0]), bfhi(t[0]), bflo(t[1]), bfhi(t[1]), bflo(t[2]), bfhi(t[2]), bflo(t[3]), bfhi(t[3])};
+    float v[8];
+    unpack8(*reinterpret_cast<const u32x4*>(lr + (long long)i * 8), v);
     float vm = -INFINITY;
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
@@ -704,56 +510,6 @@ extern "C" int os2s_embed_bwd(os2s_stream_t stream, const int32_t* ids, const ui
   }
   OS2S_LAUNCH(embed_bwd_kernel, dim3(ew_blocks(N * (D / 8))), dim3(256), 0, (hipStream_t)stream,
               ids, dout, V, D, N, emb_scale, keep_prob, seed, dtable, plain_lookup);
-  return OS2S_OK;
-}
-
-extern "C" int os2s_layernorm_fwd(os2s_stream_t stream, const uint16_t* x, const float* gamma,
-                                  const float* beta, float eps, long long N, int D, uint16_t* y,
-                                  float* mean, float* rstd) {
-  OS2S_REQUIRE(x && gamma && beta && y && N >= 0);
-  if (N == 0) return OS2S_OK;
-  dim3 grid(ceil_div(N, 4));
-  if (D == 1024) {
-    OS2S_LAUNCH(layernorm_fwd_kernel<2>, grid, dim3(256), 0, (hipStream_t)stream, x, gamma, beta, eps,
-                N, y, mean, rstd);
-  } else if (D == 512) {
-    OS2S_LAUNCH(layernorm_fwd_kernel<1>, grid, dim3(256), 0, (hipStream_t)stream, x, gamma, beta, eps,
-                N, y, mean, rstd);
-  } else if (ln_any_width_ok(D)) {      // every other width: the row kernel with a runtime column loop
-    OS2S_LAUNCH(layernorm_any_fwd_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, x, gamma, beta, eps,
-                N, D, y, mean, rstd);
-  } else {
-    return OS2S_ERR_UNSUPPORTED;
-  }
-  return OS2S_OK;
-}
-
-// rows per workgroup of the LayerNorm backward (8 / 16 / 32 measured equal on a Transformer-big step:
-// the step is bound by the sum of kernel times, not by this kernel's latency)
-static const int kLnRowsPerBlock = 32;
-extern "C" int os2s_layernorm_bwd_num_parts(long long N) { return ceil_div(N, kLnRowsPerBlock); }
-
-// partial: [num_parts, 2, D] (row 0: sum dy = dbeta, row 1: sum dy*xhat = dgamma); reduce it
-// with os2s_bn_bwd_finalize(partial, nparts, nq=2, q=1, C=D, ...).
-extern "C" int os2s_layernorm_bwd(os2s_stream_t stream, const uint16_t* dy, const uint16_t* x,
-                                  const float* gamma, const float* mean, const float* rstd,
-                                  const uint16_t* dres, long long N, int D, uint16_t* dx,
-                                  float* partial) {
-  OS2S_REQUIRE(dy && x && gamma && mean && rstd && dx && partial && N >= 0);
-  if (N == 0) return OS2S_OK;
-  dim3 grid(ceil_div(N, kLnRowsPerBlock));
-  if (D == 1024) {
-    OS2S_LAUNCH(layernorm_bwd_kernel<2>, grid, dim3(64 * kLnWaves), 0, (hipStream_t)stream, dy, x, gamma, mean,
-                rstd, dres, N, kLnRowsPerBlock, dx, partial);
-  } else if (D == 512) {
-    OS2S_LAUNCH(layernorm_bwd_kernel<1>, grid, dim3(64 * kLnWaves), 0, (hipStream_t)stream, dy, x, gamma, mean,
-                rstd, dres, N, kLnRowsPerBlock, dx, partial);
-  } else if (ln_any_width_ok(D)) {
-    OS2S_LAUNCH(layernorm_any_bwd_kernel<false>, grid, dim3(512), 0, (hipStream_t)stream, dy, x, gamma, mean,
-                rstd, dres, N, D, kLnRowsPerBlock, dx, partial);
-  } else {
-    return OS2S_ERR_UNSUPPORTED;
-  }
   return OS2S_OK;
 }
 

@@ -30,6 +30,7 @@ def _accumulate_checked(x, dx):
 
 class LayerNorm(object):
   """LayerNormalization 'layernorm_L2' (common.py:41-68): fp32 scale/bias, eps norm_params["epsilon"] (1e-6)."""
+  L1 = False
 
   def __init__(self, store, name, hidden, eps=1e-6):
     self.scale = store.add(name + "/layer_norm_scale", (hidden,), torch.ones(hidden), kind="vector")
@@ -38,8 +39,8 @@ class LayerNorm(object):
 
   def forward(self, x, tape):
     training = tape is not None
-    y, mean, rstd = capi.layernorm_fwd(x.data, self.scale.master, self.bias.master, self.eps,
-                                       save=training)
+    fwd = capi.layernorm_l1_fwd if self.L1 else capi.layernorm_fwd
+    y, mean, rsave = fwd(x.data, self.scale.master, self.bias.master, self.eps, save=training)
     out = Act(y)
     if not training:
       return out
@@ -49,40 +50,11 @@ class LayerNorm(object):
       dy = out.grad
       assert dy is not None
       dres, x.res_grad = x.res_grad, None
-      dx, finish, partial = capi.layernorm_bwd(dy, x.data, ln.scale.master, mean, rstd, dres, ln.scale.grad,
-                                               ln.bias.grad, defer_param_grads=True)
-      with on_side_stream(dx.device, partial):      # scale / bias gradients: off the main chain
-        finish()
-      _accumulate_checked(x, dx)
-      out.grad = None
-
-    tape.record(backward, [ln.scale, ln.bias])
-    return out
-
-
-class LayerNormL1(object):
-  """LayerNormalization 'layernorm_L1' (common.py:69-80): y = c / (mean|c| + eps) * scale + bias, c = x - mean(x);
-  the same two variables as layernorm_L2. The reference's fp16 saturate_cast has no counterpart: activations are
-  bf16 here, whose exponent range is fp32's."""
-
-  def __init__(self, store, name, hidden, eps=1e-6):
-    self.scale = store.add(name + "/layer_norm_scale", (hidden,), torch.ones(hidden), kind="vector")
-    self.bias = store.add(name + "/layer_norm_bias", (hidden,), torch.zeros(hidden), kind="vector")
-    self.eps = eps
-
-  def forward(self, x, tape):
-    training = tape is not None
-    y, mean, rinv = capi.layernorm_l1_fwd(x.data, self.scale.master, self.bias.master, self.eps, save=training)
-    out = Act(y)
-    if not training:
-      return out
-    ln = self
-
-    def backward():
-      dy = out.grad
-      assert dy is not None
-      dres, x.res_grad = x.res_grad, None
-      dx, partial = capi.layernorm_l1_bwd(dy, x.data, ln.scale.master, mean, rinv, dres)
+      if ln.L1:
+        dx, partial = capi.layernorm_l1_bwd(dy, x.data, ln.scale.master, mean, rsave, dres)
+      else:
+        dx, _, partial = capi.layernorm_bwd(dy, x.data, ln.scale.master, mean, rsave, dres, ln.scale.grad,
+                                            ln.bias.grad, defer_param_grads=True)
       with on_side_stream(dx.device, partial):      # scale / bias gradients: off the main chain
         capi.colsum_finalize(partial, ln.scale.grad, ln.bias.grad)
       _accumulate_checked(x, dx)
@@ -90,6 +62,13 @@ class LayerNormL1(object):
 
     tape.record(backward, [ln.scale, ln.bias])
     return out
+
+
+class LayerNormL1(LayerNorm):
+  """LayerNormalization 'layernorm_L1' (common.py:69-80): y = c / (mean|c| + eps) * scale + bias, c = x - mean(x);
+  the same two variables as layernorm_L2. The reference's fp16 saturate_cast has no counterpart: activations are
+  bf16 here, whose exponent range is fp32's."""
+  L1 = True
 
 
 class TokenBatchNorm(object):

@@ -1,4 +1,4 @@
-"""The norm_params kernels of the Transformer (csrc/transformer_norm.hip) against fp32 torch autograd:
+"""The norm_params kernels of the Transformer (csrc/layernorm.hip, csrc/transformer_norm.hip) against fp32 torch autograd:
 layernorm_L1 forward / backward (parts/transformer/common.py:69-80) and the token BatchNorm over packed [N, D]
 rows (common.py:11-38: training statistics, moving-statistics update, eval apply, backward with and without
 center_scale). Bounds are those of test_layernorm_fwd_bwd (tests/test_transformer_e2e_gpu.py)."""

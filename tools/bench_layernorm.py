@@ -5,8 +5,9 @@ three inputs of a row together, prefetches the next row and reduces with DPP mea
 (25.2-25.5 us at 16 / 32 rows per workgroup, 29.9 at 8) and was not kept — the 45 us the kernel
 averages inside a training step is CU sharing with the weight-gradient stream, not its own latency.
 
-  python tools/bench_layernorm.py
+  python tools/bench_layernorm.py [--kind {l2,l1}] [--width D] [--iters K]
 """
+import argparse
 import os
 import sys
 
@@ -16,15 +17,27 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 
 def main():
+  ap = argparse.ArgumentParser()
+  ap.add_argument("--kind", choices=("l2", "l1"), default="l2")
+  ap.add_argument("--width", type=int, default=1024)
+  ap.add_argument("--iters", type=int, default=50)
+  a = ap.parse_args()
   from openseq2seq_amd import capi
   dev = torch.device("cuda:0")
-  N, D, iters = 8310, 1024, 50
+  N, D, iters = 8310, a.width, a.iters
+  fwd = capi.layernorm_l1_fwd if a.kind == "l1" else capi.layernorm_fwd
   x = torch.randn(N, D, device=dev).to(torch.bfloat16)
   dy = torch.randn(N, D, device=dev).to(torch.bfloat16)
   dres = torch.randn(N, D, device=dev).to(torch.bfloat16)
   gam, bet = torch.rand(D, device=dev) + 0.5, torch.zeros(D, device=dev)
   dgam, dbet = torch.zeros(D, device=dev), torch.zeros(D, device=dev)
-  y, mean, rstd = capi.layernorm_fwd(x, gam, bet)
+  y, mean, rstd = fwd(x, gam, bet)
+
+  def bwd():
+    if a.kind == "l1":
+      capi.colsum_finalize(capi.layernorm_l1_bwd(dy, x, gam, mean, rstd, dres)[1], dgam, dbet)
+    else:
+      capi.layernorm_bwd(dy, x, gam, mean, rstd, dres, dgam, dbet)
 
   def timed(fn):
     for _ in range(5):
@@ -38,8 +51,8 @@ def main():
     torch.cuda.synchronize()
     return e0.elapsed_time(e1) * 1e3 / iters
 
-  tf = timed(lambda: capi.layernorm_fwd(x, gam, bet))
-  tb = timed(lambda: capi.layernorm_bwd(dy, x, gam, mean, rstd, dres, dgam, dbet))
+  tf = timed(lambda: fwd(x, gam, bet))
+  tb = timed(bwd)
   print("fwd %.1f us (HBM time %.1f us)  bwd + finalize %.1f us (HBM time %.1f us)" %
         (tf, 2 * N * D * 2 / 8e6, tb, 4 * N * D * 2 / 8e6))
 

@@ -27,8 +27,11 @@ NORMS = {
 
 # kernel-name fragments of each family (the parameter-gradient reductions included)
 FAMILIES = {
-    "layernorm_L2": ("layernorm_fwd_kernel", "layernorm_bwd_kernel"),
-    "layernorm_L1": ("layernorm_l1_fwd_kernel", "layernorm_l1_bwd_kernel"),
+    # csrc/layernorm.hip: template <bool kL1, ...>, the kind is the first argument of the demangled name
+    "layernorm_L2": ("layernorm_fwd_kernel<false", "layernorm_bwd_kernel<false", "layernorm_any_fwd_kernel<false",
+                     "layernorm_any_bwd_kernel<false"),
+    "layernorm_L1": ("layernorm_fwd_kernel<true", "layernorm_bwd_kernel<true", "layernorm_any_fwd_kernel<true",
+                     "layernorm_any_bwd_kernel<true"),
     "batch_norm": ("bn_stats_kernel", "bn_finalize_kernel", "token_bn_apply_kernel", "token_bn_bwd_reduce_kernel",
                    "token_bn_bwd_apply_kernel"),
     "bn_bwd_finalize (all families' parameter gradients)": ("bn_bwd_finalize_kernel",),
