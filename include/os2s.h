@@ -807,8 +807,9 @@ int os2s_add_bf16(os2s_stream_t stream, const uint16_t* a, const uint16_t* b, lo
  * channels [h*dh, (h+1)*dh) of each row (split_heads/combine_heads are indexing only).
  * bias = padding mask (absent keys in the packed layout) and, if causal, the decoder's
  * lower-triangular band (utils.py:57-79). lse [Nq, H] is saved for the backward, which
- * recomputes the probabilities. dh in {8, 16, 32, 64, 128} (64 is the tuned kernel family, the other four share
- * one family templated on the head dim; anything else: OS2S_ERR_UNSUPPORTED). The dropout mask is element
+ * recomputes the probabilities. dh in {8, 16, 32, 64, 128} (one kernel family templated on the head dim, tuned at
+ * 64; anything else: OS2S_ERR_UNSUPPORTED). Every row stride is a multiple of 8, at least dh and below 2^22, every
+ * tensor pointer 16-byte aligned and 0 < keep_prob <= 1 (OS2S_ERR_INVALID_ARG otherwise). The dropout mask is element
  * ((b*H + h)*Lp + q)*Lp + key of the generator behind os2s_dropout_mask whatever dh, with q and key counted from
  * the start of the sequence, Lp = max_len rounded up to a multiple of 64, in 64-bit arithmetic: it depends on the
  * launch's max_len, so forward and backward must be given the same one. Two kernel families, chosen by max_len:

@@ -1,8 +1,9 @@
-// The attention BACKWARD for sequences longer than one 64-token tile (included by attention.hip after
-// attention_dh.hpp), one family templated on the head dim for all of 8, 16, 32, 64 and 128. Same contract as the rest
-// of attention.hip: packed token-major q / k / v with arbitrary row strides, lse [Nq, H] fp32 of the undropped
-// scaled logits, fp32 softmax, bf16 I/O. Calls with max_len <= 64 never come here. The forward it belongs to is
-// attn_fwd_long_dh_kernel<DH, kDrop> (attn_fwd_long_kernel at head dim 64 without dropout).
+// The attention BACKWARD for sequences longer than one 64-token tile (included by attention.hip after its kernels,
+// on top of its helpers: HeadDim, head_rsrc, load8, load_piece, frag_tr, long_drop_z, store_dT_quad; launched by
+// os2s_attention_bwd_long there), templated on the head dim like them. Same contract as the rest of attention.hip:
+// packed token-major q / k / v with arbitrary row strides, lse [Nq, H] fp32 of the undropped scaled logits, fp32
+// softmax, bf16 I/O. Calls with max_len <= 64 never come here. The forward it belongs to is
+// attn_fwd_long_kernel<DH, kDrop>.
 //
 // Dropout mask (long_drop_z, shared with that forward): element ((b*H + h)*Lp + q)*Lp + key of the generator behind
 // os2s_dropout_mask, q and key counted from the start of the sequence, Lp = max_len rounded up to 64, 64-bit
@@ -71,7 +72,7 @@ __device__ __forceinline__ void long_frags(__amdgpu_buffer_rsrc_t rs, int ld, in
                                            bf16x8 (&f)[HeadDim<DH>::kSteps]) {
   const int voff = (lane & 31) * ld * 2 + (lane >> 5) * 16;
 #pragma unroll
-  for (int kk = 0; kk < HeadDim<DH>::kSteps; ++kk) f[kk] = load8_dh<DH>(rs, voff + kk * 32, soff, lane >> 5);
+  for (int kk = 0; kk < HeadDim<DH>::kSteps; ++kk) f[kk] = load8<DH>(rs, voff + kk * 32, soff, lane >> 5);
 }
 
 // a [64 rows][DH] tile into kImgs transpose-read images, by the whole workgroup (zeros past `rs`'s rows / the head)
@@ -82,18 +83,19 @@ __device__ __forceinline__ void long_stage(char* img, __amdgpu_buffer_rsrc_t rs,
   for (int hh = 0; hh < HeadDim<DH>::kImgs; ++hh) {
     const int ch = hh * 64 + (tid & 7) * 8;
 #pragma unroll
-    for (int it = 0; it < 2; ++it) {
-      u32x4 t = {0u, 0u, 0u, 0u};
-      if (ch < DH) t = __builtin_amdgcn_raw_buffer_load_b128(rs, srow * ld * 2 + ch * 2, it * 32 * ld * 2, 0);
-      *reinterpret_cast<u32x4*>(img + hh * 8192 + tr_off(it * 32 + srow, (tid & 7) * 8)) = t;
-    }
+    for (int it = 0; it < 2; ++it)
+      *reinterpret_cast<u32x4*>(img + hh * 8192 + tr_off(it * 32 + srow, (tid & 7) * 8)) =
+          load_piece<DH>(rs, srow * ld * 2 + ch * 2, it * 32 * ld * 2, ch);
   }
 }
 
 // Block (key block wi, query block wj) of the tile (keys ks .., queries qs ..): S^T = K Q^T and dPd^T = V dO^T on
 // the MFMA, then per element P (pv), Pd = P o m / keep (pd) and dPd o m / keep (dpm); the callers form delta =
 // sum_key pv * dpm and dS = pv * (dpm - delta). Register 4g + e of a lane is key wi*32 + 8g + e + 4*lhi of query
-// wj*32 + l31. lse2 = lse * log2(e) of the lane's query. Lq, Lk: live rows of the tile.
+// wj*32 + l31. lse2 = lse * log2(e) of the lane's query. Lq, Lk: live rows of the tile. (attn_bwd_kernel spells
+// this block out for one tile, writing PM as it goes: called with qs = ks = 0, Lp = 64 this function cost its
+// dropout instance at head dim 64 32 more registers and a wave per SIMD, and its delta sum lost its FMAs, which
+// is another rounding: profiles/attention_unified.md.)
 template <int DH, bool kDrop>
 __device__ __forceinline__ void long_bwd_block(const AttnArgs& p, const LongSeq& sq, int Lp,
                                                const bf16x8 (&fk)[HeadDim<DH>::kSteps],
@@ -170,8 +172,8 @@ __global__ __launch_bounds__(kBwdThreads) void attn_bwd_long_dq_kernel(AttnArgs 
   const int ldq = (int)p.ldq, ldk = (int)p.ldk, ldv = (int)p.ldv, lddo = (int)p.lddo;
   const long long qrow = (long long)(sq.q0 + qs);
   const int hc = sq.h * DH;
-  const __amdgpu_buffer_rsrc_t qrs = head_rsrc_dh<DH>(p.q + qrow * p.ldq + hc, p.ldq, Lq);
-  const __amdgpu_buffer_rsrc_t dors = head_rsrc_dh<DH>(p.d_o + qrow * p.lddo + hc, p.lddo, Lq);
+  const __amdgpu_buffer_rsrc_t qrs = head_rsrc<DH>(p.q + qrow * p.ldq + hc, p.ldq, Lq);
+  const __amdgpu_buffer_rsrc_t dors = head_rsrc<DH>(p.d_o + qrow * p.lddo + hc, p.lddo, Lq);
   bf16x8 fq[LD::kSteps], fdo[LD::kSteps];
   long_frags<DH>(qrs, ldq, wj * 32 * ldq * 2, lane, fq);
   long_frags<DH>(dors, lddo, wj * 32 * lddo * 2, lane, fdo);
@@ -185,8 +187,8 @@ __global__ __launch_bounds__(kBwdThreads) void attn_bwd_long_dq_kernel(AttnArgs 
     const int ks = kt * kL;
     const int Lk = min(sq.Lk_tot - ks, kL);
     const long long krow = (long long)(sq.k0 + ks);
-    const __amdgpu_buffer_rsrc_t krs = head_rsrc_dh<DH>(p.k + krow * p.ldk + hc, p.ldk, Lk);
-    const __amdgpu_buffer_rsrc_t vrs = head_rsrc_dh<DH>(p.v + krow * p.ldv + hc, p.ldv, Lk);
+    const __amdgpu_buffer_rsrc_t krs = head_rsrc<DH>(p.k + krow * p.ldk + hc, p.ldk, Lk);
+    const __amdgpu_buffer_rsrc_t vrs = head_rsrc<DH>(p.v + krow * p.ldv + hc, p.ldv, Lk);
     bf16x8 fk[LD::kSteps], fv[LD::kSteps];
     long_frags<DH>(krs, ldk, wi * 32 * ldk * 2, lane, fk);
     long_frags<DH>(vrs, ldv, wi * 32 * ldv * 2, lane, fv);
@@ -210,8 +212,8 @@ __global__ __launch_bounds__(kBwdThreads) void attn_bwd_long_dq_kernel(AttnArgs 
     const int ks = kt * kL;
     const int Lk = min(sq.Lk_tot - ks, kL);
     const long long krow = (long long)(sq.k0 + ks);
-    const __amdgpu_buffer_rsrc_t krs = head_rsrc_dh<DH>(p.k + krow * p.ldk + hc, p.ldk, Lk);
-    const __amdgpu_buffer_rsrc_t vrs = head_rsrc_dh<DH>(p.v + krow * p.ldv + hc, p.ldv, Lk);
+    const __amdgpu_buffer_rsrc_t krs = head_rsrc<DH>(p.k + krow * p.ldk + hc, p.ldk, Lk);
+    const __amdgpu_buffer_rsrc_t vrs = head_rsrc<DH>(p.v + krow * p.ldv + hc, p.ldv, Lk);
     bf16x8 fk[LD::kSteps], fv[LD::kSteps];
     long_frags<DH>(krs, ldk, wi * 32 * ldk * 2, lane, fk);
     long_frags<DH>(vrs, ldv, wi * 32 * ldv * 2, lane, fv);
@@ -242,7 +244,7 @@ __global__ __launch_bounds__(kBwdThreads) void attn_bwd_long_dq_kernel(AttnArgs 
     for (int n = 0; n < long_own<DH>(); ++n) {
       const int db = wi + 2 * n;
       if (db < LD::kDBlocks)
-        store_dT_quad_dh<DH>(dq[n], db, wj, p.dq + qrow * p.lddq + hc, p.lddq, Lq, p.scale, lane);
+        store_dT_quad<DH>(dq[n], db, wj, p.dq + qrow * p.lddq + hc, p.lddq, Lq, p.scale, lane);
     }
   }
 }
@@ -270,8 +272,8 @@ __global__ __launch_bounds__(kBwdThreads) void attn_bwd_long_dkv_kernel(AttnArgs
   const int ldq = (int)p.ldq, ldk = (int)p.ldk, ldv = (int)p.ldv, lddo = (int)p.lddo;
   const long long krow = (long long)(sq.k0 + ks);
   const int hc = sq.h * DH;
-  const __amdgpu_buffer_rsrc_t krs = head_rsrc_dh<DH>(p.k + krow * p.ldk + hc, p.ldk, Lk);
-  const __amdgpu_buffer_rsrc_t vrs = head_rsrc_dh<DH>(p.v + krow * p.ldv + hc, p.ldv, Lk);
+  const __amdgpu_buffer_rsrc_t krs = head_rsrc<DH>(p.k + krow * p.ldk + hc, p.ldk, Lk);
+  const __amdgpu_buffer_rsrc_t vrs = head_rsrc<DH>(p.v + krow * p.ldv + hc, p.ldv, Lk);
   bf16x8 fk[LD::kSteps], fv[LD::kSteps];
   long_frags<DH>(krs, ldk, wi * 32 * ldk * 2, lane, fk);
   long_frags<DH>(vrs, ldv, wi * 32 * ldv * 2, lane, fv);
@@ -286,8 +288,8 @@ __global__ __launch_bounds__(kBwdThreads) void attn_bwd_long_dkv_kernel(AttnArgs
     const int qs = qt * kL;
     const int Lq = min(sq.Lq_tot - qs, kL);
     const long long qrow = (long long)(sq.q0 + qs);
-    const __amdgpu_buffer_rsrc_t qrs = head_rsrc_dh<DH>(p.q + qrow * p.ldq + hc, p.ldq, Lq);
-    const __amdgpu_buffer_rsrc_t dors = head_rsrc_dh<DH>(p.d_o + qrow * p.lddo + hc, p.lddo, Lq);
+    const __amdgpu_buffer_rsrc_t qrs = head_rsrc<DH>(p.q + qrow * p.ldq + hc, p.ldq, Lq);
+    const __amdgpu_buffer_rsrc_t dors = head_rsrc<DH>(p.d_o + qrow * p.lddo + hc, p.lddo, Lq);
     bf16x8 fq[LD::kSteps], fdo[LD::kSteps];
     long_frags<DH>(qrs, ldq, wj * 32 * ldq * 2, lane, fq);
     long_frags<DH>(dors, lddo, wj * 32 * lddo * 2, lane, fdo);
@@ -328,8 +330,8 @@ __global__ __launch_bounds__(kBwdThreads) void attn_bwd_long_dkv_kernel(AttnArgs
     for (int n = 0; n < long_own<DH>(); ++n) {
       const int db = wi + 2 * n;
       if (db >= LD::kDBlocks) continue;
-      store_dT_quad_dh<DH>(dv[n], db, wj, p.dv + krow * p.lddv + hc, p.lddv, Lk, 1.f, lane);
-      store_dT_quad_dh<DH>(dk[n], db, wj, p.dk + krow * p.lddk + hc, p.lddk, Lk, p.scale, lane);
+      store_dT_quad<DH>(dv[n], db, wj, p.dv + krow * p.lddv + hc, p.lddv, Lk, 1.f, lane);
+      store_dT_quad<DH>(dk[n], db, wj, p.dk + krow * p.lddk + hc, p.lddk, Lk, p.scale, lane);
     }
   }
 }
@@ -342,35 +344,6 @@ static int attn_long_check(int B, int H, int max_len) {
   const long long tiles = (max_len + kL - 1) / kL;
   if ((long long)B * H * tiles >= (1ll << 31)) return OS2S_ERR_INVALID_ARG;
   return OS2S_OK;
-}
-
-template <int DH>
-static int attn_bwd_long_launch(hipStream_t st, const AttnArgs& a, float* delta, int max_len) {
-  const int tiles = (max_len + kL - 1) / kL;
-  const dim3 grid((unsigned)((long long)a.B * a.H * tiles)), block(kBwdThreads);
-  const size_t lds_dq = (size_t)attn_bwd_long_dq_lds<DH>(), lds_dkv = (size_t)attn_bwd_long_dkv_lds<DH>();
-  if (a.keep_prob < 1.f) {
-    OS2S_LAUNCH_LDS((attn_bwd_long_dq_kernel<DH, true>), grid, block, lds_dq, st, a, delta, tiles, tiles * kL);
-    OS2S_LAUNCH_LDS((attn_bwd_long_dkv_kernel<DH, true>), grid, block, lds_dkv, st, a, (const float*)delta, tiles,
-                    tiles * kL);
-  } else {
-    OS2S_LAUNCH_LDS((attn_bwd_long_dq_kernel<DH, false>), grid, block, lds_dq, st, a, delta, tiles, tiles * kL);
-    OS2S_LAUNCH_LDS((attn_bwd_long_dkv_kernel<DH, false>), grid, block, lds_dkv, st, a, (const float*)delta, tiles,
-                    tiles * kL);
-  }
-  return OS2S_OK;
-}
-
-// every head dim, 64 included; the caller has checked dh with attn_dh_ok
-static int attn_bwd_long(hipStream_t st, const AttnArgs& a, float* delta, int dh, int max_len) {
-  switch (dh) {
-    case 8: return attn_bwd_long_launch<8>(st, a, delta, max_len);
-    case 16: return attn_bwd_long_launch<16>(st, a, delta, max_len);
-    case 32: return attn_bwd_long_launch<32>(st, a, delta, max_len);
-    case 64: return attn_bwd_long_launch<64>(st, a, delta, max_len);
-    case 128: return attn_bwd_long_launch<128>(st, a, delta, max_len);
-  }
-  return OS2S_ERR_UNSUPPORTED;
 }
 
 }  // namespace os2s

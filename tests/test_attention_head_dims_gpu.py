@@ -1,4 +1,5 @@
-"""The attention kernels at head dims 8, 16, 32 and 128 (csrc/attention_dh.hpp) against a float64 oracle:
+"""The attention kernels (csrc/attention.hip: attn_fwd_kernel / attn_bwd_kernel / attn_fwd_long_kernel<DH, kDrop>) at
+every head dim they are instantiated for, 8, 16, 32, 64 and 128, against a float64 oracle:
 the cases of test_attention_fwd_bwd / test_attention_fwd_long (tests/test_transformer_kernels_gpu.py) with that
 file's bounds — o 2e-2 of the tensor rms, gradients 3e-2, lse 2e-3; long forward 2e-2 / 2e-3. bf16 I/O rounding
 dominates at every head dim, so the bounds do not depend on it.
@@ -12,7 +13,7 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
-HEAD_DIMS = [8, 16, 32, 128]
+HEAD_DIMS = [8, 16, 32, 64, 128]
 B, H = 5, 3
 
 
@@ -143,3 +144,32 @@ def test_attention_unsupported_head_dim_raises(cuda, dh):
   with pytest.raises(_lib.Os2sError, match="unsupported configuration"):
     _lib.C.os2s_attention_bwd(None, p(q), p(q), p(q), p(q), p(lse), p(o), p(o), p(o), p(cu), p(cu), 1, H, dh, 64,
                               D, D, D, D, D, D, D, 0, 1.0, 1.0, 0)
+
+
+@pytest.mark.parametrize("dh", [32, 64])
+def test_attention_invalid_stride_and_keep_prob_raise(cuda, dh):
+  """The three entry points apply one set of checks whatever the head dim: a row stride shorter than a head
+  (os2s_attention_fwd with ldq = 8) and keep_prob = 0 into the backwards, which divide by it, answer
+  OS2S_ERR_INVALID_ARG before any launch: the output buffers keep their sentinel."""
+  from ctypes import c_void_p
+  from openseq2seq_amd import _lib
+  D, L = H * dh, 9
+  g = torch.Generator().manual_seed(3 + dh)
+  q, k, v, do = (torch.randn(L, D, generator=g).to(torch.bfloat16).to(cuda) for _ in range(4))
+  cu = _cu([L], cuda)
+  o, dq, dk, dv = (torch.full((L, D), 7.0, dtype=torch.bfloat16, device=cuda) for _ in range(4))
+  lse = torch.full((L, H), 7.0, dtype=torch.float32, device=cuda)
+  delta = torch.full((L, H), 7.0, dtype=torch.float32, device=cuda)
+  p = lambda t: c_void_p(t.data_ptr())
+  with pytest.raises(_lib.Os2sError, match="invalid argument"):
+    _lib.C.os2s_attention_fwd(None, p(q), p(k), p(v), p(o), p(lse), p(cu), p(cu), 1, H, dh, 64, 8, D, D, D, 0,
+                              dh ** -0.5, 1.0, 0)
+  with pytest.raises(_lib.Os2sError, match="invalid argument"):
+    _lib.C.os2s_attention_bwd(None, p(q), p(k), p(v), p(do), p(lse), p(dq), p(dk), p(dv), p(cu), p(cu), 1, H, dh, 64,
+                              D, D, D, D, D, D, D, 0, dh ** -0.5, 0.0, 0)
+  with pytest.raises(_lib.Os2sError, match="invalid argument"):
+    _lib.C.os2s_attention_bwd_long(None, p(q), p(k), p(v), p(do), p(lse), p(delta), p(dq), p(dk), p(dv), p(cu),
+                                   p(cu), 1, H, dh, 128, D, D, D, D, D, D, D, 0, dh ** -0.5, 0.0, 0)
+  torch.cuda.synchronize()
+  for t in (o, lse, delta, dq, dk, dv):
+    assert bool((t == 7.0).all())

@@ -1,5 +1,6 @@
-"""Attention TRAINING on sequences longer than one 64-token tile (csrc/attention_long.hpp: the multi-tile forward
-with dropout and the two-launch multi-tile backward) against a float64 oracle, at every head dim.
+"""Attention TRAINING on sequences longer than one 64-token tile (attn_fwd_long_kernel<DH, true> of csrc/attention.hip,
+the multi-tile forward with dropout, and attn_bwd_long_dq_kernel / attn_bwd_long_dkv_kernel of csrc/attention_long.hpp,
+the two-launch multi-tile backward) against a float64 oracle, at every head dim.
 
 Laid out like tests/test_attention_head_dims_gpu.py, with that file's bounds — o 2e-2 of the tensor rms, gradients
 3e-2, lse 2e-3: H = 3 heads, B = 5 sentences, q / k / v column slices of one [N, 3*H*dh] tensor, gradients into

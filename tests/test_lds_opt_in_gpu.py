@@ -58,9 +58,9 @@ def _wgrad_case():
   return run, check
 
 
-# ---- capi.attention_fwd / attention_bwd at dh = 128, lengths <= 64: attn_fwd_dh_kernel<128, false> with
+# ---- capi.attention_fwd / attention_bwd at dh = 128, lengths <= 64: attn_fwd_kernel<128, false> with
 # kFwdWaves * kImgs * 8192 = 4 * 2 * 8192 = 65 536 bytes (exactly the default limit: opted in), and
-# attn_bwd_dh_kernel<128, false> with attn_bwd_dh_lds<128>() = 81 920 bytes.
+# attn_bwd_kernel<128, false> with attn_bwd_lds<128>() = 81 920 bytes.
 def _attention_case():
   D = HEADS * DH
   scale = DH ** -0.5
@@ -131,7 +131,7 @@ def test_second_device_is_opted_in_too():
 
 
 def test_two_instances_of_one_site_interleaved(cuda):
-  """attention_fwd at dh = 128: attn_fwd_dh_kernel<128, false> (keep_prob = 1) and <128, true> (keep_prob < 1),
+  """attention_fwd at dh = 128: attn_fwd_kernel<128, false> (keep_prob = 1) and <128, true> (keep_prob < 1),
   65 536 bytes each, alternately, three times each. Before that, the cases of the second-device test run on this
   device, twice each: their inputs, oracles and bounds do not wait for a machine with two devices, and a second
   call of an opted-in site returns the bits of the first."""
