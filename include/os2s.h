@@ -847,6 +847,41 @@ int os2s_attention_bwd_long(os2s_stream_t stream, const uint16_t* q, const uint1
                             long long ldk, long long ldv, long long lddo, long long lddq,
                             long long lddk, long long lddv, int causal, float scale,
                             float keep_prob, unsigned long long seed);
+/* Attention.call "loung" mode (parts/transformer/attention_layer.py:104-220) on DENSE padded tensors with a head
+ * dim up to 512: the decoder -> encoder attention of Centaur (one head as wide as the hidden state). q [B, Tq, H*D],
+ * k / v [B, S, H*D] bf16 with row strides ldq / ldk / ldv (batch b starts at row b*Tq resp. b*S), head h owns
+ * channels [h*D, (h+1)*D). key_bias [B, S] fp32 is the reference's padding bias (0 for a real key, -1e9 where the
+ * source id is 0; get_padding_bias). logits = scale * q k^T in fp32 + bias, fp32 softmax over the S keys.
+ * positions [B, H, Tq] int32 (NULL: none, the training case) with window / back_step forces the monotonic window of
+ * :166-187: query t gets a further bias of 0 for keys in [w, w + window), w = max(positions[b,h,t] - back_step, 0),
+ * and -1e9 elsewhere; it is added to key_bias and the sum clipped below at -1e9, an additive fp32 bias and never
+ * -inf, so a row whose window lies wholly past the real keys is the reference's near-uniform row, not NaN. The
+ * reference applies the window only when its logits are fp32 (:154); ours always are, so the window applies
+ * whenever positions is given.
+ * Outputs: o [B, Tq, H*D] bf16 (row stride ldo); p [B, H, Tq, S] fp32 = the probabilities BEFORE dropout (the
+ * model's alignments, and what the backward reads); argmax [B, H, Tq] int32 (NULL: not wanted) = the first index of
+ * the row maximum of p (tf.argmax). Dropout acts on p after the softmax; the mask is element
+ * ((b*H + h)*Tq + t)*S + key of the generator behind os2s_dropout_mask.
+ * D in {32, 64, 128, 256, 512} and S <= 512, S % 8 == 0 (anything else: OS2S_ERR_UNSUPPORTED); Tq >= 1. Every row
+ * stride is a multiple of 8, at least H*D and below 2^22, every pointer 16-byte aligned, 0 < keep_prob <= 1
+ * (OS2S_ERR_INVALID_ARG otherwise). */
+int os2s_attention_wide_fwd(os2s_stream_t stream, const uint16_t* q, const uint16_t* k,
+                            const uint16_t* v, const float* key_bias, const int32_t* positions,
+                            uint16_t* o, float* p, int32_t* argmax, int B, int H, int D, int Tq,
+                            int S, long long ldq, long long ldk, long long ldv, long long ldo,
+                            int window, int back_step, float scale, float keep_prob,
+                            unsigned long long seed);
+/* Its backward: dq [B, Tq, H*D], dk / dv [B, S, H*D] bf16 from d_o, the forward's p and q / k / v (keep_prob and
+ * seed as given to the forward; the bias and the window take no gradient). ds is a bf16 workspace [B, H, Tq, S]:
+ * the first launch, one workgroup per 64-query tile, owns dq and leaves dS = p o (dPd - delta) there; the second,
+ * one workgroup per (64-key tile, 128-channel chunk), owns dk and dv. Plain stores only: no atomics, bitwise
+ * reproducible from run to run. Limits as os2s_attention_wide_fwd. */
+int os2s_attention_wide_bwd(os2s_stream_t stream, const uint16_t* q, const uint16_t* k,
+                            const uint16_t* v, const uint16_t* d_o, const float* p, uint16_t* ds,
+                            uint16_t* dq, uint16_t* dk, uint16_t* dv, int B, int H, int D, int Tq,
+                            int S, long long ldq, long long ldk, long long ldv, long long lddo,
+                            long long lddq, long long lddk, long long lddv, float scale,
+                            float keep_prob, unsigned long long seed);
 /* PaddedCrossEntropyLossWithSmoothing (losses/sequence_loss.py:257-309) over the N
  * non-pad target rows: row_loss[n] = xent(soft targets) - normalizing constant;
  * loss_mean = grad_scale * sum(row_loss); dlogits = grad_scale * (*grad_scale_dev) *

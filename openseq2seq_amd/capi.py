@@ -1409,6 +1409,59 @@ def attention_bwd(q, k, v, d_o, lse, dq, dk, dv, cu_q, cu_k, H, max_len, causal,
                             float(scale), float(keep_prob), int(seed) & (2**64 - 1))
 
 
+ATTENTION_WIDE_HEAD_DIMS = (32, 64, 128, 256, 512)
+ATTENTION_WIDE_MAX_KEYS = 512
+
+
+def _rows3(t, name):
+  """A bf16 [B, T, >=C] view whose batches follow each other (stride(0) == T * stride(1)) -> its row stride."""
+  if t.dtype is not torch.bfloat16 or not t.is_cuda or t.dim() != 3:
+    raise TypeError("%s: a bf16 device tensor [B, T, C] is required" % name)
+  if t.stride(2) != 1 or (t.shape[0] > 1 and t.stride(0) != t.shape[1] * t.stride(1)):
+    raise ValueError("%s: rows must be contiguous and the batches dense" % name)
+  return t.stride(1)
+
+
+def attention_wide_fwd(q, k, v, key_bias, H, scale, keep_prob=1.0, seed=0, positions=None, window=0, back_step=0,
+                       want_argmax=False):
+  """Dense cross-attention with a head dim up to 512 (os2s_attention_wide_fwd). q [B, Tq, H*D], k / v [B, S, H*D]
+  bf16 views (channel stride 1, dense batches), key_bias [B, S] fp32, positions [B, H, Tq] int32 or None.
+  Returns (o [B, Tq, H*D] bf16, p [B, H, Tq, S] fp32 before dropout, argmax [B, H, Tq] int32 or None)."""
+  B, Tq, C = q.shape
+  S = k.shape[1]
+  D = C // H
+  dev = q.device
+  o = torch.empty((B, Tq, C), dtype=torch.bfloat16, device=dev)
+  p = torch.empty((B, H, Tq, S), dtype=torch.float32, device=dev)
+  am = torch.empty((B, H, Tq), dtype=torch.int32, device=dev) if want_argmax else None
+  _lib.C.os2s_attention_wide_fwd(_stream(), c_void_p(q.data_ptr()), c_void_p(k.data_ptr()), c_void_p(v.data_ptr()),
+                                 _ptr(key_bias, torch.float32), _ptr(positions, torch.int32, True), _ptr(o),
+                                 _ptr(p), _ptr(am, None, True), B, H, D, Tq, S, _rows3(q, "q"), _rows3(k, "k"),
+                                 _rows3(v, "v"), C, int(window), int(back_step), float(scale), float(keep_prob),
+                                 int(seed) & (2**64 - 1))
+  return o, p, am
+
+
+def attention_wide_bwd(q, k, v, d_o, p, H, scale, keep_prob=1.0, seed=0, dq=None, dk=None, dv=None):
+  """Gradients of attention_wide_fwd (keep_prob and seed as given to it): (dq, dk, dv) bf16, written into the
+  given [B, T, >=H*D] views or into fresh tensors. Two launches, no atomics."""
+  B, Tq, C = q.shape
+  S = k.shape[1]
+  D = C // H
+  dev = q.device
+  dq = torch.empty((B, Tq, C), dtype=torch.bfloat16, device=dev) if dq is None else dq
+  dk = torch.empty((B, S, C), dtype=torch.bfloat16, device=dev) if dk is None else dk
+  dv = torch.empty((B, S, C), dtype=torch.bfloat16, device=dev) if dv is None else dv
+  ds = torch.empty((B, H, Tq, S), dtype=torch.bfloat16, device=dev)
+  _lib.C.os2s_attention_wide_bwd(_stream(), c_void_p(q.data_ptr()), c_void_p(k.data_ptr()), c_void_p(v.data_ptr()),
+                                 c_void_p(d_o.data_ptr()), _ptr(p, torch.float32), _ptr(ds),
+                                 c_void_p(dq.data_ptr()), c_void_p(dk.data_ptr()), c_void_p(dv.data_ptr()), B, H, D,
+                                 Tq, S, _rows3(q, "q"), _rows3(k, "k"), _rows3(v, "v"), _rows3(d_o, "d_o"),
+                                 _rows3(dq, "dq"), _rows3(dk, "dk"), _rows3(dv, "dv"), float(scale),
+                                 float(keep_prob), int(seed) & (2**64 - 1))
+  return dq, dk, dv
+
+
 def xent_smooth(logits, labels, label_smoothing, grad_scale_dev=None, want_grad=True,
                 v_valid=None, grad_scale=None):
   """logits [N,V] bf16, labels int32 [N] -> (row_loss [N], loss [1], dlogits|None).
