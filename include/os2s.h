@@ -339,6 +339,32 @@ int os2s_gemm_nt_ws(os2s_stream_t stream, const uint16_t* A, long long lda, cons
 int os2s_gemm_nt_mask_ws(os2s_stream_t stream, const uint16_t* A, long long lda, const uint16_t* W, void* C,
                          long long ldc, int M, int N, int K, const uint16_t* mask_ref, float mask_scale,
                          float* stats, void* workspace, size_t workspace_bytes);
+/* MXFP8 inference path (csrc/gemm_mx.hip; no reference counterpart: a project extension behind the
+ * 'mxfp8_inference' parameter of TransformerEncoder / TransformerDecoder). Forward-only replacement of
+ * tf.layers.Dense in parts/transformer/attention_layer.py:54-62,125-127,219, ffn_layer.py:51-85 and of the
+ * logits matmul of embedding_layer.py:90-105 in eval / infer mode.
+ *
+ * os2s_mx_quantize_rows: bf16 x [rows, K] (row stride ldx elements, ldx % 8 == 0) -> OCP MXFP8: e4m3 q
+ * [rows, K] contiguous and one E8M0 scale per 32 consecutive elements of a row. For a block with largest
+ * magnitude amax: e = floor(log2(amax)) - 8, scale byte = clamp(e + 127, 0, 254), element = x * 2^-e clamped to
+ * +-448 and rounded to nearest even; an all-zero block has scale byte 0. NaN / Inf are not handled.
+ * SCALE LAYOUT: scale is [ceil(K / 128)][rows][4] bytes — the four scale bytes of row r for the blocks
+ * 4 kt .. 4 kt + 3 form one 32-bit word at word index kt * rows + r (bytes of blocks past K / 32 are 0).
+ * One word is one row's scales for one 128-deep K tile of the GEMM, and the words of 32 consecutive rows are
+ * contiguous: the GEMM's per-lane scale operand of a K tile is one coalesced load.
+ *
+ * os2s_gemm_nt_mx: out[M,N] = act(deq(a)[M,K] . deq(w)[N,K]^T + bias) + residual, fp32 accumulation on the
+ * block-scaled MFMA (v_mfma_scale_f32_32x32x64_f8f6f4), out bf16 or fp32 (out_f32) with row stride ldc
+ * (elements); a: e4m3 with row stride lda (bytes), w: e4m3 contiguous [N, K]; a_scale / w_scale in the layout
+ * above (rows = M / N); bias fp32 [N] or NULL; act 0 or 1 (ReLU); residual bf16 with row stride ldc or NULL.
+ * Shapes: M >= 1, N % 8 == 0, K % 64 == 0, K >= 64 (OS2S_ERR_UNSUPPORTED otherwise, and for act outside
+ * {0, 1}). NULL operands, lda < K, lda % 16 != 0, ldc < N, ldc % 8 != 0 or a tensor pointer that is not 16-byte
+ * aligned (scales: 4-byte): OS2S_ERR_INVALID_ARG. */
+int os2s_mx_quantize_rows(os2s_stream_t stream, const uint16_t* x, long long ldx, int rows, int K, uint8_t* q,
+                          uint8_t* scale);
+int os2s_gemm_nt_mx(os2s_stream_t stream, const uint8_t* a, long long lda, const uint8_t* a_scale,
+                    const uint8_t* w, const uint8_t* w_scale, void* out, long long ldc, int M, int N, int K,
+                    const float* bias, int act, const uint16_t* residual, int out_f32);
 int os2s_conv1d_fwd(os2s_stream_t stream, const uint16_t* x, const uint16_t* w,
                     void* y, const int32_t* in_len, const float* bias,
                     float* stats, int B, int Tin, int Cin, int Cout, int K,

@@ -24,6 +24,11 @@ HIP_FLAGS = [
     "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC",
     "-Wno-unused-result",
 ] + os.environ.get("OS2S_EXTRA_HIPFLAGS", "").split()   # experiments (e.g. -DOS2S_PP_PRIO=1)
+# per-unit flags. gemm_mx.hip: no packed fp32 arithmetic (v_pk_add_f32 and its kin) in its epilogue; a target
+# attribute on the kernels would do the same but keeps their lambdas from being inlined (accumulators in scratch)
+UNIT_FLAGS = {
+    "gemm_mx.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+}
 
 
 def _newer(target: str, deps) -> bool:
@@ -66,7 +71,7 @@ def build_hip(force: bool = False, verbose: bool = False, only=None) -> str:
     s, o = job
     if verbose:
       print("[os2s build] hipcc", os.path.basename(s), flush=True)
-    _run([HIPCC] + HIP_FLAGS + ["-c", s, "-o", o])
+    _run([HIPCC] + HIP_FLAGS + UNIT_FLAGS.get(os.path.basename(s), []) + ["-c", s, "-o", o])
 
   if jobs:
     with ThreadPoolExecutor(max_workers=min(8, len(jobs))) as ex:

@@ -1176,6 +1176,50 @@ def gemm_nt_mask(a, w, mask_ref, mask_scale, out=None, want_colsum=False):
   return out, part
 
 
+MX_BLOCK = 32     # elements per E8M0 scale of the MXFP8 operands (OCP MX)
+
+
+def quantize_mx(x2d, q=None, scale=None):
+  """bf16 [rows, K] (row stride free) -> (e4m3 uint8 [rows, K], E8M0 scales uint8 [ceil(K/128), rows, 4])
+  (os2s_mx_quantize_rows). scale[kt, r, b] belongs to elements 128 kt + 32 b .. + 31 of row r (0 past K): the
+  layout os2s_gemm_nt_mx loads; mx_scales_by_row gives the plain [rows, K / 32] view."""
+  rows, K = x2d.shape
+  assert x2d.dtype == torch.bfloat16 and x2d.stride(1) == 1
+  if q is None:
+    q = torch.empty((rows, K), dtype=torch.uint8, device=x2d.device)
+    scale = torch.empty(((K + 127) // 128, rows, 4), dtype=torch.uint8, device=x2d.device)
+  assert tuple(q.shape) == (rows, K) and tuple(scale.shape) == ((K + 127) // 128, rows, 4)
+  _lib.C.os2s_mx_quantize_rows(_stream(), c_void_p(x2d.data_ptr()), x2d.stride(0), rows, K, _ptr(q, torch.uint8),
+                               _ptr(scale, torch.uint8))
+  return q, scale
+
+
+def mx_scales_by_row(scale, K):
+  """The scale bytes of quantize_mx as [rows, K / 32]: one per block of MX_BLOCK elements, in K order."""
+  return scale.permute(1, 0, 2).reshape(scale.shape[1], -1)[:, :K // MX_BLOCK]
+
+
+def gemm_nt_mx(a_q, a_scale, w_q, w_scale, out=None, bias=None, act=0, residual=None, out_f32=False):
+  """out[M,N] = act(deq(a)[M,K] @ deq(w)[N,K]^T + bias) + residual on the block-scaled MFMA (os2s_gemm_nt_mx);
+  operands and scales from quantize_mx. a_q: row stride free; out bf16, or fp32 with out_f32."""
+  M, K = a_q.shape
+  N, K2 = w_q.shape
+  assert K == K2 and a_q.stride(1) == 1 and w_q.is_contiguous()
+  assert a_q.dtype == torch.uint8 and w_q.dtype == torch.uint8
+  assert tuple(a_scale.shape) == ((K + 127) // 128, M, 4) and tuple(w_scale.shape) == ((K + 127) // 128, N, 4)
+  if out is None:
+    out = torch.empty((M, N), dtype=torch.float32 if out_f32 else torch.bfloat16, device=a_q.device)
+  assert out.stride(1) == 1 and tuple(out.shape) == (M, N)
+  assert out.dtype == (torch.float32 if out_f32 else torch.bfloat16)
+  assert residual is None or (residual.dtype == torch.bfloat16 and residual.stride(1) == 1 and
+                              residual.stride(0) == out.stride(0) and tuple(residual.shape) == (M, N))
+  _lib.C.os2s_gemm_nt_mx(_stream(), c_void_p(a_q.data_ptr()), a_q.stride(0), _ptr(a_scale, torch.uint8),
+                         _ptr(w_q, torch.uint8), _ptr(w_scale, torch.uint8), c_void_p(out.data_ptr()), out.stride(0),
+                         M, N, K, _ptr(bias, torch.float32, True), int(act),
+                         c_void_p(residual.data_ptr()) if residual is not None else c_void_p(0), int(bool(out_f32)))
+  return out
+
+
 def dense_epilogue(y, bias=None, act=0, keep_prob=1.0, seed=0, residual=None):
   """In place: y = residual + dropout(act(y + bias)) on bf16 [rows, C]."""
   rows, C = y.shape

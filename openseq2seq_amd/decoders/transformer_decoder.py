@@ -33,6 +33,10 @@ class TransformerDecoder(Decoder):
         'regularizer': None, 'regularizer_params': dict, 'initializer': None,
         'initializer_params': dict, 'GO_SYMBOL': int, 'PAD_SYMBOL': int, 'END_SYMBOL': int,
         'norm_params': dict,
+        # extension, as in TransformerEncoder: the forward-only Dense GEMMs with more rows than a decode step, and
+        # the logits matmul of an eval pass, on the MXFP8 GEMM (csrc/gemm_mx.hip). The beam search's steps are
+        # skinny and stay bf16; no effect on a training pass.
+        'mxfp8_inference': bool,
     })
 
   def __init__(self, params, model, name="transformer_decoder", mode='train'):
@@ -64,6 +68,8 @@ class TransformerDecoder(Decoder):
           ln3=L.make_norm(store, ls + "/ffn", D, norm, training),
           ffn=L.FeedForward(store, ls + "/ffn/feed_foward_network", D, p["filter_size"], l2=l2)))
     self.output_normalization = L.make_norm(store, scope, D, norm, training)
+    if p.get('mxfp8_inference', False):
+      L.enable_mxfp8(self.layers, self.cross_kv)
     return self
 
   def _decode(self, input_dict):
@@ -101,7 +107,7 @@ class TransformerDecoder(Decoder):
       y = lyr["ln3"].forward(x, tape)
       x = lyr["ffn"].forward(y, tape, seeds, relu_keep, post_keep, residual=x)
     out = self.output_normalization.forward(x, tape)
-    logits = emb.linear(out, tape)
+    logits = emb.linear(out, tape, mxfp8=bool(p.get('mxfp8_inference', False)))
     # vocab_size: the logical vocabulary — logits has emb.Vpad >= emb.V columns (L.SharedEmbedding)
     return {"logits": logits.data, "logits_act": logits, "packed_target": pt, "vocab_size": emb.V,
             "outputs": None, "final_state": None, "final_sequence_lengths": None}

@@ -23,6 +23,10 @@ class TransformerEncoder(Encoder):
     return dict(Encoder.get_optional_params(), **{
         'regularizer': None, 'regularizer_params': dict, 'initializer': None,
         'initializer_params': dict, 'pad_embeddings_2_eight': bool, 'norm_params': dict,
+        # extension (BASELINE.json north star "bf16/fp8"; the reference has no fp8): in eval / infer mode the Dense
+        # layers with more rows than a decode step run on the MXFP8 GEMM (csrc/gemm_mx.hip): e4m3 operands with one
+        # E8M0 scale per 32 elements, fp32 accumulation. No effect on a training pass.
+        'mxfp8_inference': bool,
     })
 
   def __init__(self, params, model, name="transformer_encoder", mode='train'):
@@ -55,6 +59,8 @@ class TransformerEncoder(Encoder):
           ln2=L.make_norm(store, ls + "/ffn", D, norm, training),
           ffn=L.FeedForward(store, ls + "/ffn/feed_foward_network", D, p["filter_size"], l2=l2)))
     self.output_normalization = L.make_norm(store, scope, D, norm, training)
+    if p.get('mxfp8_inference', False):
+      L.enable_mxfp8(self.layers)
     return self
 
   def _encode(self, input_dict):

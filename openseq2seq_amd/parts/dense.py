@@ -70,9 +70,44 @@ def bias_grad_from_rows(dy2d, bias_param):
   capi.colsum_finalize(capi.bn_stats(dy2d), None, bias_param.grad)
 
 
+def mx_usable(x2d, cin, cout, act=0, residual=None):
+  """The calls the MXFP8 inference path takes (csrc/gemm_mx.hip): more rows than the skinny kernel's, a shape and
+  an epilogue os2s_gemm_nt_mx has, 16-byte rows."""
+  return x2d.shape[0] > SKINNY_MAX_ROWS and cin >= 64 and cin % 64 == 0 and cout % 8 == 0 and act in (0, 1) and \
+      x2d.stride(1) == 1 and x2d.stride(0) % 8 == 0 and \
+      (residual is None or (residual.stride(1) == 1 and residual.stride(0) == cout))
+
+
+class MxWeight(object):
+  """The MXFP8 copy (e4m3 elements + E8M0 block scales, capi.quantize_mx) of one bf16 weight matrix, re-quantised
+  whenever the bf16 weights changed: the flat store's version counter (optimizer step, checkpoint load), as the
+  e4m3 copies of rnn_decoders.py::fp8_copies."""
+
+  def __init__(self):
+    self.ver, self.q, self.scale = object(), None, None
+
+  def get(self, store, w2d):
+    ver = getattr(store, "version", None) if store is not None else None
+    if self.q is None or ver is None or ver != self.ver:
+      self.q, self.scale = capi.quantize_mx(w2d, self.q, self.scale)
+      self.ver = ver
+    return self.q, self.scale
+
+
+def mx_gemm(cache, store, x2d, w2d, bias=None, act=0, residual=None):
+  """act(x W^T + b) + residual with both operands in MXFP8: the cached weight copy, the activation quantised here."""
+  wq, ws = cache.get(store, w2d)
+  aq, asc = capi.quantize_mx(x2d)
+  return capi.gemm_nt_mx(aq, asc, wq, ws, bias=bias, act=act, residual=residual)
+
+
 class Dense(object):
   """tf.layers.Dense on [N, Cin] rows; kernel stored [1, Cout, Cin] (device layout,
-  = the transpose of TF's [Cin, Cout])."""
+  = the transpose of TF's [Cin, Cout]).
+
+  mxfp8 (set by the 'mxfp8_inference' parameter of TransformerEncoder / TransformerDecoder): without a tape, calls
+  with more than SKINNY_MAX_ROWS rows run on the MXFP8 GEMM (mx_usable); everything else is the bf16 path."""
+  mxfp8 = False
 
   def __init__(self, store, name, cin, cout, use_bias, l2=0.0):
     self.cin, self.cout = cin, cout
@@ -99,6 +134,10 @@ class Dense(object):
                                   relu=(act == 1), residual=residual.data if residual is not None else None))
     bias = self.bias.master if self.bias is not None else None
     res = residual.data if residual is not None else None
+    if self.mxfp8 and tape is None and keep >= 1.0 and mx_usable(x.data, self.cin, self.cout, act, res):
+      if getattr(self, "_mx", None) is None:
+        self._mx = MxWeight()
+      return Act(mx_gemm(self._mx, self.kernel.store, x.data, self.w, bias=bias, act=act, residual=res))
     if self.cin % 64 == 0 and act in (0, 1, 3) and self.cout % 8 == 0:   # what gemm_pp.hip accepts
       y = capi.gemm_nt(x.data, self.w, bias=bias, act=act, keep_prob=keep, seed=seed, residual=res)
     else:

@@ -290,6 +290,14 @@ class FusedCrossKV(object):
     k0, n = self.kvs[0].kernel, len(self.kvs)
     return flat[k0.offset:k0.offset + n * k0.numel].view(n * 2 * self.D, self.D)
 
+  def _gemm(self, x2d, tape):
+    w = self._rows(self.store.w16)
+    if self.kvs[0].mxfp8 and tape is None and dense.mx_usable(x2d, w.shape[1], w.shape[0]):
+      if getattr(self, "_mx", None) is None:
+        self._mx = dense.MxWeight()
+      return dense.mx_gemm(self._mx, self.store, x2d, w)
+    return capi.gemm_nt(x2d, w)
+
   def forward(self, enc_out, tape):
     # on the side stream: nothing of the decoder needs the result before its first encoder-decoder attention, and
     # the embedding + self-attention sublayer in front of it are 132-tile launches that leave half the chip idle
@@ -297,11 +305,11 @@ class FusedCrossKV(object):
     self._side = None
     if FUSE_CROSS_KV_SIDE:
       with on_side_stream(enc_out.data.device, enc_out.data) as ctx:
-        y = capi.gemm_nt(enc_out.data, self._rows(self.store.w16))
+        y = self._gemm(enc_out.data, tape)
         ctx.hand_over(y)
         self._side = ctx.side
     else:
-      y = capi.gemm_nt(enc_out.data, self._rows(self.store.w16))
+      y = self._gemm(enc_out.data, tape)
     out = Act(y)
     if tape is None:
       return out
@@ -337,6 +345,20 @@ class FeedForward(object):
     s1, s2 = (seeds.next(), seeds.next()) if seeds is not None else (0, 0)
     h = self.filter_layer.forward(x, tape, act=1, keep=relu_keep, seed=s1)
     return self.output_layer.forward(h, tape, keep=post_keep, seed=s2, residual=residual)
+
+
+def enable_mxfp8(*objs):
+  """'mxfp8_inference': every Dense reachable from the given layer objects (layer dicts, lists, attention / FFN
+  blocks, FusedCrossKV) takes the MXFP8 GEMM for its forward-only calls (parts/dense.py)."""
+  for o in objs:
+    if isinstance(o, dict):
+      enable_mxfp8(*o.values())
+    elif isinstance(o, (list, tuple)):
+      enable_mxfp8(*o)
+    elif isinstance(o, Dense):
+      o.mxfp8 = True
+    elif isinstance(o, (MultiHeadAttention, FeedForward, FusedCrossKV)):
+      enable_mxfp8(*[v for v in vars(o).values() if isinstance(v, (Dense, list))])
 
 
 class SharedEmbedding(object):
@@ -389,10 +411,15 @@ class SharedEmbedding(object):
       tape.record(backward, [emb.weights] if final_use else ())
     return out
 
-  def linear(self, x, tape):
-    """logits = x E^T  (bf16 [N, Vpad]; columns >= V are the zero padding rows' and count nowhere)."""
+  def linear(self, x, tape, mxfp8=False):
+    """logits = x E^T  (bf16 [N, Vpad]; columns >= V are the zero padding rows' and count nowhere). mxfp8: the
+    decoder's 'mxfp8_inference' — a forward-only call with more rows than a decode step runs on the MXFP8 GEMM."""
     if tape is None and x.data.shape[0] <= dense.SKINNY_MAX_ROWS and SKINNY_LOGITS:
       return Act(capi.gemm_skinny(x.data, self.table))
+    if mxfp8 and tape is None and dense.mx_usable(x.data, self.D, self.Vpad):
+      if getattr(self, "_mx", None) is None:
+        self._mx = dense.MxWeight()
+      return Act(dense.mx_gemm(self._mx, self.weights.store, x.data, self.table))
     out = Act(capi.gemm(x.data, self.table))
     if tape is not None:
       emb = self
