@@ -1018,6 +1018,21 @@ int os2s_dense_epilogue(os2s_stream_t stream, uint16_t* y, const float* bias, lo
 int os2s_gemm_skinny(os2s_stream_t stream, const uint16_t* x, long long ldx, const uint16_t* w,
                      long long ldw, const float* bias, const uint16_t* residual, long long ldr,
                      int M, int N, int K, int relu, uint16_t* y, long long ldy);
+/* os2s_gemm_skinny with MXFP8 operands on the block-scaled MFMA (csrc/gemm_skinny_mx.hip; a project extension
+ * behind the 'mxfp8_decode' parameter of TransformerDecoder): the tf.layers.Dense calls under
+ * TransformerDecoder._get_symbols_to_logits_fn (open_seq2seq/decoders/transformer_decoder.py:232-285).
+ *   y[M,N] = act(deq(mx(x))[M,K] . deq(w_q)[N,K]^T + bias) (+ residual)       (bf16, fp32 accumulation)
+ * x: bf16 [M, K] (row stride ldx, ldx % 8 == 0), quantised to MXFP8 INSIDE the kernel under the rule of
+ * os2s_mx_quantize_rows (bit-identical to it; no quantiser launch). w_q / w_scale: what os2s_mx_quantize_rows
+ * produces for the [N, K] weights (e4m3 bytes, scale words [ceil(K / 128)][N]). bias fp32 [N] or NULL, residual
+ * bf16 (row stride ldr) or NULL, relu 0 or 1, y bf16 with row stride ldy. K-shares are reduced in a fixed order:
+ * bitwise reproducible. Shapes: M >= 1 (meant for <= 512), N >= 8, N % 8 == 0, K >= 64, K % 64 == 0
+ * (OS2S_ERR_UNSUPPORTED otherwise); NULL operands or misaligned pointers / strides: OS2S_ERR_INVALID_ARG.
+ * tile: -1 = chosen by shape; 0 .. 4 force one tile of the family (m x n: 32x32, 64x64, 64x128, 128x256, 256x256) —
+ * for tests and measurements; every tile takes every shape. */
+int os2s_gemm_skinny_mx(os2s_stream_t stream, const uint16_t* x, long long ldx, const uint8_t* w_q,
+                        const uint8_t* w_scale, const float* bias, const uint16_t* residual, long long ldr,
+                        int M, int N, int K, int relu, uint16_t* y, long long ldy, int tile);
 /* Decoder self-attention for ONE new position per beam row (SelfAttention with cache,
  * parts/transformer/attention_layer.py:133-139): appends knew/vnew [N, H*dh] (row stride
  * ldnew) to the append-only caches [N, Tmax, H*dh] at slot `step`, sets

@@ -28,6 +28,9 @@ HIP_FLAGS = [
 # attribute on the kernels would do the same but keeps their lambdas from being inlined (accumulators in scratch)
 UNIT_FLAGS = {
     "gemm_mx.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+    # the same for the bias / residual adds of four adjacent columns in gemm_skinny_mx.hip's epilogue and the
+    # clamp multiplies of its in-kernel quantiser
+    "gemm_skinny_mx.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
 }
 
 

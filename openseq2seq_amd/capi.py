@@ -1241,6 +1241,25 @@ def gemm_skinny(x2d, w, bias=None, relu=False, residual=None):
   return y
 
 
+def gemm_skinny_mx(x2d, w_q, w_scale, bias=None, relu=False, residual=None, tile=-1):
+  """gemm_skinny with MXFP8 operands (os2s_gemm_skinny_mx): x2d [M,K] bf16 (row stride free) is quantised inside the
+  kernel, w_q [N,K] e4m3 / w_scale from quantize_mx -> bf16 [M,N]; for small M (decoding steps). tile: -1 = by shape,
+  0 .. 4 = one tile of the family (tests, tools)."""
+  M, K = x2d.shape
+  N = w_q.shape[0]
+  assert x2d.dtype == torch.bfloat16 and x2d.stride(1) == 1 and w_q.dtype == torch.uint8 and w_q.is_contiguous()
+  assert tuple(w_q.shape) == (N, K) and tuple(w_scale.shape) == ((K + 127) // 128, N, 4)
+  assert residual is None or (residual.dtype == torch.bfloat16 and residual.stride(1) == 1 and
+                              tuple(residual.shape) == (M, N))
+  y = torch.empty((M, N), dtype=torch.bfloat16, device=x2d.device)
+  _lib.C.os2s_gemm_skinny_mx(_stream(), c_void_p(x2d.data_ptr()), x2d.stride(0), _ptr(w_q, torch.uint8),
+                             _ptr(w_scale, torch.uint8), _ptr(bias, torch.float32, True),
+                             c_void_p(residual.data_ptr()) if residual is not None else c_void_p(0),
+                             residual.stride(0) if residual is not None else 0, M, N, K, int(bool(relu)), _ptr(y), N,
+                             int(tile))
+  return y
+
+
 def gemm_wgrad(x2d, dy2d, out, accumulate=True):
   """dW [Cout,Cin] (+)= dy^T x (fp32)."""
   N, Cin = x2d.shape

@@ -29,7 +29,7 @@
 // 32x32 (128 registers), K tile 128: a tile row is 128 bytes, two MFMA steps of 64. 32x32x64 and not 16x16x128:
 // it needs half the fragment bytes per FLOP (a 32-row fragment feeds 32 columns) and the LDS read port, not the
 // matrix core, is what a tile of 8-bit operands runs into first. Transformer-big eval has M = 16 384: N = 1024
-// is 256 tiles, one per CU; a narrow-M tile is not built (the decode steps stay on the bf16 skinny kernel).
+// is 256 tiles, one per CU; the narrow-M tiles of the decode steps are gemm_skinny_mx.hip.
 //   LDS: two stages x (A 32 KB + W 32 KB) = 128 KB, filled by buffer-load-to-LDS, 16 bytes per lane: one
 //     instruction writes 8 rows x 128 bytes, 8 per wave per K tile. A lane's fragment is 32 bytes of a row = the
 //     two 16-byte slots 4 ks + l / 32 and 4 ks + 2 + l / 32. Slots are stored at (slot ^ ((row >> 1) & 7)): the
@@ -44,11 +44,9 @@
 //     lane: bias, ReLU, residual, one 16-byte store of bf16 (two of fp32).
 #include <type_traits>
 
-#include "os2s_common.hpp"
+#include "mx_common.hpp"
 
 namespace os2s {
-
-typedef __attribute__((ext_vector_type(8))) int i32x8;
 
 // ------------------------------------------------------------------------------------------------------------
 // Quantiser: 16 lanes own one (row, K tile) unit of 128 elements, 4 lanes a block of 32, 8 elements a lane.
@@ -64,33 +62,10 @@ __global__ __launch_bounds__(256) void mx_quantize_rows_kernel(const bf16_t* __r
   const bool live = r < rows && k < K;        // K % 64 == 0: the last unit of a row may be half empty
   u32x4 v = {0u, 0u, 0u, 0u};
   if (live) v = *reinterpret_cast<const u32x4*>(x + (long long)r * ldx + k);
-  // largest magnitude as an integer: bf16 without its sign orders like its value
-  int m = 0;
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    const int lo = (int)(v[e] & 0x7fffu), hi = (int)((v[e] >> 16) & 0x7fffu);
-    m = max(m, max(lo, hi));
-  }
-  m = max(m, __builtin_amdgcn_update_dpp(0, m, 0xB1, 0xf, 0xf, false));   // quad_perm [1,0,3,2]
-  m = max(m, __builtin_amdgcn_update_dpp(0, m, 0x4E, 0xf, 0xf, false));   // quad_perm [2,3,0,1]
-  const int byte = max((m >> 7) - 8, 0);                                  // exponent field - 8, clamped at 0
-  const float mult = __builtin_bit_cast(float, (uint32_t)(254 - byte) << 23);   // 2^-(byte - 127)
-  u32x2 o;
-#pragma unroll
-  for (int h = 0; h < 2; ++h) {
-    const float a0 = fminf(fmaxf(bflo(v[2 * h]) * mult, -448.f), 448.f);
-    const float a1 = fminf(fmaxf(bfhi(v[2 * h]) * mult, -448.f), 448.f);
-    const float a2 = fminf(fmaxf(bflo(v[2 * h + 1]) * mult, -448.f), 448.f);
-    const float a3 = fminf(fmaxf(bfhi(v[2 * h + 1]) * mult, -448.f), 448.f);
-    int pk = __builtin_amdgcn_cvt_pk_fp8_f32(a0, a1, 0, false);
-    pk = __builtin_amdgcn_cvt_pk_fp8_f32(a2, a3, pk, true);
-    o[h] = (uint32_t)pk;
-  }
+  int byte;
+  const u32x2 o = mx_quantize8(v, byte);
   if (live) *reinterpret_cast<u32x2*>(q + (long long)r * K + k) = o;
-  // the unit's four scale bytes, gathered from the first lane of each quad, as one word
-  const int g0 = lane & 48;
-  const uint32_t word = (uint32_t)__shfl(byte, g0, 64) | ((uint32_t)__shfl(byte, g0 + 4, 64) << 8) |
-                        ((uint32_t)__shfl(byte, g0 + 8, 64) << 16) | ((uint32_t)__shfl(byte, g0 + 12, 64) << 24);
+  const uint32_t word = mx_scale_word(byte, lane);   // the unit's four scale bytes as one word
   if (sub == 0 && r < rows) scale[(long long)kt * rows + r] = word;
 }
 
@@ -110,20 +85,6 @@ constexpr int kMxStage = 2 * kMxOperand;                // A + W
 constexpr int kMxPatchStride = 68;                      // floats per row of a wave's epilogue patch
 constexpr int kMxPatch = 32 * kMxPatchStride * 4;       // bytes
 constexpr size_t kMxLds = 2 * kMxStage;                 // 128 KB (the 8 epilogue patches reuse 68 KB of it)
-
-__device__ __forceinline__ void mx_barrier() {
-  __builtin_amdgcn_sched_barrier(0);
-  __builtin_amdgcn_s_barrier();
-  __builtin_amdgcn_sched_barrier(0);
-}
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t mx_rsrc(const uint8_t* base, long long bytes) {
-  const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)(unsigned long long)base);
-  const unsigned hi = __builtin_amdgcn_readfirstlane((unsigned)((unsigned long long)base >> 32));
-  const long long cl = bytes < 0 ? 0 : (bytes < 0x7fffffffll ? bytes : 0x7fffffffll);
-  return __builtin_amdgcn_make_buffer_rsrc((void*)(((unsigned long long)hi << 32) | lo), 0,
-                                           __builtin_amdgcn_readfirstlane((int)cl), 0x00020000);
-}
 
 __global__ __launch_bounds__(512, 1) void gemm_nt_mx_kernel(MxGemmArgs p) {
   constexpr int MI = 4, NI = 2;

@@ -35,8 +35,13 @@ class TransformerDecoder(Decoder):
         'norm_params': dict,
         # extension, as in TransformerEncoder: the forward-only Dense GEMMs with more rows than a decode step, and
         # the logits matmul of an eval pass, on the MXFP8 GEMM (csrc/gemm_mx.hip). The beam search's steps are
-        # skinny and stay bf16; no effect on a training pass.
+        # skinny and stay bf16 ('mxfp8_decode' below is their switch); no effect on a training pass.
         'mxfp8_inference': bool,
+        # extension, independent of the one above: the Dense layers and the logits matmul of the beam search's
+        # decode steps on the MXFP8 skinny kernel (csrc/gemm_skinny_mx.hip), except at the shapes where the bf16
+        # kernels measured faster — today every Transformer-big shape (parts/dense.py::mx_decode_wins). No effect on
+        # a training or eval pass.
+        'mxfp8_decode': bool,
     })
 
   def __init__(self, params, model, name="transformer_decoder", mode='train'):
@@ -70,6 +75,8 @@ class TransformerDecoder(Decoder):
     self.output_normalization = L.make_norm(store, scope, D, norm, training)
     if p.get('mxfp8_inference', False):
       L.enable_mxfp8(self.layers, self.cross_kv)
+    if p.get('mxfp8_decode', False):
+      L.enable_mxfp8_decode(self.layers)
     return self
 
   def _decode(self, input_dict):
@@ -128,6 +135,17 @@ class TransformerDecoder(Decoder):
     vc = [torch.empty((N, Tmax, D), dtype=torch.bfloat16, device=dev) for _ in self.layers]
     enc_kv = [lyr["cross"].kv.forward(enc_out, None).data for lyr in self.layers]
     pos = torch.arange(Tmax, dtype=torch.int32, device=dev)[:, None].expand(Tmax, N).contiguous()
+    mx_decode = bool(p.get('mxfp8_decode', False))
+    if mx_decode:
+      # the MXFP8 weight copies exist before any step runs: no quantiser launch inside a captured step
+      wins = L.dense.mx_decode_wins
+      if wins(N, emb.Vpad, emb.D):
+        emb.mx_table()
+      for lyr in self.layers:
+        for d in (lyr["self_att"].qkv, lyr["self_att"].out, lyr["cross"].q, lyr["cross"].out,
+                  lyr["ffn"].filter_layer, lyr["ffn"].output_layer):
+          if wins(N, d.cout, d.cin):
+            d.mx_weight()
 
     def step(last, positions, i, status, cache):
       anc = cache["ancestry"]
@@ -146,7 +164,7 @@ class TransformerDecoder(Decoder):
         y = lyr["ln3"].forward(x, None)
         x = lyr["ffn"].forward(y, None, None, 1.0, 1.0, residual=x)
       out = self.output_normalization.forward(x, None)
-      return emb.linear(out, None).data, cache
+      return emb.linear(out, None, mxfp8_decode=mx_decode).data, cache
 
     def symbols_to_logits_fn(ids, i, cache):
       return step(ids[:, -1].contiguous(), pos[i], i, None, cache)

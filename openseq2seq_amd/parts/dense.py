@@ -78,6 +78,23 @@ def mx_usable(x2d, cin, cout, act=0, residual=None):
       (residual is None or (residual.stride(1) == 1 and residual.stride(0) == cout))
 
 
+def mx_decode_usable(x2d, cin, cout, residual=None):
+  """The decode-step calls os2s_gemm_skinny_mx takes under 'mxfp8_decode' (csrc/gemm_skinny_mx.hip): a shape the
+  kernel has, 16-byte rows, and a shape at which an MX tile beat the bf16 skinny kernel by more than the measured
+  spread (mx_decode_wins; profiles/mxfp8_decode_first_measurements.md) — every other call keeps bf16."""
+  return cin >= 64 and cin % 64 == 0 and cout >= 8 and cout % 8 == 0 and x2d.stride(1) == 1 and \
+      x2d.stride(0) % 8 == 0 and x2d.data_ptr() % 16 == 0 and (residual is None or residual.stride(1) == 1) and \
+      mx_decode_wins(x2d.shape[0], cout, cin)
+
+
+def mx_decode_wins(rows, cout, cin):
+  """The by-shape rule of 'mxfp8_decode', from profiles/mxfp8_decode_first_measurements.md (MI355X, 256 rows): at
+  every Transformer-big decode shape — proj, qkv, ffn-in, ffn-out, logits: weight matrices of 2^20 elements and
+  more — the best MX tile took 1.03 - 1.41 x the time of the best bf16 kernel, so those keep bf16. Smaller weight
+  matrices were not measured (both paths are one launch latency there) and take the MX kernel."""
+  return cout * cin < (1 << 20)
+
+
 class MxWeight(object):
   """The MXFP8 copy (e4m3 elements + E8M0 block scales, capi.quantize_mx) of one bf16 weight matrix, re-quantised
   whenever the bf16 weights changed: the flat store's version counter (optimizer step, checkpoint load), as the
@@ -108,6 +125,9 @@ class Dense(object):
   mxfp8 (set by the 'mxfp8_inference' parameter of TransformerEncoder / TransformerDecoder): without a tape, calls
   with more than SKINNY_MAX_ROWS rows run on the MXFP8 GEMM (mx_usable); everything else is the bf16 path."""
   mxfp8 = False
+  # set by the 'mxfp8_decode' parameter of TransformerDecoder: without a tape, calls of SKINNY_MAX_ROWS rows or fewer
+  # (the beam search's steps) run on the MXFP8 skinny kernel where mx_decode_usable; independent of `mxfp8`
+  mxfp8_decode = False
 
   def __init__(self, store, name, cin, cout, use_bias, l2=0.0):
     self.cin, self.cout = cin, cout
@@ -126,9 +146,20 @@ class Dense(object):
   def w(self):
     return self.kernel.w16.view(self.cout, self.cin)
 
+  def mx_weight(self):
+    """(e4m3 bytes, scale words) of the weights: the one MxWeight cache of this layer, current."""
+    if getattr(self, "_mx", None) is None:
+      self._mx = MxWeight()
+    return self._mx.get(self.kernel.store, self.w)
+
   def forward(self, x, tape, act=0, keep=1.0, seed=0, residual=None):
     """y = residual + dropout(act(x W^T + b)); x, residual: Act; returns Act."""
     if tape is None and keep >= 1.0 and x.data.shape[0] <= SKINNY_MAX_ROWS:
+      res = residual.data if residual is not None else None
+      if self.mxfp8_decode and act in (0, 1) and mx_decode_usable(x.data, self.cin, self.cout, res):
+        wq, ws = self.mx_weight()
+        return Act(capi.gemm_skinny_mx(x.data, wq, ws, bias=self.bias.master if self.bias is not None else None,
+                                       relu=(act == 1), residual=res))
       # decoding step: a few hundred rows — latency-bound kernel (csrc/gemm_skinny.hip)
       return Act(capi.gemm_skinny(x.data, self.w, bias=self.bias.master if self.bias is not None else None,
                                   relu=(act == 1), residual=residual.data if residual is not None else None))

@@ -361,6 +361,20 @@ def enable_mxfp8(*objs):
       enable_mxfp8(*[v for v in vars(o).values() if isinstance(v, (Dense, list))])
 
 
+def enable_mxfp8_decode(*objs):
+  """'mxfp8_decode': every Dense reachable from the given layer objects takes the MXFP8 skinny kernel for its
+  decode-step calls (parts/dense.py)."""
+  for o in objs:
+    if isinstance(o, dict):
+      enable_mxfp8_decode(*o.values())
+    elif isinstance(o, (list, tuple)):
+      enable_mxfp8_decode(*o)
+    elif isinstance(o, Dense):
+      o.mxfp8_decode = True
+    elif isinstance(o, (MultiHeadAttention, FeedForward)):
+      enable_mxfp8_decode(*[v for v in vars(o).values() if isinstance(v, (Dense, list))])
+
+
 class SharedEmbedding(object):
   """EmbeddingSharedWeights (embedding_layer.py:26-105): one [V, D] matrix used for the
   input embeddings of both stacks and, transposed, for the pre-softmax projection.
@@ -411,9 +425,20 @@ class SharedEmbedding(object):
       tape.record(backward, [emb.weights] if final_use else ())
     return out
 
-  def linear(self, x, tape, mxfp8=False):
+  def mx_table(self):
+    """(e4m3 bytes, scale words) of the table: the one MxWeight cache of this layer, current."""
+    if getattr(self, "_mx", None) is None:
+      self._mx = dense.MxWeight()
+    return self._mx.get(self.weights.store, self.table)
+
+  def linear(self, x, tape, mxfp8=False, mxfp8_decode=False):
     """logits = x E^T  (bf16 [N, Vpad]; columns >= V are the zero padding rows' and count nowhere). mxfp8: the
-    decoder's 'mxfp8_inference' — a forward-only call with more rows than a decode step runs on the MXFP8 GEMM."""
+    decoder's 'mxfp8_inference' — a forward-only call with more rows than a decode step runs on the MXFP8 GEMM.
+    mxfp8_decode: the decoder's 'mxfp8_decode' — a decode-step call runs on the MXFP8 skinny kernel."""
+    if mxfp8_decode and tape is None and x.data.shape[0] <= dense.SKINNY_MAX_ROWS and \
+        dense.mx_decode_usable(x.data, self.D, self.Vpad):
+      wq, ws = self.mx_table()
+      return Act(capi.gemm_skinny_mx(x.data, wq, ws))
     if tape is None and x.data.shape[0] <= dense.SKINNY_MAX_ROWS and SKINNY_LOGITS:
       return Act(capi.gemm_skinny(x.data, self.table))
     if mxfp8 and tape is None and dense.mx_usable(x.data, self.D, self.Vpad):

@@ -1,13 +1,20 @@
 #!/usr/bin/env python
 """Micro-benchmarks of the kernels of one Transformer-big beam-search step (N = 256 beam rows):
-skinny GEMMs per shape, the logits GEMM, decode attention, LayerNorm, the beam kernels."""
+skinny GEMMs per shape, the logits GEMM, decode attention, LayerNorm, the beam kernels.
+
+  --mx    the MXFP8 skinny kernel (os2s_gemm_skinny_mx: every forced tile and the by-shape choice) next to the bf16
+          skinny kernel's by-shape choice and the LDS-tiled bf16 GEMM the logits take, alternated in one process
+  --step  ms per beam-search step of Transformer-big, 64 sentences x beam 4 (the workload of
+          bench.py --only-transformer-infer), 'mxfp8_decode' off and on, two models alternated in one process"""
+import argparse
 import os
+import time
 import sys
 
 import torch
 import os as _os, sys as _sys
 _sys.path.insert(0, _os.path.join(_os.path.dirname(_os.path.abspath(__file__)), "lt"))
-import lt_backend  # noqa: E402  (hipBLASLt comparison harness, tools only)
+import lt_backend  # noqa: E402  (hipBLASLt comparison harness, tools only; loads its library at the first call)
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from openseq2seq_amd import _lib, capi  # noqa: E402
@@ -33,8 +40,69 @@ def timeit(fn, reps=20, warm=3):
   return e0.elapsed_time(e1) * 1e3 / (5 * reps)
 
 
+DECODE_SHAPES = {"proj 1024x1024": (1024, 1024), "qkv 3072x1024": (3072, 1024), "ffn-in 4096x1024": (4096, 1024),
+                 "ffn-out 1024x4096": (1024, 4096), "logits 32768x1024": (32768, 1024)}
+MX_TILES = ["32x32", "64x64", "64x128", "128x256", "256x256"]      # tile 0 .. 4 of capi.gemm_skinny_mx (m x n)
+
+
+def bench_mx(dev, rows=256, rounds=5):
+  """us per call, median over `rounds` alternated rounds, and the spread (max - min) / median of the bf16 column."""
+  bf = lambda *s: torch.randn(*s, device=dev).to(torch.bfloat16)
+  for name, (n, k) in DECODE_SHAPES.items():
+    x, w = bf(rows, k), bf(n, k) * k ** -0.5
+    wq, ws = capi.quantize_mx(w)
+    cols = {"bf16 skinny": lambda: capi.gemm_skinny(x, w), "bf16 gemm": lambda: capi.gemm(x, w)}
+    t = {c: [] for c in list(cols) + MX_TILES + ["mx auto"]}
+    for _ in range(rounds):
+      for c, fn in cols.items():
+        t[c].append(timeit(fn))
+      for v, c in enumerate(MX_TILES):
+        t[c].append(timeit(lambda: capi.gemm_skinny_mx(x, wq, ws, tile=v)))
+      t["mx auto"].append(timeit(lambda: capi.gemm_skinny_mx(x, wq, ws)))
+    med = {c: sorted(v)[len(v) // 2] for c, v in t.items()}
+    base = min(med["bf16 skinny"], med["bf16 gemm"])
+    spread = max((max(v) - min(v)) / med[c] for c, v in t.items())
+    print("%-18s rows %d  " % (name, rows) + "  ".join("%s %.1f" % (c, med[c]) for c in t) +
+          "  us | best mx / best bf16 %.2f, spread %.1f %%" % (min(med[c] for c in MX_TILES) / base, 100 * spread),
+          flush=True)
+
+
+def bench_step(dev, batch=64, rounds=4):
+  from openseq2seq_amd.configs.transformer import transformer_config
+  models = {}
+  for on in (False, True):
+    model_cls, params = transformer_config(batch_size_per_gpu=batch)
+    params["decoder_params"]["mxfp8_decode"] = on
+    torch.manual_seed(0)
+    models[on] = model_cls(params, mode="infer", hvd=None, device=dev)
+    models[on].compile()
+  data = models[False].get_data_layer().synthetic_batch(dev, seed=7)
+  ms = {False: [], True: []}
+  for r in range(rounds + 1):
+    for on in (False, True):
+      torch.cuda.synchronize()
+      t0 = time.perf_counter()
+      ids, _ = models[on].infer_batch(data)
+      torch.cuda.synchronize()
+      if r > 0:                     # round 0 warms up
+        ms[on].append(1e3 * (time.perf_counter() - t0) / int(ids.shape[1]))
+  for on in (False, True):
+    print("mxfp8_decode %-5s ms per decode step (encoder included): %s  median %.4f" %
+          (on, " ".join("%.4f" % v for v in ms[on]), sorted(ms[on])[len(ms[on]) // 2]), flush=True)
+
+
 def main():
+  ap = argparse.ArgumentParser()
+  ap.add_argument("--mx", action="store_true")
+  ap.add_argument("--step", action="store_true")
+  args = ap.parse_args()
   dev = torch.device("cuda:0")
+  if args.mx or args.step:
+    if args.mx:
+      bench_mx(dev)
+    if args.step:
+      bench_step(dev)
+    return
   N, D, H, F, V = 256, 1024, 16, 4096, 32768
   bf = lambda *s: torch.randn(*s, device=dev).to(torch.bfloat16)
   x, xf = bf(N, D), bf(N, F)
