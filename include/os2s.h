@@ -365,6 +365,27 @@ int os2s_mx_quantize_rows(os2s_stream_t stream, const uint16_t* x, long long ldx
 int os2s_gemm_nt_mx(os2s_stream_t stream, const uint8_t* a, long long lda, const uint8_t* a_scale,
                     const uint8_t* w, const uint8_t* w_scale, void* out, long long ldc, int M, int N, int K,
                     const float* bias, int act, const uint16_t* residual, int out_f32);
+/* MXFP8 inference convolution (csrc/conv1d_mx.hip; a project extension behind the 'mxfp8_inference' parameter of
+ * TDNNEncoder). Forward-only replacement, in eval / infer mode, of tf.layers.conv1d(use_bias=False) +
+ * tf.layers.batch_normalization(training=False) + activation_fn in conv_bn_actv (parts/cnns/conv_blocks.py:195-232)
+ * and of the convolution of conv_actv (:17-58), stride 1:
+ *   y[b,t,co] = act(ch_scale[co] * sum_{k,ci} deq(xq)[b, t + k*dil - padL, ci] * deq(wq)[k,co,ci] + ch_shift[co])
+ *   y[b,t,:]  = 0 for t >= out_len[b] (out_len NULL: no mask)
+ * on the block-scaled MFMA, fp32 accumulation. xq [B,Tin,Cin] e4m3 / x_scale: os2s_mx_quantize_rows of the
+ * [B*Tin, Cin] view of the activation; wq [K,Cout,Cin] / w_scale: the same of the [K*Cout, Cin] view of the weights
+ * (scale layout above, rows = B*Tin / K*Cout). Input rows outside [0, in_len[b]) (in_len NULL: Tin) count as zeros
+ * whatever the buffers hold: padding and the fused sequence mask of os2s_conv1d_fwd. ch_scale / ch_shift fp32 [Cout]
+ * or NULL (1 / 0): os2s_bn_finalize(training = 0)'s scale / shift. act 0 or 1 (ReLU). y bf16, or fp32 with out_f32,
+ * strides in elements as in os2s_conv1d_fwd. There is no stride argument: strided layers keep bf16.
+ * OS2S_ERR_UNSUPPORTED: Cin < 64, Cin % 64 != 0, Cout % 8 != 0, (K-1)*dil > 64, act outside {0, 1}, a sample or
+ * weight tensor whose byte offsets do not fit 32 bits. OS2S_ERR_INVALID_ARG: a NULL operand, padL outside
+ * [0, (K-1)*dil], y strides that are no multiple of 8 (y_stride_t < Cout), a tensor pointer that is not 16-byte
+ * aligned (scales, lengths: 4-byte). */
+int os2s_conv1d_fwd_mx(os2s_stream_t stream, const uint8_t* xq, const uint8_t* x_scale, const uint8_t* wq,
+                       const uint8_t* w_scale, void* y, const int32_t* in_len, const int32_t* out_len,
+                       const float* ch_scale, const float* ch_shift, int B, int Tin, int Cin, int Cout, int K,
+                       int dil, int padL, int Tout, long long y_stride_b, long long y_stride_t, int out_f32,
+                       int act);
 int os2s_conv1d_fwd(os2s_stream_t stream, const uint16_t* x, const uint16_t* w,
                     void* y, const int32_t* in_len, const float* bias,
                     float* stats, int B, int Tin, int Cin, int Cout, int K,

@@ -31,6 +31,8 @@ UNIT_FLAGS = {
     # the same for the bias / residual adds of four adjacent columns in gemm_skinny_mx.hip's epilogue and the
     # clamp multiplies of its in-kernel quantiser
     "gemm_skinny_mx.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+    # conv1d_mx.hip: the per-channel scale / shift of eight adjacent columns in its epilogue
+    "conv1d_mx.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
 }
 
 

@@ -1220,6 +1220,37 @@ def gemm_nt_mx(a_q, a_scale, w_q, w_scale, out=None, bias=None, act=0, residual=
   return out
 
 
+MX_CONV_MAX_HALO = 64     # (K - 1) * dil of os2s_conv1d_fwd_mx: the slab of one 256-row tile in LDS
+
+
+def conv1d_fwd_mx(xq, x_scale, wq, w_scale, *, k, dil=1, pad_left=None, tout=None, in_len=None, out_len=None,
+                  ch_scale=None, ch_shift=None, act=0, out=None, out_f32=False):
+  """act(ch_scale * conv(deq(xq), deq(wq)) + ch_shift), rows at or past out_len zero, on the block-scaled MFMA
+  (os2s_conv1d_fwd_mx, stride 1). xq [B,Tin,Cin] e4m3 / x_scale: quantize_mx of the [B*Tin, Cin] view of the
+  activation; wq [K*Cout, Cin] / w_scale: quantize_mx of that view of the [K,Cout,Cin] weights. pad_left / tout
+  default to TF 'SAME'. -> [B,Tout,Cout] bf16, or fp32 with out_f32."""
+  B, Tin, Cin = xq.shape
+  KC, Cin2 = wq.shape
+  K = int(k)
+  assert Cin == Cin2 and KC % K == 0 and xq.dtype == torch.uint8 and wq.dtype == torch.uint8
+  Cout = KC // K
+  KT = (Cin + 127) // 128
+  assert tuple(x_scale.shape) == (KT, B * Tin, 4) and tuple(w_scale.shape) == (KT, KC, 4)
+  if pad_left is None or tout is None:
+    tout, pad_left = same_padding(Tin, K, 1, dil)
+  dt = torch.float32 if out_f32 else torch.bfloat16
+  if out is None:
+    out = torch.empty((B, tout, Cout), dtype=dt, device=xq.device)
+  assert tuple(out.shape) == (B, tout, Cout) and out.stride(2) == 1 and out.dtype == dt and out.is_cuda
+  _lib.C.os2s_conv1d_fwd_mx(_stream(), _ptr(xq, torch.uint8), _ptr(x_scale, torch.uint8), _ptr(wq, torch.uint8),
+                            _ptr(w_scale, torch.uint8), c_void_p(out.data_ptr()),
+                            _ptr(in_len, torch.int32, True), _ptr(out_len, torch.int32, True),
+                            _ptr(ch_scale, torch.float32, True), _ptr(ch_shift, torch.float32, True),
+                            B, Tin, Cin, Cout, K, int(dil), int(pad_left), int(tout), out.stride(0), out.stride(1),
+                            int(bool(out_f32)), int(act))
+  return out
+
+
 def dense_epilogue(y, bias=None, act=0, keep_prob=1.0, seed=0, residual=None):
   """In place: y = residual + dropout(act(y + bias)) on bf16 [rows, C]."""
   rows, C = y.shape

@@ -79,11 +79,7 @@ struct MxGemmArgs {
   int M, N, K, act, out_f32, NT, U;
 };
 
-constexpr int kMxTile = 256, kMxKTile = 128;
-constexpr int kMxOperand = kMxTile * kMxKTile;          // bytes of one operand tile
 constexpr int kMxStage = 2 * kMxOperand;                // A + W
-constexpr int kMxPatchStride = 68;                      // floats per row of a wave's epilogue patch
-constexpr int kMxPatch = 32 * kMxPatchStride * 4;       // bytes
 constexpr size_t kMxLds = 2 * kMxStage;                 // 128 KB (the 8 epilogue patches reuse 68 KB of it)
 
 __global__ __launch_bounds__(512, 1) void gemm_nt_mx_kernel(MxGemmArgs p) {
@@ -156,14 +152,7 @@ __global__ __launch_bounds__(512, 1) void gemm_nt_mx_kernel(MxGemmArgs p) {
     for (int h = 0; h < 2; ++h)
       foff[ks][h] = l31 * kMxKTile + (((ks * 4 + h * 2 + lhi) ^ ((l31 >> 1) & 7)) << 4);
   const int abase = wm * 128 * kMxKTile, wbase = kMxOperand + wn * 64 * kMxKTile;
-  auto frag = [&](const char* s, int ks) {
-    const u32x4 lo = *reinterpret_cast<const u32x4*>(s + foff[ks][0]);
-    const u32x4 hi = *reinterpret_cast<const u32x4*>(s + foff[ks][1]);
-    i32x8 f;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) { f[e] = (int)lo[e]; f[4 + e] = (int)hi[e]; }
-    return f;
-  };
+  auto frag = [&](const char* s, int ks) { return mx_frag(s, foff[ks][0], foff[ks][1]); };
 
   const int nkt = (p.K + kMxKTile - 1) / kMxKTile;
   const bool half_tail = (p.K & (kMxKTile - 1)) != 0;
@@ -216,12 +205,7 @@ __global__ __launch_bounds__(512, 1) void gemm_nt_mx_kernel(MxGemmArgs p) {
 #pragma unroll
   for (int im = 0; im < MI; ++im) {
 #pragma unroll
-    for (int in = 0; in < NI; ++in)
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const f32x4 v = {acc[in][im][4 * q], acc[in][im][4 * q + 1], acc[in][im][4 * q + 2], acc[in][im][4 * q + 3]};
-        *reinterpret_cast<f32x4*>(patch + l31 * kMxPatchStride + in * 32 + q * 8 + lhi * 4) = v;
-      }
+    for (int in = 0; in < NI; ++in) mx_acc_to_patch(patch, acc[in][im], in, l31, lhi);
     __builtin_amdgcn_wave_barrier();
 #pragma unroll
     for (int ps = 0; ps < 4; ++ps) {

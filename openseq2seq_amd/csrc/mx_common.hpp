@@ -1,5 +1,6 @@
-// Device helpers shared by the MXFP8 kernels (gemm_mx.hip, gemm_skinny_mx.hip): the quantisation of eight
-// elements under the format rule at the head of gemm_mx.hip, the buffer descriptor of the LDS DMA, the barrier.
+// Device helpers shared by the MXFP8 kernels (gemm_mx.hip, gemm_skinny_mx.hip, conv1d_mx.hip): the quantisation of
+// eight elements under the format rule at the head of gemm_mx.hip, the buffer descriptor of the LDS DMA, the
+// barrier, and the fragment read / epilogue patch of the 256 x 256 tile.
 #pragma once
 #include "os2s_common.hpp"
 
@@ -47,6 +48,33 @@ __device__ __forceinline__ void mx_barrier() {
   __builtin_amdgcn_sched_barrier(0);
   __builtin_amdgcn_s_barrier();
   __builtin_amdgcn_sched_barrier(0);
+}
+
+// ---- the 256 x 256 tile of gemm_mx.hip and conv1d_mx.hip (layout and swizzle: the head of gemm_mx.hip) ----
+constexpr int kMxTile = 256, kMxKTile = 128;
+constexpr int kMxOperand = kMxTile * kMxKTile;          // bytes of one operand tile
+constexpr int kMxPatchStride = 68;                      // floats per row of a wave's epilogue patch
+constexpr int kMxPatch = 32 * kMxPatchStride * 4;       // bytes
+
+// A lane's 32-byte fragment of one MFMA step: its two 16-byte pieces (scale block 0, scale block 1) at the byte
+// offsets off0 / off1 of a 32-row block in LDS.
+__device__ __forceinline__ i32x8 mx_frag(const char* s, int off0, int off1) {
+  const u32x4 lo = *reinterpret_cast<const u32x4*>(s + off0);
+  const u32x4 hi = *reinterpret_cast<const u32x4*>(s + off1);
+  i32x8 f;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) { f[e] = (int)lo[e]; f[4 + e] = (int)hi[e]; }
+  return f;
+}
+
+// One 32x32 accumulator block D[i][j] (i = output column = 8 (e / 4) + 4 (lane / 32) + e % 4, j = output row =
+// lane % 32) into columns 32 in .. 32 in + 31 of this wave's epilogue patch.
+__device__ __forceinline__ void mx_acc_to_patch(float* patch, const f32x16& a, int in, int l31, int lhi) {
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const f32x4 v = {a[4 * q], a[4 * q + 1], a[4 * q + 2], a[4 * q + 3]};
+    *reinterpret_cast<f32x4*>(patch + l31 * kMxPatchStride + in * 32 + q * 8 + lhi * 4) = v;
+  }
 }
 
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t mx_rsrc(const uint8_t* base, long long bytes) {

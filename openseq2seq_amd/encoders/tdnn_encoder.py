@@ -47,6 +47,11 @@ class TDNNEncoder(Encoder):
         'use_conv_mask': bool,
         'drop_block_prob': float,
         'drop_block_index': int,
+        # project extension (no reference counterpart), off by default: in eval / infer mode the stride-1 plain
+        # convolutions run on the MXFP8 kernel (csrc/conv1d_mx.hip): e4m3 operands with one power-of-two scale per
+        # 32 channels, eval BatchNorm + ReLU + mask in its epilogue (parts/cnns/conv_blocks.py::mx_conv_usable).
+        # Strided, separable and sample-norm layers, the 1x1 residual branches and training keep bf16.
+        'mxfp8_inference': bool,
     })
 
   def __init__(self, params, model, name="w2l_encoder", mode='train'):
@@ -128,6 +133,9 @@ class TDNNEncoder(Encoder):
         cin = blk['num_channels']
     self._layers = layers
     self.output_dim = cin
+    if p.get('mxfp8_inference', False) and self._mode != 'train':
+      for L in layers:
+        L['main'].mxfp8 = True
     # Dense-residual block ends without branch tensors (parts/cnns/dense_residual.py): every residual block is
     # dense, keeps the frame rate, and its branches are plain 1x1 conv + BatchNorm pairs over channel counts that
     # are multiples of 64; block dropping keeps the branch-by-branch path

@@ -18,6 +18,7 @@ from ... import capi
 from .. import streams, tape as _tape      # (`tape` is the Tape argument of every block function here)
 # compatibility: names that tests, tools and bench.py reach through this module (the same objects, not copies)
 from ..activations import act_id  # noqa: F401
+from ..dense import MxWeight
 from ..streams import join_side_streams, on_side_stream, set_side_stream_enabled, side_streams  # noqa: F401
 from ..tape import Act, Tape, accumulate_grad, backward_interleaved, current_tape, reshape_act  # noqa: F401
 
@@ -69,7 +70,17 @@ def glorot_uniform_conv(shape_dev):
 class ConvBN(object):
   """tf.layers.conv1d(use_bias=False) + tf.layers.batch_normalization: the pair of
   variables '<name>/kernel' and '<name>/bn/{gamma,beta,moving_mean,moving_variance}'
-  (conv_blocks.py:195-227; residual branches :78-99)."""
+  (conv_blocks.py:195-227; residual branches :78-99).
+
+  mxfp8 (set by the 'mxfp8_inference' parameter of TDNNEncoder): in an eval / infer pass without a tape the
+  convolution runs on the MXFP8 kernel (csrc/conv1d_mx.hip) where mx_conv_usable; everything else is bf16."""
+  mxfp8 = False
+
+  def mx_weight(self):
+    """(e4m3 bytes, scale words) of the [K*Cout, Cin] view of the kernel: the one MxWeight cache of this layer."""
+    if getattr(self, "_mx", None) is None:
+      self._mx = MxWeight()
+    return self._mx.get(self.kernel.store, self.kernel.w16.view(self.k * self.cout, self.cin))
 
   def __init__(self, store, name, bn_name, cin, cout, k, stride=1, dilation=1,
                padding="SAME", bn_momentum=0.9, bn_epsilon=1e-3, l2=0.0,
@@ -102,13 +113,16 @@ class ConvBN(object):
       return capi.same_padding(tin, self.k, self.stride, self.dil)
     return capi.valid_padding(tin, self.k, self.stride, self.dil)
 
-  def conv_bn_stats(self, x, training):
-    """Returns dict(y, scale, shift, mean, rstd, tout, pad_left)."""
+  def conv_bn_stats(self, x, training, mx=False):
+    """Returns dict(y, scale, shift, mean, rstd, tout, pad_left). mx (the caller checked mx_conv_usable): y comes
+    from the MXFP8 kernel with the identity epilogue — the main convolution of a residual block end."""
     B, Tin, _ = x.data.shape
     tout, pl = self.out_geometry(Tin)
     dev = x.data.device
     C = self.cout
     stats = None
+    if mx:
+      return self.bn_from_stats(mx_conv(self, x, tout, pl), None, B, tout, False, pl)
     if training:
       stats = torch.empty((capi.conv1d_num_mtiles(B, tout), 2, C), dtype=torch.float32,
                           device=dev)
@@ -202,6 +216,36 @@ class ConvBN(object):
       capi.conv1d_fwd(dy, wt16, dil=self.dil, pad_left=pl, tout=tin, out=g,
                       accumulate=inp.grad_init, out_len=inp.lens)
       inp.grad_init = True
+
+
+def mx_conv_wins(cin, cout, k):
+  """The by-shape rule of 'mxfp8_inference' on the speech encoders, from profiles/mxfp8_conv_first_measurements.md
+  (MI355X, the Jasper 10x5 stride-1 layers at B = 32): quantise + MXFP8 convolution with the fused epilogue took
+  0.71 - 0.85 x the time of the bf16 convolution + BatchNorm / activation pass at Cout <= 512 and at Cout 896 / 1024
+  (spread <= 1.5 %), but 1.12 - 1.23 x at the four layer classes with Cout 640 and 768 — the shapes with three
+  256-wide column tiles. That class keeps bf16; widths that were not measured follow the nearest measured class."""
+  return (cout + 255) // 256 != 3
+
+
+def mx_conv_usable(layer, x, act, training, tape):
+  """The calls the MXFP8 inference convolution takes (csrc/conv1d_mx.hip): the layer's switch is on, an eval / infer
+  pass without a tape, a plain convolution (ConvBN or ConvOnly itself: no separable, depthwise or sample-norm
+  layer) of stride 1 with a shape os2s_conv1d_fwd_mx has, ReLU or no activation, and a shape class at which the
+  kernel measured faster (mx_conv_wins). Every other call keeps the bf16 path."""
+  return layer.mxfp8 and not training and tape is None and type(layer) in (ConvBN, ConvOnly) and act in (0, 1) and \
+      layer.stride == 1 and layer.cin >= 64 and layer.cin % 64 == 0 and layer.cout % 8 == 0 and \
+      (layer.k - 1) * layer.dil <= capi.MX_CONV_MAX_HALO and x.data.is_contiguous() and \
+      mx_conv_wins(layer.cin, layer.cout, layer.k)
+
+
+def mx_conv(layer, x, tout, pl, scale=None, shift=None, act=0, out_len=None):
+  """act(scale * conv(x) + shift), masked to out_len, with both operands in MXFP8: the layer's cached weight copy,
+  the activation quantised here ONCE along the channels for all K taps."""
+  B, Tin, Cin = x.data.shape
+  wq, ws = layer.mx_weight()
+  xq, xs = capi.quantize_mx(x.data.view(B * Tin, Cin))
+  return capi.conv1d_fwd_mx(xq.view(B, Tin, Cin), xs, wq, ws, k=layer.k, dil=layer.dil, pad_left=pl, tout=tout,
+                            in_len=x.lens, out_len=out_len, ch_scale=scale, ch_shift=shift, act=act)
 
 
 def bn_vectors(C, dev, training):
@@ -421,7 +465,19 @@ def conv_bn_res_bn_actv(main, res_branches, x, res_inputs, out_lens, activation_
   act = act_id(activation_fn)
   branches = [main] + list(res_branches)
   inputs = [x] + list(res_inputs)
-  fw_main = main.conv_bn_stats(x, training)
+  mx = mx_conv_usable(main, x, act, training, tape)
+  if mx and not res_branches:
+    # 'mxfp8_inference', a plain layer: BatchNorm on moving statistics is a per-channel affine map and rides with
+    # the activation and the mask in the MXFP8 convolution's epilogue — ONE launch after the quantiser, no raw y
+    B, Tin, _ = x.data.shape
+    tout, pl = main.out_geometry(Tin)
+    sc, sh, _, _ = bn_vectors(main.cout, x.data.device, False)
+    capi.bn_finalize(None, B * tout, main.gamma.master, main.beta.master, main.eps, main.momentum, False,
+                     main.moving_mean, main.moving_var, None, None, sc, sh)
+    lens = out_lens if mask_output else None
+    return Act(mx_conv(main, x, tout, pl, sc, sh, act, lens), lens)
+  # (a block end: the main convolution on the MXFP8 kernel, its y into the bf16 BatchNorm sum below)
+  fw_main = main.conv_bn_stats(x, training, mx=True) if mx else main.conv_bn_stats(x, training)
   if res_fw is not None:         # launched earlier on the side stream (launch_residual_early)
     streams.join_side_streams()
     global _FWD_SIDE_BUSY
@@ -543,7 +599,10 @@ def conv_bn_dres_actv(main, x, dfw, out_lens, activation_fn, training, tape, kee
   the BatchNorm'd 1x1 branches, no branch tensor materialised). Backward hands the gradient at the sum to
   dense_residual.backward_end (side stream) and runs the main branch as conv_bn_res_bn_actv does."""
   act = act_id(activation_fn)
-  fw = main.conv_bn_stats(x, training)
+  if mx_conv_usable(main, x, act, training, tape):      # 'mxfp8_inference': as the block end of conv_bn_res_bn_actv
+    fw = main.conv_bn_stats(x, training, mx=True)
+  else:
+    fw = main.conv_bn_stats(x, training)
   streams.join_side_streams()
   global _FWD_SIDE_BUSY
   _FWD_SIDE_BUSY = False
@@ -719,6 +778,10 @@ def conv_actv(layer, x, out_lens, activation_fn, training, tape, keep_prob=1.0, 
   tout, pl = layer.out_geometry(Tin)
   dev = x.data.device
   C = layer.cout
+  if mx_conv_usable(layer, x, act, training, tape):
+    # 'mxfp8_inference': activation and mask in the MXFP8 convolution's epilogue, one launch after the quantiser
+    lens = out_lens if mask_output else None
+    return Act(mx_conv(layer, x, tout, pl, act=act, out_len=lens), lens)
   y = capi.conv1d_fwd(x.data, layer.kernel.w16, stride=layer.stride, dil=layer.dil, pad_left=pl, tout=tout,
                       in_len=x.lens)
   # conv_ln_actv / conv_in_actv: the per-sample normalisation sits between the convolution and the activation
