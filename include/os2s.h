@@ -386,6 +386,27 @@ int os2s_conv1d_fwd_mx(os2s_stream_t stream, const uint8_t* xq, const uint8_t* x
                        const float* ch_scale, const float* ch_shift, int B, int Tin, int Cin, int Cout, int K,
                        int dil, int padL, int Tout, long long y_stride_b, long long y_stride_t, int out_f32,
                        int act);
+/* MXFP8 inference separable convolution in one launch (csrc/sepconv1d_mx.hip; a project extension behind the
+ * 'mxfp8_inference' parameter of TDNNEncoder). Forward-only replacement, in eval / infer mode, of
+ * tf.layers.separable_conv1d(use_bias=False) + tf.layers.batch_normalization(training=False) + activation_fn of the
+ * "sep_conv1d" layers (parts/cnns/conv_blocks.py:11-16):
+ *   z[b,t,ci]  = bf16(sum_k x[b, t + k - padL, ci] * d[k,ci])      rows outside [0, in_len[b]) read as 0; fp32 sum
+ *   zq, zs     = the format rule of os2s_mx_quantize_rows applied to z along ci (blocks of 32)
+ *   y[b,t,co]  = act(ch_scale[co] * sum_ci deq(zq,zs)[b,t,ci] * deq(wq,w_scale)[co,ci] + ch_shift[co])
+ *   y[b,t,:]   = 0 for t >= out_len[b] (out_len NULL: no mask)
+ * x [B,Tin,Cin] bf16 (not quantised); d [K,Cin] fp32, the depthwise kernel os2s_depthwise_conv1d_fwd takes;
+ * wq [Cout,Cin] e4m3 / w_scale: os2s_mx_quantize_rows of the pointwise kernel (scale layout above, rows = Cout).
+ * z never reaches memory. ch_scale / ch_shift fp32 [Cout] or NULL (1 / 0); act 0 or 1 (ReLU); y bf16, or fp32 with
+ * out_f32, strides in elements as in os2s_conv1d_fwd_mx.
+ * OS2S_ERR_UNSUPPORTED: stride != 1, dil != 1, K > 96, Cin < 64, Cin % 64 != 0, Cin > 512, Cout % 8 != 0, act
+ * outside {0, 1}, a sample whose byte offsets do not fit 32 bits. OS2S_ERR_INVALID_ARG: a NULL operand, padL
+ * outside [0, K-1], y strides that are no multiple of 8 (y_stride_t < Cout), a tensor pointer that is not 16-byte
+ * aligned (d, scales, lengths: 4-byte). */
+int os2s_sepconv1d_fwd_mx(os2s_stream_t stream, const uint16_t* x, const float* d, const uint8_t* wq,
+                          const uint8_t* w_scale, void* y, const int32_t* in_len, const int32_t* out_len,
+                          const float* ch_scale, const float* ch_shift, int B, int Tin, int Cin, int Cout, int K,
+                          int stride, int dil, int padL, int Tout, long long y_stride_b, long long y_stride_t,
+                          int out_f32, int act);
 int os2s_conv1d_fwd(os2s_stream_t stream, const uint16_t* x, const uint16_t* w,
                     void* y, const int32_t* in_len, const float* bias,
                     float* stats, int B, int Tin, int Cin, int Cout, int K,

@@ -50,7 +50,10 @@ class TDNNEncoder(Encoder):
         # project extension (no reference counterpart), off by default: in eval / infer mode the stride-1 plain
         # convolutions run on the MXFP8 kernel (csrc/conv1d_mx.hip): e4m3 operands with one power-of-two scale per
         # 32 channels, eval BatchNorm + ReLU + mask in its epilogue (parts/cnns/conv_blocks.py::mx_conv_usable).
-        # Strided, separable and sample-norm layers, the 1x1 residual branches and training keep bf16.
+        # The stride-1, dilation-1 separable layers (K <= 96, Cin <= 512) run depthwise FIR, quantiser, pointwise GEMM
+        # and that epilogue in one launch (csrc/sepconv1d_mx.hip, ::mx_sep_usable; by the measured rule only plain
+        # layers with Cin < 384, the main branch of a residual block end keeps bf16). Strided, dilated-separable and
+        # sample-norm layers, the 1x1 residual branches (plain or folded separable) and training keep bf16.
         'mxfp8_inference': bool,
     })
 

@@ -248,6 +248,39 @@ def mx_conv(layer, x, tout, pl, scale=None, shift=None, act=0, out_len=None):
                             in_len=x.lens, out_len=out_len, ch_scale=scale, ch_shift=shift, act=act)
 
 
+def mx_sep_wins(cin, cout, k, block_end=False):
+  """The by-shape rule of 'mxfp8_inference' on the separable layers, from
+  profiles/mxfp8_sepconv_first_measurements.md (MI355X, the QuartzNet 15x5 stride-1 layer classes at B = 32):
+  bn_finalize + the fused launch took 0.79 - 0.82 x the time of the bf16 chain of four launches at Cin 256 (K 33, 39,
+  and the 256 -> 512 layer with K 51; spread <= 1 %), but 1.09 - 1.30 x at Cin 512 (K 51, 63, 75): the register-window
+  FIR of phase 1 grows with Cin K and is up to half of the launch there. Cin 512 keeps bf16. Only the widths 256 and
+  512 were measured: the boundary at 384 is the midpoint between them and nothing more, and cout and k do not enter
+  because no measured class turned on them.
+  block_end: the main branch of a residual block end, where the fused launch has the identity epilogue and the
+  BatchNorm / residual sum stays a launch of its own. That chain took 1.07 - 1.10 x the bf16 chain's time at Cin 256
+  and 1.29 - 1.49 x at Cin 512: block ends keep bf16 at every width."""
+  return cin < 384 and not block_end
+
+
+def mx_sep_usable(layer, x, act, training, tape, block_end=False):
+  """The calls the fused MXFP8 separable convolution takes (csrc/sepconv1d_mx.hip): the layer's switch is on, an eval
+  / infer pass without a tape, a SepConvBN itself that is not a folded one-tap layer, ReLU or no activation, a shape
+  os2s_sepconv1d_fwd_mx has (stride 1, dilation 1, K <= 96, Cin a multiple of 64 up to 512, Cout a multiple of 8)
+  and a shape class at which the kernel measured faster (mx_sep_wins). Every other call keeps the bf16 chain."""
+  return layer.mxfp8 and not training and tape is None and type(layer) is SepConvBN and not layer.folded() and \
+      act in (0, 1) and layer.stride == 1 and layer.dil == 1 and layer.k <= capi.MX_SEP_MAX_K and \
+      layer.cin % 64 == 0 and 64 <= layer.cin <= capi.MX_SEP_MAX_CIN and layer.cout % 8 == 0 and \
+      x.data.is_contiguous() and mx_sep_wins(layer.cin, layer.cout, layer.k, block_end)
+
+
+def mx_sep_conv(layer, x, tout, pl, scale=None, shift=None, act=0, out_len=None):
+  """act(scale * pointwise(mx(depthwise(x))) + shift), masked to out_len, in ONE launch: the depthwise output is
+  quantised in the kernel, the pointwise kernel is the layer's cached MXFP8 copy."""
+  wq, ws = layer.mx_weight()
+  return capi.sepconv1d_fwd_mx(x.data, layer.depthwise.master, wq, ws, pad_left=pl, tout=tout, in_len=x.lens,
+                               out_len=out_len, ch_scale=scale, ch_shift=shift, act=act)
+
+
 def bn_vectors(C, dev, training):
   """scale, shift (and mean, rstd in training) of one BatchNorm: rows of ONE allocation (an allocation is 1.4 us of
   the Python thread, four of them per layer were 0.4 ms of a QuartzNet step)."""
@@ -276,12 +309,26 @@ class SepConvBN(ConvBN):
     self.kernel = store.add(name + "/pointwise_kernel", (1, cout, cin), initializer, kind="conv", l2=l2)
     self._add_bn(store, bn_name, cout, l2)
 
-  def conv_bn_stats(self, x, training):
+  def mx_weight(self):
+    """(e4m3 bytes, scale words) of the [Cout, Cin] pointwise kernel: the one MxWeight cache of this layer."""
+    if getattr(self, "_mx", None) is None:
+      self._mx = MxWeight()
+    return self._mx.get(self.kernel.store, self.kernel.w16.view(self.cout, self.cin))
+
+  def conv_bn_stats(self, x, training, mx=False, out_len=None):
+    """mx (the caller checked mx_sep_usable): y comes from the fused MXFP8 kernel with the identity epilogue — the
+    main convolution of a residual block end. out_len: the lengths the caller's BatchNorm sum masks its output to;
+    the kernel then skips the row tiles past a sample's end (rows at or past the length come out as zeros, and the
+    masked sum does not depend on them), as the bf16 depthwise kernel does."""
     B, Tin, _ = x.data.shape
     tout, pl = self.out_geometry(Tin)
     dev = x.data.device
     C = self.cout
     stats = None
+    if mx:
+      d = self.bn_from_stats(mx_sep_conv(self, x, tout, pl, out_len=out_len), None, B, tout, False, pl)
+      d["z"] = d["wt_eff"] = None
+      return d
     if training:
       stats = torch.empty((capi.conv1d_num_mtiles(B, tout), 2, C), dtype=torch.float32, device=dev)
     wt_eff = None
@@ -465,19 +512,24 @@ def conv_bn_res_bn_actv(main, res_branches, x, res_inputs, out_lens, activation_
   act = act_id(activation_fn)
   branches = [main] + list(res_branches)
   inputs = [x] + list(res_inputs)
-  mx = mx_conv_usable(main, x, act, training, tape)
+  mx_sep = mx_sep_usable(main, x, act, training, tape, block_end=bool(res_branches))
+  mx = mx_sep or mx_conv_usable(main, x, act, training, tape)
   if mx and not res_branches:
     # 'mxfp8_inference', a plain layer: BatchNorm on moving statistics is a per-channel affine map and rides with
     # the activation and the mask in the MXFP8 convolution's epilogue — ONE launch after the quantiser, no raw y
+    # (a separable layer: ONE launch in all, the quantiser sits between the two halves inside the kernel)
     B, Tin, _ = x.data.shape
     tout, pl = main.out_geometry(Tin)
     sc, sh, _, _ = bn_vectors(main.cout, x.data.device, False)
     capi.bn_finalize(None, B * tout, main.gamma.master, main.beta.master, main.eps, main.momentum, False,
                      main.moving_mean, main.moving_var, None, None, sc, sh)
     lens = out_lens if mask_output else None
-    return Act(mx_conv(main, x, tout, pl, sc, sh, act, lens), lens)
+    return Act((mx_sep_conv if mx_sep else mx_conv)(main, x, tout, pl, sc, sh, act, lens), lens)
   # (a block end: the main convolution on the MXFP8 kernel, its y into the bf16 BatchNorm sum below)
-  fw_main = main.conv_bn_stats(x, training, mx=True) if mx else main.conv_bn_stats(x, training)
+  if mx_sep:
+    fw_main = main.conv_bn_stats(x, training, mx=True, out_len=out_lens if mask_output else None)
+  else:
+    fw_main = main.conv_bn_stats(x, training, mx=True) if mx else main.conv_bn_stats(x, training)
   if res_fw is not None:         # launched earlier on the side stream (launch_residual_early)
     streams.join_side_streams()
     global _FWD_SIDE_BUSY
