@@ -407,6 +407,37 @@ int os2s_sepconv1d_fwd_mx(os2s_stream_t stream, const uint16_t* x, const float* 
                           const float* ch_scale, const float* ch_shift, int B, int Tin, int Cin, int Cout, int K,
                           int stride, int dil, int padL, int Tout, long long y_stride_b, long long y_stride_t,
                           int out_f32, int act);
+/* MXFP8 residual block end in one launch (csrc/conv1d_block_end_mx.hip; a project extension behind the
+ * 'mxfp8_inference' parameter of TDNNEncoder). Forward-only replacement, in eval / infer mode, of the whole of
+ * conv_bn_res_bn_actv (parts/cnns/conv_blocks.py:61-168): the main tf.layers.conv1d, one tf.layers.conv1d(kernel_size=1)
+ * per residual input, their tf.layers.batch_normalization(training=False), the sum and activation_fn:
+ *   y[b,t,co] = act(sum_{k,ci} deq(xq)[b, t + k*dil - padL, ci] * deq(wq)[k,co,ci]
+ *                   + sum_{r<R} sum_ci deq(src[r].sq)[b,t,ci] * deq(src[r].vq)[co,ci] + ch_shift[co])
+ *   y[b,t,:]  = 0 for t >= out_len[b] (out_len NULL: no mask)
+ * one fp32 accumulation on the block-scaled MFMA: first the main convolution's (channel tile, tap) steps in the order
+ * of os2s_conv1d_fwd_mx (R = 0 gives that entry's bits with ch_scale NULL), then each source's channel tiles as
+ * one-tap steps. xq / x_scale / wq / w_scale, in_len, y, out_f32, strides and act as in os2s_conv1d_fwd_mx. There is
+ * no per-channel scale: the caller folds every branch's BatchNorm scale into the rows of that branch's weights before
+ * quantising them, and ch_shift (fp32 [Cout] or NULL) is the sum of the branches' shifts. `src` is a HOST array of R
+ * sources (copied into the launch; NULL with R = 0): sq [B,Tout,C] e4m3 / s_scale: os2s_mx_quantize_rows of the
+ * [B*Tout, C] view of residual input r; vq [Cout,C] / v_scale: the same of its 1x1 kernel (rows = B*Tout / Cout). Source
+ * rows at or past out_len[b] count as zeros whatever the buffer holds (they only reach output rows that are zero).
+ * `variant` (trailing, for tests and tools): -1 = the one kernel there is; anything else is OS2S_ERR_INVALID_ARG.
+ * OS2S_ERR_UNSUPPORTED: every limit of os2s_conv1d_fwd_mx, R > 16, a source with C < 64 or C % 64 != 0, a source
+ * whose byte offsets do not fit 32 bits. OS2S_ERR_INVALID_ARG: as os2s_conv1d_fwd_mx; R < 0, src NULL with R > 0, a
+ * NULL or misaligned pointer in a source (tensors 16-byte, scales 4-byte). */
+typedef struct {
+  const uint8_t* sq;        /* [B, Tout, C] e4m3 */
+  const uint8_t* s_scale;   /* [ceil(C/128)][B*Tout] words */
+  const uint8_t* vq;        /* [Cout, C] e4m3, BatchNorm scale folded in */
+  const uint8_t* v_scale;   /* [ceil(C/128)][Cout] words */
+  int C;
+} os2s_mx_res_src_t;
+int os2s_conv1d_block_end_fwd_mx(os2s_stream_t stream, const uint8_t* xq, const uint8_t* x_scale, const uint8_t* wq,
+                                 const uint8_t* w_scale, const os2s_mx_res_src_t* src, int R, void* y,
+                                 const int32_t* in_len, const int32_t* out_len, const float* ch_shift, int B, int Tin,
+                                 int Cin, int Cout, int K, int dil, int padL, int Tout, long long y_stride_b,
+                                 long long y_stride_t, int out_f32, int act, int variant);
 int os2s_conv1d_fwd(os2s_stream_t stream, const uint16_t* x, const uint16_t* w,
                     void* y, const int32_t* in_len, const float* bias,
                     float* stats, int B, int Tin, int Cin, int Cout, int K,

@@ -369,6 +369,7 @@ def dres_seg_table(segs, device):
 
 
 def dres_bn_fwd(table, nseg, Cout, Kk, wp, shift, count, eps, momentum, training):
+  _note_moving_stats(training)
   assert wp.numel() == Cout * Kk and shift.numel() == Cout and table.numel() == nseg * _lib.ctypes.sizeof(_DresSeg)
   _lib.C.os2s_dres_bn_fwd(_stream(), _ptr(table, torch.uint8), nseg, Cout, Kk, _ptr(wp, torch.bfloat16),
                           _ptr(shift, torch.float32), int(count), float(eps), float(momentum), int(bool(training)))
@@ -519,8 +520,23 @@ def _ptr_array(tensors, dtype):
   return arr
 
 
+_MOVING_STATS_EPOCH = [0]
+
+
+def _note_moving_stats(training):
+  """A training-mode BatchNorm finalize writes moving statistics from a kernel, which no tensor version counter sees:
+  caches derived from them (the folded MXFP8 block-end weights) compare moving_stats_epoch()."""
+  if training:
+    _MOVING_STATS_EPOCH[0] += 1
+
+
+def moving_stats_epoch():
+  return _MOVING_STATS_EPOCH[0]
+
+
 def bn_finalize(partial, count, gamma, beta, eps, momentum, training, moving_mean,
                 moving_var, mean_out, rstd_out, scale_out, shift_out):
+  _note_moving_stats(training)
   C = scale_out.numel()
   nparts = 0 if partial is None else partial.shape[0]
   _lib.C.os2s_bn_finalize(_stream(), _ptr(partial, torch.float32, True), nparts, C, int(count),
@@ -534,6 +550,7 @@ def bn_finalize(partial, count, gamma, beta, eps, momentum, training, moving_mea
 def bn_finalize_multi(items, count, eps, momentum, training):
   """items: list (<= 16) of dict(partial, gamma, beta, moving_mean, moving_var, mean_out, rstd_out,
   scale_out, shift_out) of one geometry — os2s_bn_finalize for all of them in one launch."""
+  _note_moving_stats(training)
   J = len(items)
   C = items[0]["scale_out"].numel()
   nparts = 0 if items[0]["partial"] is None else items[0]["partial"].shape[0]
@@ -1251,7 +1268,51 @@ def conv1d_fwd_mx(xq, x_scale, wq, w_scale, *, k, dil=1, pad_left=None, tout=Non
   return out
 
 
-MX_SEP_MAX_K, MX_SEP_MAX_CIN = 96, 512     # os2s_sepconv1d_fwd_mx: the register-window FIR's slab, the zq tile in LDS
+class _MxResSrc(_lib.ctypes.Structure):
+  _fields_ = [("sq", c_void_p), ("s_scale", c_void_p), ("vq", c_void_p), ("v_scale", c_void_p), ("C", c_int)]
+
+
+MX_END_MAX_SOURCES = 16   # residual sources of one os2s_conv1d_block_end_fwd_mx launch
+
+
+def conv1d_block_end_fwd_mx(xq, x_scale, wq, w_scale, sources, *, k, dil=1, pad_left=None, tout=None, in_len=None,
+                            out_len=None, ch_shift=None, act=0, out=None, out_f32=False, variant=-1):
+  """act(conv(deq(xq), deq(wq)) + sum_r deq(sq_r) . deq(vq_r)^T + ch_shift), rows at or past out_len zero, in ONE
+  launch on the block-scaled MFMA (os2s_conv1d_block_end_fwd_mx): a residual block end whose BatchNorm scales are
+  folded into the weight rows. xq / x_scale / wq / w_scale as conv1d_fwd_mx; sources: up to 16 tuples
+  (sq [B,Tout,C] e4m3, s_scale, vq [Cout,C] e4m3, v_scale), each pair from quantize_mx of the [B*Tout, C] view of a
+  residual input and of its 1x1 kernel. -> [B,Tout,Cout] bf16, or fp32 with out_f32."""
+  B, Tin, Cin = xq.shape
+  KC, Cin2 = wq.shape
+  K = int(k)
+  assert Cin == Cin2 and KC % K == 0 and xq.dtype == torch.uint8 and wq.dtype == torch.uint8
+  Cout = KC // K
+  KT = (Cin + 127) // 128
+  assert tuple(x_scale.shape) == (KT, B * Tin, 4) and tuple(w_scale.shape) == (KT, KC, 4)
+  if pad_left is None or tout is None:
+    tout, pad_left = same_padding(Tin, K, 1, dil)
+  arr = (_MxResSrc * max(len(sources), 1))()
+  for g, (sq, ss, vq, vs) in zip(arr, sources):
+    C = sq.shape[2]
+    assert tuple(sq.shape) == (B, tout, C) and tuple(vq.shape) == (Cout, C) and sq.is_contiguous() and \
+        vq.is_contiguous() and tuple(ss.shape) == ((C + 127) // 128, B * tout, 4) and \
+        tuple(vs.shape) == ((C + 127) // 128, Cout, 4)
+    g.sq, g.s_scale, g.vq, g.v_scale, g.C = _ptr(sq, torch.uint8), _ptr(ss, torch.uint8), _ptr(vq, torch.uint8), \
+        _ptr(vs, torch.uint8), C
+  dt = torch.float32 if out_f32 else torch.bfloat16
+  if out is None:
+    out = torch.empty((B, tout, Cout), dtype=dt, device=xq.device)
+  assert tuple(out.shape) == (B, tout, Cout) and out.stride(2) == 1 and out.dtype == dt and out.is_cuda
+  _lib.C.os2s_conv1d_block_end_fwd_mx(_stream(), _ptr(xq, torch.uint8), _ptr(x_scale, torch.uint8),
+                                      _ptr(wq, torch.uint8), _ptr(w_scale, torch.uint8), arr, len(sources),
+                                      c_void_p(out.data_ptr()), _ptr(in_len, torch.int32, True),
+                                      _ptr(out_len, torch.int32, True), _ptr(ch_shift, torch.float32, True),
+                                      B, Tin, Cin, Cout, K, int(dil), int(pad_left), int(tout), out.stride(0),
+                                      out.stride(1), int(bool(out_f32)), int(act), int(variant))
+  return out
+
+
+MX_SEP_MAX_K, MX_SEP_MAX_CIN = 96, 512    # os2s_sepconv1d_fwd_mx: the register-window FIR's slab, the zq tile in LDS
 
 
 def sepconv1d_fwd_mx(x, d, wq, w_scale, *, pad_left=None, tout=None, in_len=None, out_len=None, ch_scale=None,

@@ -16,7 +16,7 @@ import os
 
 from ..parts.cnns.conv_blocks import (ConvBN, ConvOnly, ConvSampleNorm, SepConvBN, conv_actv, conv_bn_res_bn_actv,
                                       xavier_normal_conv, glorot_uniform_conv, launch_residual_early,
-                                      launch_dense_residual, conv_bn_dres_actv)
+                                      launch_dense_residual, conv_bn_dres_actv, act_id, mx_block_end_planned)
 from ..parts.tape import Act
 from ..parts.cnns.dense_residual import DenseResidualPlan
 
@@ -191,6 +191,18 @@ class TDNNEncoder(Encoder):
       if self._dres_plan is False:
         self._dres_plan = DenseResidualPlan(self._dres_ends, x.data.device)
       dpass = self._dres_plan.begin(training)
+    # 'mxfp8_inference': a block end that runs as one fused MXFP8 launch (conv_blocks.mx_block_end_planned) reads its
+    # residual inputs itself — nothing of it is started on the side stream. dres_last: the last dense-residual end
+    # that still goes through the dense-residual pass (sources past it are not copied into the pass)
+    act = act_id(act_fn)
+    fused = [bool(L['res']) and mx_block_end_planned(
+        L['main'], L['res'], act, training, tape,
+        dropped=self.params.get('drop_block_prob', 0.0) > 0 and self.params.get('drop_block_index', -1) == L['block'])
+             for L in self._layers]
+    ends = [li for li, L in enumerate(self._layers) if L['res']]
+    dres_last = max([k for k, li in enumerate(ends) if not fused[li]], default=-1)
+    if dres_last < 0:
+      dpass = None
     hint_stale = host_len is not None
     nl = len(self._layers)
     for li, L in enumerate(self._layers):
@@ -202,8 +214,9 @@ class TDNNEncoder(Encoder):
         if blk.get('residual_dense', False):
           residual_aggregation.append(x)
           layer_res = list(residual_aggregation)
-          if dpass is not None:
-            pending_dres = launch_dense_residual(dpass, len(residual_aggregation) - 1, x)
+          k = len(residual_aggregation) - 1
+          if dpass is not None and k <= dres_last:
+            pending_dres = launch_dense_residual(dpass, k, x, end=not fused[li + blk['repeat'] - 1])
         else:
           layer_res = [x]
       s = blk['stride'][0]
@@ -226,7 +239,7 @@ class TDNNEncoder(Encoder):
       if dpass is None and blk.get('residual', False) and blk['repeat'] > 1 and s == 1 and \
          L['rep'] == min(RES_EARLY_REP, blk['repeat'] - 2) and RES_EARLY_REP >= 0:
         end = self._layers[li + blk['repeat'] - 1 - L['rep']]
-        if end['res'] and len(end['res']) >= 2:
+        if end['res'] and len(end['res']) >= 2 and not fused[li + blk['repeat'] - 1 - L['rep']]:
           pending_res = launch_residual_early(end['res'], layer_res, training)
       res_fw = None
       if L['res']:

@@ -82,6 +82,23 @@ class ConvBN(object):
       self._mx = MxWeight()
     return self._mx.get(self.kernel.store, self.kernel.w16.view(self.k * self.cout, self.cin))
 
+  def mx_folded(self):
+    """(e4m3 bytes, scale words, shift, key) of this layer as a branch of an MXFP8 block end: the [K*Cout, Cin] view
+    of the kernel with row (k, co) scaled in fp32 by the eval BatchNorm's gamma / sqrt(moving_var + eps), rounded to
+    bf16 and quantised; shift = beta - moving_mean * that scale. A second cached copy next to mx_weight's. key: what
+    the copy was made from — the store's version counter (kernel, gamma, beta: optimizer step, checkpoint load), the
+    tensor versions of the moving statistics (in-place writes through torch) and capi.moving_stats_epoch() (writes by
+    a training-mode BatchNorm kernel, which no tensor version sees)."""
+    key = (getattr(self.kernel.store, "version", None), self.moving_mean._version, self.moving_var._version,
+           capi.moving_stats_epoch())
+    c = getattr(self, "_mx_fold", None)
+    if c is None or key[0] is None or c[3] != key:
+      scale = self.gamma.master.float() / torch.sqrt(self.moving_var + self.eps)
+      w = (self.kernel.w16.float() * scale[None, :, None]).to(torch.bfloat16).view(self.k * self.cout, self.cin)
+      q, s = capi.quantize_mx(w, *(c[:2] if c is not None else ()))
+      c = self._mx_fold = (q, s, self.beta.master.float() - self.moving_mean * scale, key)
+    return c
+
   def __init__(self, store, name, bn_name, cin, cout, k, stride=1, dilation=1,
                padding="SAME", bn_momentum=0.9, bn_epsilon=1e-3, l2=0.0,
                initializer=xavier_normal_conv):
@@ -232,20 +249,75 @@ def mx_conv_usable(layer, x, act, training, tape):
   pass without a tape, a plain convolution (ConvBN or ConvOnly itself: no separable, depthwise or sample-norm
   layer) of stride 1 with a shape os2s_conv1d_fwd_mx has, ReLU or no activation, and a shape class at which the
   kernel measured faster (mx_conv_wins). Every other call keeps the bf16 path."""
+  return _mx_conv_takes(layer, act, training, tape) and x.data.is_contiguous() and \
+      mx_conv_wins(layer.cin, layer.cout, layer.k)
+
+
+def _mx_conv_takes(layer, act, training, tape):
+  """mx_conv_usable without the tensor and without the by-shape rule: what is known when the encoder is built."""
   return layer.mxfp8 and not training and tape is None and type(layer) in (ConvBN, ConvOnly) and act in (0, 1) and \
       layer.stride == 1 and layer.cin >= 64 and layer.cin % 64 == 0 and layer.cout % 8 == 0 and \
-      (layer.k - 1) * layer.dil <= capi.MX_CONV_MAX_HALO and x.data.is_contiguous() and \
-      mx_conv_wins(layer.cin, layer.cout, layer.k)
+      (layer.k - 1) * layer.dil <= capi.MX_CONV_MAX_HALO
+
+
+def mx_quantized(x):
+  """(e4m3 bytes [B,T,C], scale words) of an Act, quantised once per pass and kept on it: a block input is the first
+  layer's input and a residual source of every later block end."""
+  if x.mx is None:
+    B, T, C = x.data.shape
+    xq, xs = capi.quantize_mx(x.data.view(B * T, C))
+    x.mx = (xq.view(B, T, C), xs)
+  return x.mx
 
 
 def mx_conv(layer, x, tout, pl, scale=None, shift=None, act=0, out_len=None):
   """act(scale * conv(x) + shift), masked to out_len, with both operands in MXFP8: the layer's cached weight copy,
-  the activation quantised here ONCE along the channels for all K taps."""
-  B, Tin, Cin = x.data.shape
+  the activation quantised ONCE along the channels for all K taps (and for every later use: mx_quantized)."""
   wq, ws = layer.mx_weight()
-  xq, xs = capi.quantize_mx(x.data.view(B * Tin, Cin))
-  return capi.conv1d_fwd_mx(xq.view(B, Tin, Cin), xs, wq, ws, k=layer.k, dil=layer.dil, pad_left=pl, tout=tout,
+  xq, xs = mx_quantized(x)
+  return capi.conv1d_fwd_mx(xq, xs, wq, ws, k=layer.k, dil=layer.dil, pad_left=pl, tout=tout,
                             in_len=x.lens, out_len=out_len, ch_scale=scale, ch_shift=shift, act=act)
+
+
+def mx_block_end_wins(cout, k, sources):
+  """The by-shape rule of the fused MXFP8 block end (csrc/conv1d_block_end_mx.hip), from
+  profiles/mxfp8_block_end_first_measurements.md (MI355X, the ten dense-residual block ends of Jasper 10x5 in eval
+  mode at B = 32, T = 808 ragged). sources: the channel counts of the residual inputs. Quantise + the fused launch
+  took 0.66 - 0.86 x the time of the faster of the bf16 block end and the block end with only its main convolution in
+  MXFP8 at Cout 256, 384 and 512 (K 11 - 17, 1 - 6 sources; 0.73 - 0.86 x with the newest source's quantiser counted
+  too; spread <= 1.7 %), but 1.18 - 1.27 x at Cout 640 and 768 (K 21, 25, 7 - 10 sources; spread <= 2.2 %): the
+  classes with three 256-wide column tiles, where the plain MXFP8 convolution loses as well (mx_conv_wins). Those keep
+  today's path. Neither K nor the sources turned a class: the residual steps are 8 - 19 % of a launch's steps. Widths
+  that were not measured follow the column-tile count, as there."""
+  return (cout + 255) // 256 != 3
+
+
+def mx_block_end_planned(main, res_branches, act, training, tape, dropped=False):
+  """A residual block end that runs as ONE launch of os2s_conv1d_block_end_fwd_mx, as far as the layers tell (the
+  encoder asks this before it would start the end's residual branches on the side stream): the switch is on, an eval
+  / infer pass without a tape, the main branch a plain stride-1 ConvBN the kernel has, every residual branch a plain
+  1x1 ConvBN on a multiple of 64 channels, at most 16 of them, ReLU or no activation, the block not dropped, and a
+  shape class at which the launch measured faster (mx_block_end_wins)."""
+  return bool(res_branches) and not dropped and type(main) is ConvBN and _mx_conv_takes(main, act, training, tape) and \
+      len(res_branches) <= capi.MX_END_MAX_SOURCES and \
+      all(_is_plain_1x1(br) and br.cin >= 64 and br.cin % 64 == 0 and br.cout == main.cout for br in res_branches) and \
+      mx_block_end_wins(main.cout, main.k, [br.cin for br in res_branches])
+
+
+def mx_block_end(main, res_branches, x, res_inputs, tout, pl, act, out_len):
+  """act(BN(conv(x)) + sum_i BN_i(conv1x1_i(res_i))), masked to out_len, in one launch: every branch's folded weight
+  copy (ConvBN.mx_folded), the summed shift cached on the main layer under the branches' keys, every activation's
+  MXFP8 copy made at most once per pass (mx_quantized). In the steady state: the quantiser of x, of the sources nobody
+  quantised yet, and the launch."""
+  folded = [br.mx_folded() for br in [main] + list(res_branches)]
+  keys = tuple((id(br), f[3]) for br, f in zip([main] + list(res_branches), folded))
+  c = getattr(main, "_mx_end_shift", None)
+  if c is None or c[0] != keys:
+    c = main._mx_end_shift = (keys, torch.stack([f[2] for f in folded]).sum(0).contiguous())
+  xq, xs = mx_quantized(x)
+  sources = [mx_quantized(r) + f[:2] for r, f in zip(res_inputs, folded[1:])]
+  return capi.conv1d_block_end_fwd_mx(xq, xs, folded[0][0], folded[0][1], sources, k=main.k, dil=main.dil, pad_left=pl,
+                                      tout=tout, in_len=x.lens, out_len=out_len, ch_shift=c[1], act=act)
 
 
 def mx_sep_wins(cin, cout, k, block_end=False):
@@ -525,7 +597,17 @@ def conv_bn_res_bn_actv(main, res_branches, x, res_inputs, out_lens, activation_
                      main.moving_mean, main.moving_var, None, None, sc, sh)
     lens = out_lens if mask_output else None
     return Act((mx_sep_conv if mx_sep else mx_conv)(main, x, tout, pl, sc, sh, act, lens), lens)
-  # (a block end: the main convolution on the MXFP8 kernel, its y into the bf16 BatchNorm sum below)
+  if res_fw is None and mx_block_end_planned(main, res_branches, act, training, tape,
+                                             dropped=drop_block_prob > 0 and bool(drop_block)):
+    # 'mxfp8_inference', a block end: main convolution, residual branches, their BatchNorms, the sum, the activation
+    # and the mask are ONE accumulation in one launch (the sources must have the output's rows)
+    B, Tin, _ = x.data.shape
+    tout, pl = main.out_geometry(Tin)
+    if x.data.is_contiguous() and all(tuple(r.data.shape[:2]) == (B, tout) and r.data.is_contiguous()
+                                      for r in res_inputs):
+      lens = out_lens if mask_output else None
+      return Act(mx_block_end(main, res_branches, x, res_inputs, tout, pl, act, lens), lens)
+  # (any other block end: the main convolution on the MXFP8 kernel, its y into the bf16 BatchNorm sum below)
   if mx_sep:
     fw_main = main.conv_bn_stats(x, training, mx=True, out_len=out_lens if mask_output else None)
   else:
@@ -628,17 +710,20 @@ def conv_bn_res_bn_actv(main, res_branches, x, res_inputs, out_lens, activation_
   return result
 
 
-def launch_dense_residual(dpass, k, x):
+def launch_dense_residual(dpass, k, x, end=True):
   """Registers block k's input `x` as source k of the dense-residual pass and evaluates block end k's residual
   sum — it depends on the block INPUTS only — on the side stream, next to the block's own layers. Returns the
-  record conv_bn_dres_actv consumes (it joins the side stream first)."""
+  record conv_bn_dres_actv consumes (it joins the side stream first). end=False (block end k runs as the fused MXFP8
+  launch, a later one does not): the source only, returns None."""
   if not DRES_FWD_SIDE or streams._side_stream(x.data.device, 1) is None:
     dpass.add_source(x)
-    return dpass.forward_end(k)
+    return dpass.forward_end(k) if end else None
   global _FWD_SIDE_BUSY
   _FWD_SIDE_BUSY = True
   with on_side_stream(x.data.device, x.data, which=1) as ctx:
     dpass.add_source(x)
+    if not end:
+      return None
     fw = dpass.forward_end(k)
     ctx.hand_over(fw["y"])
   return fw

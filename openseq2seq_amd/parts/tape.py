@@ -233,10 +233,12 @@ def current_tape():
 class Act(object):
   """An activation tensor + its valid lengths + (optionally) its gradient."""
   __slots__ = ("data", "lens", "grad", "grad_init", "requires_grad", "res_grad", "mask_scale",
-               "grad_masked", "bias_part", "bn_y", "bn_scale", "grad_event", "bn_full_rows")
+               "grad_masked", "bias_part", "bn_y", "bn_scale", "grad_event", "bn_full_rows", "mx")
 
   def __init__(self, data, lens=None, requires_grad=True):
     self.data, self.lens = data, lens
+    # (e4m3 bytes, scale words) of data, made by the first MXFP8 inference consumer (conv_blocks.mx_quantized)
+    self.mx = None
     self.grad, self.grad_init = None, False
     self.requires_grad = requires_grad
     self.res_grad = None   # gradient arriving through a residual connection (pre-norm blocks)

@@ -56,11 +56,93 @@ def window(fn, n):
   return e0.elapsed_time(e1) / n
 
 
+def block_ends(args, dev, B, T, lens_h, lens):
+  """--block-ends: the ten dense-residual block ends of Jasper 10x5 in eval mode (end k: Cout x Cout x K main
+  convolution + k + 1 residual 1x1 branches), three chains as the layers issue them, alternated in one process:
+
+    bf16:   os2s_conv1d_fwd + bn_finalize, the dense-residual end (dres_bn_fwd + the concatenated 1x1 GEMM), bn_act_fwd
+    mx:     the same with the main convolution on os2s_conv1d_fwd_mx (identity epilogue) where mx_conv_wins — the block
+            end of 'mxfp8_inference' before the fused launch; equal to bf16 where that rule keeps bf16
+    fused:  quantise x + os2s_conv1d_block_end_fwd_mx; fused+src: the same plus the quantiser of the newest source
+            (the block's input, when the block's first layer kept bf16 and did not leave its MXFP8 copy)
+
+  The source copies of the dense-residual pass (one per source and pass, shared by all ends) are not timed, and the
+  dense-residual end runs on the timing stream, not next to the block's layers: both favour bf16 / mx."""
+  from openseq2seq_amd.optimizers.flat_params import FlatParams
+  from openseq2seq_amd.parts.cnns import conv_blocks as cb
+  from openseq2seq_amd.parts.cnns.dense_residual import DenseResidualPlan
+  blocks = [blk for blk in jasper_convnet_layers() if blk.get("residual")]
+  widths, ks = [blk["num_channels"] for blk in blocks], [blk["kernel_size"][0] for blk in blocks]
+  src_c = [jasper_convnet_layers()[0]["num_channels"]] + widths[:-1]
+  torch.manual_seed(0)
+  store = FlatParams(dev)
+  mains = [cb.ConvBN(store, "m%d" % k, "m%d/bn" % k, widths[k], widths[k], ks[k]) for k in range(len(blocks))]
+  res = [[cb.ConvBN(store, "e%d/r%d" % (k, i), "e%d/bn%d" % (k, i), src_c[i], widths[k], 1,
+                    initializer=cb.glorot_uniform_conv) for i in range(k + 1)] for k in range(len(blocks))]
+  store.finalize()
+  for L in mains + [br for e in res for br in e]:
+    L.gamma.master.copy_(0.5 + torch.rand(L.cout))
+    L.beta.master.copy_(torch.randn(L.cout) * 0.1)
+    L.moving_mean.copy_(torch.randn(L.cout) * 0.1)
+    L.moving_var.copy_(0.5 + torch.rand(L.cout))
+  mask = (torch.arange(T, device=dev)[None, :] < lens[:, None])[..., None]
+
+  def act(c):                                        # a masked ReLU output
+    return cb.Act((torch.randn(B, T, c, device=dev).clamp_min(0.0) * mask).to(torch.bfloat16), lens,
+                  requires_grad=False)
+  cb.mx_block_end_wins = lambda cout, k, sources: True      # every class is measured, whatever the rule says today
+  srcs = [act(c) for c in src_c]
+  dpass = DenseResidualPlan(res, dev).begin(False)
+  for s in srcs:
+    dpass.add_source(s)
+  lines = ["B = %d, T = %d, live rows %d of %d" % (B, T, int(lens_h.sum()), B * T), "",
+           "| end | Cout | K | sources (channels) | bf16 ms | mx ms | fused ms | fused+src ms | fused / min(bf16, mx) "
+           "| fused+src / min | spread bf16 / mx / fused | wins | rel L2 fused vs bf16 |",
+           "|---|---|---|---|---|---|---|---|---|---|---|---|---|"]
+  for k, main in enumerate(mains):
+    x = act(widths[k])
+    outs = {}
+
+    def old(mx):
+      main.mxfp8, x.mx = mx, None
+      outs[mx] = cb.conv_bn_dres_actv(main, x, dpass.forward_end(k), lens, "relu", False, None).data
+
+    def fused(cold=False):
+      main.mxfp8, x.mx = True, None
+      if cold:
+        srcs[k].mx = None
+      outs["fused"] = cb.conv_bn_res_bn_actv(main, res[k], x, srcs[:k + 1], lens, "relu", False, None).data
+    fns = {"bf16": lambda: old(False), "mx": lambda: old(True), "fused": fused, "fused+src": lambda: fused(True)}
+    n = max(8, int(3e13 / (2.0 * B * T * widths[k] * (widths[k] * ks[k] + sum(src_c[:k + 1])))))
+    for f in fns.values():
+      for _ in range(3):
+        f()
+    torch.cuda.synchronize()
+    t = {name: [] for name in fns}
+    for _ in range(args.windows):                    # alternate the chains
+      for name, f in fns.items():
+        t[name].append(window(f, n))
+    med = {name: statistics.median(v) for name, v in t.items()}
+    spread = {name: (max(v) - min(v)) / med[name] for name, v in t.items()}
+    best = min(med["bf16"], med["mx"])
+    worst_spread = max(spread.values())
+    rel = float((outs["fused"].float() - outs[False].float()).norm() / outs[False].float().norm())
+    lines.append("| %d | %d | %d | %d (%d) | %.3f | %.3f | %.3f | %.3f | %.2f | %.2f | %.1f %% / %.1f %% / %.1f %% | %s "
+                 "| %.2e |" % (
+                     k, widths[k], ks[k], k + 1, sum(src_c[:k + 1]), med["bf16"], med["mx"], med["fused"],
+                     med["fused+src"], med["fused"] / best, med["fused+src"] / best, 100 * spread["bf16"],
+                     100 * spread["mx"], 100 * spread["fused"],
+                     "yes" if med["fused+src"] / best < 1.0 - worst_spread else "no", rel))
+    print(lines[-1], flush=True)
+  return lines
+
+
 def main():
   ap = argparse.ArgumentParser()
   ap.add_argument("--out", default=None)
   ap.add_argument("--windows", type=int, default=7)
   ap.add_argument("--batch", type=int, default=32)
+  ap.add_argument("--block-ends", action="store_true", help="the dense-residual block ends instead of the plain layers")
   args = ap.parse_args()
   if not torch.cuda.is_available():
     raise SystemExit("bench_conv_mx.py measures on the GPU; none found")
@@ -68,6 +150,13 @@ def main():
   B = args.batch
   lens_h, T = bench_lengths(B)
   lens = torch.from_numpy(lens_h.astype(np.int32)).to(dev)
+  if args.block_ends:
+    text = "\n".join(block_ends(args, dev, B, T, lens_h, lens)) + "\n"
+    print(text)
+    if args.out:
+      with open(args.out, "w") as f:
+        f.write(text)
+    return
   lines = ["B = %d, T = %d, live rows %d of %d" % (B, T, int(lens_h.sum()), B * T), "",
            "| Cin | Cout | K | dil | bf16 chain ms (TF/s) | mx chain ms (TF/s) | of which quantise ms | mx / bf16 "
            "| spread bf16 / mx | wins | rel L2 mx vs bf16 |", "|---|---|---|---|---|---|---|---|---|---|---|"]
