@@ -407,6 +407,17 @@ int os2s_sepconv1d_fwd_mx(os2s_stream_t stream, const uint16_t* x, const float* 
                           const float* ch_scale, const float* ch_shift, int B, int Tin, int Cin, int Cout, int K,
                           int stride, int dil, int padL, int Tout, long long y_stride_b, long long y_stride_t,
                           int out_f32, int act);
+/* os2s_sepconv1d_fwd_mx with the kernel variant chosen by the caller: the same operands, definition, refusals and
+ * errors, and a trailing variant that names how the depthwise half is computed. 0: the register-window FIR on the
+ * vector pipe, what os2s_sepconv1d_fwd_mx runs (bit-identical to it). 1: the Toeplitz-band product on
+ * v_mfma_f32_16x16x32_bf16 with the fp32 taps as a bf16 hi + lo pair (the FIR's result up to fp32 rounding). -1: chosen
+ * by shape (variant 1 for Cin >= 384, from profiles/mxfp8_sepconv_mfma_first_measurements.md). Any other variant:
+ * OS2S_ERR_INVALID_ARG. */
+int os2s_sepconv1d_fwd_mx_variant(os2s_stream_t stream, const uint16_t* x, const float* d, const uint8_t* wq,
+                                  const uint8_t* w_scale, void* y, const int32_t* in_len, const int32_t* out_len,
+                                  const float* ch_scale, const float* ch_shift, int B, int Tin, int Cin, int Cout,
+                                  int K, int stride, int dil, int padL, int Tout, long long y_stride_b,
+                                  long long y_stride_t, int out_f32, int act, int variant);
 /* MXFP8 residual block end in one launch (csrc/conv1d_block_end_mx.hip; a project extension behind the
  * 'mxfp8_inference' parameter of TDNNEncoder). Forward-only replacement, in eval / infer mode, of the whole of
  * conv_bn_res_bn_actv (parts/cnns/conv_blocks.py:61-168): the main tf.layers.conv1d, one tf.layers.conv1d(kernel_size=1)

@@ -1316,11 +1316,13 @@ MX_SEP_MAX_K, MX_SEP_MAX_CIN = 96, 512    # os2s_sepconv1d_fwd_mx: the register-
 
 
 def sepconv1d_fwd_mx(x, d, wq, w_scale, *, pad_left=None, tout=None, in_len=None, out_len=None, ch_scale=None,
-                     ch_shift=None, act=0, out=None, out_f32=False):
+                     ch_shift=None, act=0, out=None, out_f32=False, variant=-1):
   """act(ch_scale * pointwise(mx(bf16(depthwise(x, d))), deq(wq)) + ch_shift), rows at or past out_len zero, in ONE
-  launch (os2s_sepconv1d_fwd_mx, stride 1, dilation 1): the depthwise output is quantised in the kernel and never
-  reaches memory. x [B,Tin,Cin] bf16; d [K,Cin] fp32; wq [Cout,Cin] / w_scale: quantize_mx of the pointwise kernel.
-  pad_left / tout default to TF 'SAME'. -> [B,Tout,Cout] bf16, or fp32 with out_f32."""
+  launch (os2s_sepconv1d_fwd_mx_variant, stride 1, dilation 1): the depthwise output is quantised in the kernel and
+  never reaches memory. x [B,Tin,Cin] bf16; d [K,Cin] fp32; wq [Cout,Cin] / w_scale: quantize_mx of the pointwise
+  kernel. pad_left / tout default to TF 'SAME'. variant: the depthwise half as the register-window FIR (0), as the
+  Toeplitz-band product on the matrix pipe (1), or chosen by shape (-1). -> [B,Tout,Cout] bf16, or fp32 with
+  out_f32."""
   B, Tin, Cin = x.shape
   K, Cin1 = d.shape
   Cout, Cin2 = wq.shape
@@ -1332,12 +1334,12 @@ def sepconv1d_fwd_mx(x, d, wq, w_scale, *, pad_left=None, tout=None, in_len=None
   if out is None:
     out = torch.empty((B, tout, Cout), dtype=dt, device=x.device)
   assert tuple(out.shape) == (B, tout, Cout) and out.stride(2) == 1 and out.dtype == dt and out.is_cuda
-  _lib.C.os2s_sepconv1d_fwd_mx(_stream(), _ptr(x, torch.bfloat16), _ptr(d, torch.float32), _ptr(wq, torch.uint8),
-                               _ptr(w_scale, torch.uint8), c_void_p(out.data_ptr()),
-                               _ptr(in_len, torch.int32, True), _ptr(out_len, torch.int32, True),
-                               _ptr(ch_scale, torch.float32, True), _ptr(ch_shift, torch.float32, True),
-                               B, Tin, Cin, Cout, K, 1, 1, int(pad_left), int(tout), out.stride(0), out.stride(1),
-                               int(bool(out_f32)), int(act))
+  _lib.C.os2s_sepconv1d_fwd_mx_variant(_stream(), _ptr(x, torch.bfloat16), _ptr(d, torch.float32),
+                                       _ptr(wq, torch.uint8), _ptr(w_scale, torch.uint8), c_void_p(out.data_ptr()),
+                                       _ptr(in_len, torch.int32, True), _ptr(out_len, torch.int32, True),
+                                       _ptr(ch_scale, torch.float32, True), _ptr(ch_shift, torch.float32, True),
+                                       B, Tin, Cin, Cout, K, 1, 1, int(pad_left), int(tout), out.stride(0),
+                                       out.stride(1), int(bool(out_f32)), int(act), int(variant))
   return out
 
 

@@ -70,7 +70,48 @@
 // What remains at K = 1 is far above phase 2's matrix work: with one workgroup per CU the DMA waits of both phases
 // are exposed; which phase holds most of that is not established.
 // Follow-up: the Toeplitz-band depthwise on v_mfma_f32_16x16x32_bf16 (depthwise_mfma_fwd_kernel's hi + lo tap pair)
-// inside phase 1, which needs no packed fp32 arithmetic.
+// inside phase 1, which needs no packed fp32 arithmetic. That is variant 1, below.
+//
+// ---- variant 1 (os2s_sepconv1d_fwd_mx_variant): phase 1 on the matrix pipe --------------------------------------
+// Same workgroup, same zq / zs, same phase 2; what is above is variant 0. For one (sample, channel) the depthwise
+// sum is a Toeplitz-band product (header of depthwise_mfma_fwd_kernel), here on v_mfma_f32_16x16x32_bf16:
+//     z[16 s + i] = sum_p T[i][p] X[p][s],   T[i][p] = d[p - i],   X[p][s] = x[t0 - padL + 16 s + p]
+// M = position i in a 16-step segment, N = segment s (a 128-row tile is 8 segments: columns 8 .. 15 repeat 0 .. 7, the
+// same addresses, and serve the store below), K = window position p in J = ceil((16 + K - 1) / 32) steps of 32. The
+// fp32 taps enter as a bf16 hi + lo pair, two MFMAs a step: the fp32-tap sum of the FIR up to fp32 rounding. J is a
+// template parameter (1 .. 4): with a run-time J every step is a basic block that waits for its own reads.
+// Split: groups of 64 channels, wave w owns the 8 consecutive channels 8 w .. 8 w + 7 of the group — one 16-byte slot
+//   of a row — and all 128 rows: 8 J x 2 MFMAs a group, 32 fp32 accumulators a lane.
+// In: thread = (4 window positions, 8 channels): four 16-byte row loads (rows outside [0, in_len) and positions past
+//   128 + K - 1 masked to zero; a dead row's address is clamped, there is no branch), one group ahead in registers,
+//   transposed to eight 8-byte writes, one per channel PLANE (time-contiguous, 112 + 32 J positions). The LDS DMA
+//   cannot transpose. Taps: lane = (tap mod 8, channel) reads 32-byte runs of d, one group ahead, and writes hi / lo
+//   into the wave's own zero-padded tables [8 channels][hi, lo][32 J + 24], tap k at element 16 + k.
+// Fragments: B = one aligned ds_read_b128 of the plane at position 16 s + 32 j + 8 (lane / 16). A = 8 taps from
+//   element 16 + 32 j + 8 (lane / 16) - i, 2-byte aligned: five aligned words and v_alignbit by 0 or 16 bits (a
+//   lane-private unaligned ds_read_b128 costs ~100 cycles, see depthwise_mfma_fwd_kernel). The reads of channel i + 1
+//   are issued before the MFMAs of channel i (two register sets, sched_barrier).
+// Out: acc[i][e] is channel 8 w + i at row 16 s + 4 (lane / 16) + e: a lane packs its 8 channels of a row to bf16 in
+//   registers, one ds_write_b128 into the row-major bounce tile [128 rows][128 B] (columns 0 .. 7 rows e = 0, 1,
+//   columns 8 .. 15 e = 2, 3); after a barrier "8 consecutive channels per lane, 4 lanes per 32-block" is a
+//   ds_read_b128, then mx_quantize8 and the zq / zs stores of variant 0. Two barriers a group.
+// LDS: zq + zs as above (66 KB at Cin 512) + one region shared with phase 2: planes 64 x 288 B (J = 1) or 64 x 544 B
+//   + bounce 16 KB + tables 64 x 2 x (32 J + 24) x 2 B: 48 KB (J = 1) .. 88 KB (J = 4); 154 KB at Cin 512, K 96.
+// Bank conflicts: plane writes — 32 lanes = 4 positions-of-4 (8 B apart) x 8 planes whose stride is 32 B mod 256 B:
+//   256 distinct bytes, that is why a plane is 288 or 544 B long; plane reads — a wave reads ONE plane, 16 lanes of a
+//   16-byte quarter read chunks 2 s + const, columns 8 .. 15 the addresses of 0 .. 7 (broadcast): no conflict; tap
+//   reads — ONE table, the wave's words span 20 consecutive ones, equal addresses broadcast: none; bounce — slot w of
+//   row r lies at w ^ (r >> 4): the 8 lanes of a 128-byte write beat have 8 different s, so 8 different slots; the read
+//   back takes whole rows.
+// Resources (hipcc -O3, gfx950, -Rpass-analysis=kernel-resource-usage), J = 1 / 2 / 3 / 4: 144 / 164 / 198 / 241
+//   VGPRs, 0 AGPRs, 74 / 76 / 83 / 91 SGPRs, scratch 0, no VGPR spill (variant 0 is unchanged: 145 VGPRs).
+// Measured (profiles/mxfp8_sepconv_mfma_first_measurements.md, same batch): the chain with this launch takes 22.1 /
+//   22.0 / 31.1 us at (256, 256, 33) / (256, 256, 39) / (256, 512, 51) and 49.6 / 49.8 / 49.7 us at (512, 512, 51 / 63 /
+//   75): 0.65 - 0.84 x variant 0, 0.87 - 0.90 x the bf16 chain at Cin 512. K moves it only through J; with one tap it
+//   takes 18.2 / 23.2 / 34.3 us, 1 - 2 us more than variant 0 with one tap. So a window step more (its MFMAs,
+//   fragment reads, 32 more plane positions and table elements) costs about 4 us at Cin 256 and 7.6 us at Cin 512 —
+//   J = 2 at K 33 / 39, J = 3 at K 51 .. 75 — and the larger part of the launch now is what is left at K = 1 (staging, quantiser, phase
+//   2), as §"resources" above says of variant 0; which part of that is largest is not established.
 #include <type_traits>
 
 #include "mx_common.hpp"
@@ -111,6 +152,167 @@ __device__ __forceinline__ void sep_row(const char* ptr, float (&dst)[2]) {
   dst[1] = bfhi(v);
 }
 
+// ---- variant 1: phase 1 as a Toeplitz-band product (geometry: the head of this file) ----
+constexpr int kSmCh = 64;                             // channels of a group: 8 consecutive ones per wave
+constexpr int kSmOff = 16;                            // table element of tap 0
+constexpr int kSmBounce = kSepRows * kSmCh * 2;       // z of one group, bf16, row-major
+__host__ __device__ constexpr int sm_steps(int K) { return (16 + K - 1 + 31) / 32; }        // window steps of 32
+__host__ __device__ constexpr int sm_rows(int K) { return 112 + 32 * sm_steps(K); }         // time steps of a plane
+__host__ __device__ constexpr int sm_plane_bytes(int K) { return sm_steps(K) == 1 ? 288 : 544; }   // % 256 == 32
+__host__ __device__ constexpr int sm_table(int K) { return 32 * sm_steps(K) + 24; }         // elements of a tap table
+__host__ __device__ constexpr int sm_phase1_bytes(int K) {
+  return kSmCh * sm_plane_bytes(K) + kSmBounce + kSmCh * 2 * sm_table(K) * 2;
+}
+
+template <int J>   // J = sm_steps(K): a constant, so that the fragment reads of a group's 8 J steps can be issued ahead of its MFMAs
+__device__ __forceinline__ void sep_phase1_mfma(const MxSepArgs& p, int b, int t0, int lin, char* zq, char* zs,
+                                                char* sh) {
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
+  constexpr int pb = J == 1 ? 288 : 544, wt = 32 * J + 24;           // sm_plane_bytes, sm_table
+  const int ng = p.Cin >> 6;
+  char* const planes = sh;                             // [64 planes][pb]: channel 8 w + i of the group is plane 8 i + w
+  char* const bounce = sh + kSmCh * pb;                // [128 rows][8 slots of 16 B], slot w of row r at w ^ (r >> 4)
+  bf16_t* const tabs = reinterpret_cast<bf16_t*>(bounce + kSmBounce) + wid * 16 * wt;   // this wave's [8][hi, lo][wt]
+
+  // staging item: plane positions 4 p4 .. 4 p4 + 3 (input rows t0 - padL + ...) x the 8 channels of wave cg. Rows
+  // outside [0, in_len) and positions past the tile's window (they meet zero taps only) are zeros, not loads
+  // (a dead row loads row 0 or Tin - 1 and is masked where it is used, a group later: no branch around the loads
+  // and nothing that waits for them before the MFMAs of the group in between)
+  const int cg = tid & 7, p4 = tid >> 3, live = kSepRows + p.K - 1;
+  const bf16_t* xb[4];
+  uint32_t xm[4];
+#pragma unroll
+  for (int u = 0; u < 4; ++u) {
+    const int r = p4 * 4 + u, tin = t0 - p.padL + r;
+    xb[u] = p.x + ((long long)b * p.Tin + min(max(tin, 0), p.Tin - 1)) * p.Cin + cg * 8;
+    xm[u] = (r < live && tin >= 0 && tin < lin) ? 0xffffffffu : 0u;
+  }
+  u32x4 xr[4];
+  auto load_rows = [&](int g) {
+#pragma unroll
+    for (int u = 0; u < 4; ++u) xr[u] = *reinterpret_cast<const u32x4*>(xb[u] + g * kSmCh);
+  };
+  // taps of the wave's 8 channels: lane = (tap k mod 8, channel), 32-byte runs of d
+  constexpr int kTapRegs = 4 * J - 1;                 // K <= 32 J - 15: taps k < 32 J - 8, zeros from K on
+  const int tk = lane >> 3, ti = lane & 7;
+  float tp[kTapRegs];
+  auto load_taps = [&](int g) {
+#pragma unroll
+    for (int r = 0; r < kTapRegs; ++r) {
+      const int k = r * 8 + tk;
+      tp[r] = p.d[(long long)min(k, p.K - 1) * p.Cin + g * kSmCh + wid * 8 + ti];       // masked at the table
+    }
+  };
+  // the tables are zero outside [kSmOff, kSmOff + K), and K is the same for every group
+  for (int i = lane; i < 2 * wt; i += 64) reinterpret_cast<u32x4*>(tabs)[i] = u32x4{0u, 0u, 0u, 0u};
+  asm volatile("" ::: "memory");
+  load_rows(0);
+  load_taps(0);
+
+  const int n = lane & 15, kg = lane >> 4, seg = n & 7, up = n >> 3;   // columns 8 .. 15 repeat segments 0 .. 7
+  const int e0 = kSmOff + 8 * kg - n;                  // table element of A[i = n][p = 8 kg] of step 0: 1 .. 40
+  const uint32_t shb = (e0 & 1) ? 16u : 0u;
+  for (int g = 0; g < ng; ++g) {
+    // nobody reads the planes of group g - 1 any more (barrier B below); the tables are the wave's own
+    if (p4 * 4 < 112 + 32 * J) {                        // sm_rows
+      char* const dst = planes + cg * pb + p4 * 8;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        // channel 2k (low halves) and 2k + 1 (high halves) of the wave's eight
+        u32x2 lo, hi;
+        const uint32_t x0 = xr[0][k] & xm[0], x1 = xr[1][k] & xm[1], x2 = xr[2][k] & xm[2], x3 = xr[3][k] & xm[3];
+        lo[0] = (x0 & 0xffffu) | (x1 << 16);
+        lo[1] = (x2 & 0xffffu) | (x3 << 16);
+        hi[0] = (x0 >> 16) | (x1 & 0xffff0000u);
+        hi[1] = (x2 >> 16) | (x3 & 0xffff0000u);
+        *reinterpret_cast<u32x2*>(dst + (2 * k) * 8 * pb) = lo;
+        *reinterpret_cast<u32x2*>(dst + (2 * k + 1) * 8 * pb) = hi;
+      }
+    }
+#pragma unroll
+    for (int r = 0; r < kTapRegs; ++r) {
+      const int k = r * 8 + tk;
+      const float w = k < p.K ? tp[r] : 0.f;
+      const bf16_t h = f2bf(w);
+      tabs[(2 * ti) * wt + kSmOff + k] = h;
+      tabs[(2 * ti + 1) * wt + kSmOff + k] = f2bf(w - bf2f(h));
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    mx_barrier();                                      // A: the planes of group g are everybody's
+    if (g + 1 < ng) {
+      load_rows(g + 1);
+      load_taps(g + 1);
+    }
+    // D[i][n] = sum_p T[i][p] X[p][n]: T[i][p] = tap p - i, X[p][n] = plane position 16 seg + p
+    // The fragments of channel i + 1 are read while channel i multiplies (two register sets, the scheduler held to
+    // that order): left to itself the compiler waits for each step's reads right in front of its two MFMAs.
+    // B fragment: one aligned 16-byte read of the plane. A fragment: it starts at a 2-byte-aligned element, so five
+    // aligned words and a funnel shift by 0 or 16 bits (depthwise_mfma_fwd_kernel says why it is no unaligned read)
+    f32x4 acc[8];
+    bf16x8 fb[2][J];
+    uint32_t fh[2][J][5], fl[2][J][5];
+    auto read_frags = [&](int i, int s) {
+      const char* const pl = planes + (i * 8 + wid) * pb + (2 * seg + kg) * 16;
+      const uint32_t* const th = reinterpret_cast<const uint32_t*>(tabs + (2 * i) * wt) + (e0 >> 1);
+      const uint32_t* const tl = th + (wt >> 1);
+#pragma unroll
+      for (int j = 0; j < J; ++j) {
+        fb[s][j] = *reinterpret_cast<const bf16x8*>(pl + j * 64);
+#pragma unroll
+        for (int k = 0; k < 5; ++k) { fh[s][j][k] = th[16 * j + k]; fl[s][j][k] = tl[16 * j + k]; }
+      }
+    };
+    read_frags(0, 0);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      if (i + 1 < 8) read_frags(i + 1, (i + 1) & 1);
+      __builtin_amdgcn_sched_barrier(0);
+      acc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int j = 0; j < J; ++j) {
+        u32x4 ah, al;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          ah[k] = __builtin_amdgcn_alignbit(fh[i & 1][j][k + 1], fh[i & 1][j][k], shb);
+          al[k] = __builtin_amdgcn_alignbit(fl[i & 1][j][k + 1], fl[i & 1][j][k], shb);
+        }
+        acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, ah), fb[i & 1][j], acc[i], 0, 0, 0);
+        acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, al), fb[i & 1][j], acc[i], 0, 0, 0);
+      }
+      __builtin_amdgcn_sched_barrier(0);
+    }
+    // acc[i][e]: channel 8 w + i at row 16 seg + 4 kg + e. Eight channels of a row are one 16-byte slot; the lanes of
+    // the repeated columns store e = 2, 3, the others e = 0, 1
+#pragma unroll
+    for (int ee = 0; ee < 2; ++ee) {
+      u32x4 o;
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+        o[k] = pack2bf(up ? acc[2 * k][2 + ee] : acc[2 * k][ee], up ? acc[2 * k + 1][2 + ee] : acc[2 * k + 1][ee]);
+      const int row = 16 * seg + 4 * kg + 2 * up + ee;
+      *reinterpret_cast<u32x4*>(bounce + row * 128 + ((wid ^ seg) << 4)) = o;
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    mx_barrier();                                      // B: everybody is through with the planes; z of the group is there
+    const int q = tid & 7, ct = g >> 1;                // 8 channels 8 q .. of the group; quad = one block of 32
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      const int row = h * 64 + (tid >> 3);
+      const u32x4 v = *reinterpret_cast<const u32x4*>(bounce + row * 128 + ((q ^ (row >> 4)) << 4));
+      int byte;
+      const u32x2 o = mx_quantize8(v, byte);
+      const int slot = (g & 1) * 4 + (q >> 1);
+      *reinterpret_cast<u32x2*>(zq + ct * kSepZTile + row * kMxKTile + ((slot ^ ((row >> 1) & 7)) << 4) +
+                                (q & 1) * 8) = o;
+      if ((q & 3) == 0) zs[(ct * kSepRows + row) * 4 + (g & 1) * 2 + (q >> 2)] = (char)byte;
+    }
+  }
+}
+
+// V: phase 1. 0 = the register-window FIR (variant 0); 1 .. 4 = the Toeplitz-band product on the matrix pipe (variant
+// 1) with V = sm_steps(K) window steps.
+template <int V>
 __global__ __launch_bounds__(512, 1) void sepconv1d_mx_kernel(MxSepArgs p) {
   constexpr int MI = 2, NI = 2;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -137,7 +339,9 @@ __global__ __launch_bounds__(512, 1) void sepconv1d_mx_kernel(MxSepArgs p) {
   char* const sh = zs + nct * (kSepRows * 4);          // the shared region
 
   // ================= phase 1: depthwise FIR -> bf16 -> MX quantiser -> zq / zs =================
-  {
+  if constexpr (V >= 1) {
+    sep_phase1_mfma<V>(p, b, t0, lin, zq, zs, sh);
+  } else {
     const int nsl = p.slab >> 10;                      // DMA instructions of one slab, 8 rows each
     const int r0 = t0 - p.padL;                        // the input row of slab row 0
     const int row_bytes = p.Cin * 2;
@@ -371,14 +575,17 @@ __global__ __launch_bounds__(512, 1) void sepconv1d_mx_kernel(MxSepArgs p) {
   }
 }
 
-}  // namespace os2s
+// variant -1: the choice by shape. Variant 1 where it measured faster than variant 0
+// (profiles/mxfp8_sepconv_mfma_first_measurements.md); 384 is the midpoint of the measured widths 256 and 512, a
+// convention.
+static int sep_variant_by_shape(int Cin) { return Cin >= 384 ? 1 : 0; }
 
-extern "C" int os2s_sepconv1d_fwd_mx(os2s_stream_t stream, const uint16_t* x, const float* d, const uint8_t* wq,
-                                     const uint8_t* w_scale, void* y, const int32_t* in_len, const int32_t* out_len,
-                                     const float* ch_scale, const float* ch_shift, int B, int Tin, int Cin, int Cout,
-                                     int K, int stride, int dil, int padL, int Tout, long long y_stride_b,
-                                     long long y_stride_t, int out_f32, int act) {
-  using namespace os2s;
+static int sepconv1d_mx_launch(os2s_stream_t stream, const uint16_t* x, const float* d, const uint8_t* wq,
+                               const uint8_t* w_scale, void* y, const int32_t* in_len, const int32_t* out_len,
+                               const float* ch_scale, const float* ch_shift, int B, int Tin, int Cin, int Cout, int K,
+                               int stride, int dil, int padL, int Tout, long long y_stride_b, long long y_stride_t,
+                               int out_f32, int act, int variant) {
+  OS2S_REQUIRE(variant >= -1 && variant <= 1);
   OS2S_REQUIRE(x && d && wq && w_scale && y);
   OS2S_REQUIRE(B >= 1 && Tin >= 1 && Tout >= 1 && K >= 1 && stride >= 1 && dil >= 1 && Cin >= 1 && Cout >= 1);
   if (stride != 1 || dil != 1 || K > kSepMaxK) return OS2S_ERR_UNSUPPORTED;
@@ -401,8 +608,41 @@ extern "C" int os2s_sepconv1d_fwd_mx(os2s_stream_t stream, const uint16_t* x, co
   p.slab = sep_slab_bytes(K);
   if ((long long)B * p.MT >= (1ll << 31)) return OS2S_ERR_UNSUPPORTED;
   const int nct = ceil_div(Cin, kMxKTile);
-  const int phase1 = 2 * p.slab + K * 64 * 4, phase2 = 2 * kMxOperand;
+  if (variant < 0) variant = sep_variant_by_shape(Cin);
+  const int phase1 = variant == 1 ? sm_phase1_bytes(K) : 2 * p.slab + K * 64 * 4, phase2 = 2 * kMxOperand;
   const size_t lds = (size_t)nct * (kSepZTile + kSepRows * 4) + (size_t)(phase1 > phase2 ? phase1 : phase2);
-  OS2S_LAUNCH_LDS(sepconv1d_mx_kernel, dim3(B * p.MT), dim3(512), lds, (hipStream_t)stream, p);
+  const int J = sm_steps(K);
+  if (variant == 1 && J == 1) {
+    OS2S_LAUNCH_LDS(sepconv1d_mx_kernel<1>, dim3(B * p.MT), dim3(512), lds, (hipStream_t)stream, p);
+  } else if (variant == 1 && J == 2) {
+    OS2S_LAUNCH_LDS(sepconv1d_mx_kernel<2>, dim3(B * p.MT), dim3(512), lds, (hipStream_t)stream, p);
+  } else if (variant == 1 && J == 3) {
+    OS2S_LAUNCH_LDS(sepconv1d_mx_kernel<3>, dim3(B * p.MT), dim3(512), lds, (hipStream_t)stream, p);
+  } else if (variant == 1) {
+    OS2S_LAUNCH_LDS(sepconv1d_mx_kernel<4>, dim3(B * p.MT), dim3(512), lds, (hipStream_t)stream, p);
+  } else {
+    OS2S_LAUNCH_LDS(sepconv1d_mx_kernel<0>, dim3(B * p.MT), dim3(512), lds, (hipStream_t)stream, p);
+  }
   return OS2S_OK;
+}
+
+}  // namespace os2s
+
+extern "C" int os2s_sepconv1d_fwd_mx(os2s_stream_t stream, const uint16_t* x, const float* d, const uint8_t* wq,
+                                     const uint8_t* w_scale, void* y, const int32_t* in_len, const int32_t* out_len,
+                                     const float* ch_scale, const float* ch_shift, int B, int Tin, int Cin, int Cout,
+                                     int K, int stride, int dil, int padL, int Tout, long long y_stride_b,
+                                     long long y_stride_t, int out_f32, int act) {
+  return os2s::sepconv1d_mx_launch(stream, x, d, wq, w_scale, y, in_len, out_len, ch_scale, ch_shift, B, Tin, Cin,
+                                   Cout, K, stride, dil, padL, Tout, y_stride_b, y_stride_t, out_f32, act, 0);
+}
+
+extern "C" int os2s_sepconv1d_fwd_mx_variant(os2s_stream_t stream, const uint16_t* x, const float* d,
+                                             const uint8_t* wq, const uint8_t* w_scale, void* y,
+                                             const int32_t* in_len, const int32_t* out_len, const float* ch_scale,
+                                             const float* ch_shift, int B, int Tin, int Cin, int Cout, int K,
+                                             int stride, int dil, int padL, int Tout, long long y_stride_b,
+                                             long long y_stride_t, int out_f32, int act, int variant) {
+  return os2s::sepconv1d_mx_launch(stream, x, d, wq, w_scale, y, in_len, out_len, ch_scale, ch_shift, B, Tin, Cin,
+                                   Cout, K, stride, dil, padL, Tout, y_stride_b, y_stride_t, out_f32, act, variant);
 }

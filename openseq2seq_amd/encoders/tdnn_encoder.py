@@ -51,8 +51,9 @@ class TDNNEncoder(Encoder):
         # convolutions run on the MXFP8 kernel (csrc/conv1d_mx.hip): e4m3 operands with one power-of-two scale per
         # 32 channels, eval BatchNorm + ReLU + mask in its epilogue (parts/cnns/conv_blocks.py::mx_conv_usable).
         # The stride-1, dilation-1 separable layers (K <= 96, Cin <= 512) run depthwise FIR, quantiser, pointwise GEMM
-        # and that epilogue in one launch (csrc/sepconv1d_mx.hip, ::mx_sep_usable; by the measured rule only plain
-        # layers with Cin < 384, the main branch of a residual block end keeps bf16). Strided, dilated-separable and
+        # and that epilogue in one launch (csrc/sepconv1d_mx.hip, ::mx_sep_usable; by the measured rule plain
+        # layers only — from 384 channels on with the depthwise phase on the matrix pipe, ::mx_sep_variant — while the
+        # main branch of a residual block end keeps bf16). Strided, dilated-separable and
         # sample-norm layers, the 1x1 residual branches (plain or folded separable) and training keep bf16.
         'mxfp8_inference': bool,
     })

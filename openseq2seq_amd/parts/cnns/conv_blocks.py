@@ -323,15 +323,28 @@ def mx_block_end(main, res_branches, x, res_inputs, tout, pl, act, out_len):
 def mx_sep_wins(cin, cout, k, block_end=False):
   """The by-shape rule of 'mxfp8_inference' on the separable layers, from
   profiles/mxfp8_sepconv_first_measurements.md (MI355X, the QuartzNet 15x5 stride-1 layer classes at B = 32):
-  bn_finalize + the fused launch took 0.79 - 0.82 x the time of the bf16 chain of four launches at Cin 256 (K 33, 39,
-  and the 256 -> 512 layer with K 51; spread <= 1 %), but 1.09 - 1.30 x at Cin 512 (K 51, 63, 75): the register-window
-  FIR of phase 1 grows with Cin K and is up to half of the launch there. Cin 512 keeps bf16. Only the widths 256 and
-  512 were measured: the boundary at 384 is the midpoint between them and nothing more, and cout and k do not enter
-  because no measured class turned on them.
+  bn_finalize + the fused launch with the register-window FIR (variant 0) took 0.79 - 0.83 x the time of the bf16
+  chain of four launches at Cin 256 (K 33, 39, and the 256 -> 512 layer with K 51), but 1.11 - 1.33 x at Cin 512
+  (K 51, 63, 75). With the depthwise half on the matrix pipe (variant 1,
+  profiles/mxfp8_sepconv_mfma_first_measurements.md) the same chain took 0.87 - 0.90 x the bf16 chain's time at
+  Cin 512 and 0.65 - 0.81 x variant 0's (spreads <= 0.8 %): plain layers take the fused kernel at every width the
+  kernel has, with the variant of mx_sep_variant. cout and k do not enter because no measured class turned on them.
   block_end: the main branch of a residual block end, where the fused launch has the identity epilogue and the
-  BatchNorm / residual sum stays a launch of its own. That chain took 1.07 - 1.10 x the bf16 chain's time at Cin 256
-  and 1.29 - 1.49 x at Cin 512: block ends keep bf16 at every width."""
-  return cin < 384 and not block_end
+  BatchNorm / residual sum stays a launch of its own. At Cin 512 that chain took 1.32 - 1.53 x the bf16 chain's time
+  with variant 0 and 1.06 - 1.10 x with variant 1: those block ends keep bf16. At Cin 256 it took 0.92 - 0.97 x with
+  variant 1 (1.07 - 1.13 x with variant 0), but the layers below 384 channels keep variant 0 and their bits for now
+  (mx_sep_variant), so block ends keep bf16 at every width."""
+  return not block_end
+
+
+def mx_sep_variant(cin, cout, k):
+  """The kernel variant of os2s_sepconv1d_fwd_mx_variant a layer takes: the register-window FIR (0) below 384
+  channels, those layers' kernel since 'mxfp8_inference' reached them, and the matrix-pipe depthwise (1) from there
+  on, where only it beats the bf16 chain (mx_sep_wins has the measurements). Variant 1 measured faster than variant
+  0 at Cin 256 too (0.78 - 0.84 x); moving those layers changes their bits (fp32 summation order of the depthwise
+  half) and is left to a change of its own. Only the widths 256 and 512 were measured: 384 is their midpoint, a
+  convention."""
+  return 0 if cin < 384 else 1
 
 
 def mx_sep_usable(layer, x, act, training, tape, block_end=False):
@@ -350,7 +363,8 @@ def mx_sep_conv(layer, x, tout, pl, scale=None, shift=None, act=0, out_len=None)
   quantised in the kernel, the pointwise kernel is the layer's cached MXFP8 copy."""
   wq, ws = layer.mx_weight()
   return capi.sepconv1d_fwd_mx(x.data, layer.depthwise.master, wq, ws, pad_left=pl, tout=tout, in_len=x.lens,
-                               out_len=out_len, ch_scale=scale, ch_shift=shift, act=act)
+                               out_len=out_len, ch_scale=scale, ch_shift=shift, act=act,
+                               variant=mx_sep_variant(layer.cin, layer.cout, layer.k))
 
 
 def bn_vectors(C, dev, training):

@@ -2,20 +2,21 @@
 chain, each as TDNNEncoder issues it, at the five stride-1 layer classes of quartznet15x5_LibriSpeech.py and the
 256 -> 512 transition (B = 32, the ragged lengths of bench.py's synthetic batch after the stride-2 first layer):
 
-  mx:   os2s_bn_finalize + os2s_sepconv1d_fwd_mx with scale / shift / ReLU / mask (the weight copy is cached)
   bf16: os2s_depthwise_conv1d_fwd + os2s_conv1d_fwd (K = 1) + os2s_bn_finalize + os2s_bn_act_fwd
-  mx block end: os2s_bn_finalize + os2s_sepconv1d_fwd_mx with the identity epilogue + os2s_bn_act_fwd: the main branch
-        of a residual block end, against the same bf16 chain (the residual branch is common to both)
+  vN:   os2s_bn_finalize + os2s_sepconv1d_fwd_mx_variant(variant = N) with scale / shift / ReLU / mask (the weight copy
+        is cached), for every N of --variant: 0 the register-window FIR, 1 the depthwise phase on the matrix pipe
+  vN block end: os2s_bn_finalize + the same launch with the identity epilogue + os2s_bn_act_fwd: the main branch of a
+        residual block end, against the same bf16 chain (the residual branch is common to both)
 
-Chain times from device events around windows of back-to-back chains, every shape warmed up, the two chains
-alternated inside one process; the median of the windows next to their spread ((max - min) / median). These are call
-times of the chain, not a kernel's share of peak. `wins` is the rule parts/cnns/conv_blocks.py::mx_sep_wins encodes:
-the mx median beats the bf16 median by more than both spreads. The mx chain with a one-tap depthwise kernel shows
-what the FIR costs: (mx chain - mx chain at K = 1) is the register-window FIR over its taps. rel L2: the fused layer
-output against the bf16 one.
+Chain times from device events around windows of back-to-back chains, every shape warmed up, all chains alternated
+inside one process; the median of the windows next to their spread ((max - min) / median). These are call times of
+the chain, not a kernel's share of peak. `takes` is the rule parts/cnns/conv_blocks.py::mx_sep_wins / mx_sep_variant
+encode: the fastest chain, if its median beats every other chain's by more than the larger of the two spreads.
+`at K = 1`: the chain with a one-tap depthwise kernel; what it takes off the chain is the cost of the taps. rel L2:
+the fused layer output against the bf16 one.
 Prints a markdown table; --out writes it to a file as well.
 
-  python tools/bench_sepconv_mx.py [--out sepconv_mx.md] [--windows 7]
+  python tools/bench_sepconv_mx.py [--out sepconv_mx.md] [--windows 7] [--variant 0 1]
 """
 import argparse
 import os
@@ -56,6 +57,8 @@ def main():
   ap.add_argument("--windows", type=int, default=7)
   ap.add_argument("--batch", type=int, default=32)
   ap.add_argument("--calls", type=int, default=1000, help="chains per window")
+  ap.add_argument("--variant", type=int, nargs="+", default=[0, 1], choices=[-1, 0, 1],
+                  help="kernel variants of os2s_sepconv1d_fwd_mx_variant to time (0: FIR, 1: matrix pipe, -1: by shape)")
   args = ap.parse_args()
   if not torch.cuda.is_available():
     raise SystemExit("bench_sepconv_mx.py measures on the GPU; none found")
@@ -63,10 +66,13 @@ def main():
   B = args.batch
   lens_h, T = bench_lengths(B)
   lens = torch.from_numpy(lens_h.astype(np.int32)).to(dev)
+  vs = args.variant
+  per_v = lambda fmt: " | ".join(fmt % v for v in vs)
   lines = ["B = %d, T = %d, live rows %d of %d" % (B, T, int(lens_h.sum()), B * T), "",
-           "| Cin | Cout | K | bf16 chain us | of which depthwise / pointwise us | mx chain us | mx chain at K = 1 us "
-           "| mx / bf16 | spread bf16 / mx | wins | mx block-end chain us | / bf16 | wins | rel L2 mx vs bf16 |",
-           "|---|---|---|---|---|---|---|---|---|---|---|---|---|---|"]
+           "| Cin | Cout | K | bf16 chain us | spread | of which depthwise / pointwise us | " +
+           per_v("v%d chain us | spread | at K = 1 us | / bf16 | block-end chain us | spread | / bf16 | rel L2 vs bf16") +
+           " | plain: takes | block end: takes |",
+           "|---" * (6 + 8 * len(vs) + 2) + "|"]
   for cin, cout, K in SHAPES:
     torch.manual_seed(cin + cout + K)
     x = torch.randn(B, T, cin, device=dev).clamp_min(0.0).to(torch.bfloat16)       # a ReLU output
@@ -77,7 +83,7 @@ def main():
     mean, var = torch.randn(cout, device=dev) * 0.1, 0.5 + torch.rand(cout, device=dev)
     sc, sh = torch.empty(cout, device=dev), torch.empty(cout, device=dev)
     y = torch.empty(B, T, cout, device=dev, dtype=torch.bfloat16)
-    out16, out8 = torch.empty_like(y), torch.empty_like(y)
+    out16 = torch.empty_like(y)
     wq, ws = capi.quantize_mx(w.view(cout, cin))
     zbuf = []
 
@@ -96,20 +102,26 @@ def main():
       finalize()
       capi.bn_act_fwd([y], [sc], [sh], out16, lens, 1, 1.0, 0)
 
-    def mx():
-      finalize()
-      capi.sepconv1d_fwd_mx(x, d, wq, ws, in_len=lens, out_len=lens, ch_scale=sc, ch_shift=sh, act=1, out=out8)
-    d1, out1, y8, oute = d[:1].contiguous(), torch.empty_like(out8), torch.empty_like(y), torch.empty_like(y)
+    d1, y8 = d[:1].contiguous(), torch.empty_like(y)
+    outs = {v: torch.empty_like(y) for v in vs}
+    scratch = torch.empty_like(y)
 
-    def mx_end():     # a residual block end's main branch: identity epilogue, then the BatchNorm / activation pass
-      finalize()
-      capi.sepconv1d_fwd_mx(x, d, wq, ws, in_len=lens, out_len=lens, out=y8)
-      capi.bn_act_fwd([y8], [sc], [sh], oute, lens, 1, 1.0, 0)
+    def mx(v, taps=d, out=None):   # the plain layer; taps = d1: a one-tap depthwise, what is left is not the tap loop
+      def f():
+        finalize()
+        capi.sepconv1d_fwd_mx(x, taps, wq, ws, in_len=lens, out_len=lens, ch_scale=sc, ch_shift=sh, act=1,
+                              out=scratch if out is None else out, variant=v)
+      return f
 
-    def mx_k1():      # the mx chain with a one-tap FIR: what is left of it is staging, quantiser, GEMM, epilogue
-      finalize()
-      capi.sepconv1d_fwd_mx(x, d1, wq, ws, in_len=lens, out_len=lens, ch_scale=sc, ch_shift=sh, act=1, out=out1)
-    fns = {"bf16": bf16, "mx": mx, "dw": depthwise, "pw": pointwise, "k1": mx_k1, "end": mx_end}
+    def mx_end(v):    # a residual block end's main branch: identity epilogue, then the BatchNorm / activation pass
+      def f():
+        finalize()
+        capi.sepconv1d_fwd_mx(x, d, wq, ws, in_len=lens, out_len=lens, out=y8, variant=v)
+        capi.bn_act_fwd([y8], [sc], [sh], scratch, lens, 1, 1.0, 0)
+      return f
+    fns = {"bf16": bf16, "dw": depthwise, "pw": pointwise}
+    for v in vs:
+      fns.update({("mx", v): mx(v, out=outs[v]), ("k1", v): mx(v, d1), ("end", v): mx_end(v)})
     for f in fns.values():
       for _ in range(3):
         f()
@@ -120,17 +132,26 @@ def main():
         t[k].append(window(f, args.calls) * 1e3)
     med = {k: statistics.median(v) for k, v in t.items()}
     spread = {k: (max(v) - min(v)) / med[k] for k, v in t.items()}
-    ratio = med["mx"] / med["bf16"]
-    wins = ratio < 1.0 - max(spread["bf16"], spread["mx"])
-    ratio_end = med["end"] / med["bf16"]
-    wins_end = ratio_end < 1.0 - max(spread["bf16"], spread["end"])
-    rel = float((out8.float() - out16.float()).norm() / out16.float().norm())
-    lines.append("| %d | %d | %d | %.1f | %.1f / %.1f | %.1f | %.1f | %.2f | %.1f %% / %.1f %% | %s | %.1f | %.2f | %s "
-                 "| %.2e |" % (
-        cin, cout, K, med["bf16"], med["dw"], med["pw"], med["mx"], med["k1"], ratio, 100 * spread["bf16"],
-        100 * spread["mx"], "yes" if wins else "no", med["end"], ratio_end, "yes" if wins_end else "no", rel))
+
+    def takes(kind):  # the fastest chain, if it beats every other by more than the larger of the two spreads
+      best = min(["bf16"] + [(kind, v) for v in vs], key=lambda k: med[k])
+      clear = all(med[best] < med[k] * (1.0 - max(spread[best], spread[k]))
+                  for k in ["bf16"] + [(kind, v) for v in vs] if k != best)
+      name = best if best == "bf16" else "v%d" % best[1]
+      return name if clear else name + " (inside the spread)"
+    cells = []
+    for v in vs:
+      mx(v, out=outs[v])()
+      bf16()
+      rel = float((outs[v].float() - out16.float()).norm() / out16.float().norm())
+      cells.append("%.1f | %.1f %% | %.1f | %.2f | %.1f | %.1f %% | %.2f | %.2e" % (
+          med["mx", v], 100 * spread["mx", v], med["k1", v], med["mx", v] / med["bf16"], med["end", v],
+          100 * spread["end", v], med["end", v] / med["bf16"], rel))
+    lines.append("| %d | %d | %d | %.1f | %.1f %% | %.1f / %.1f | %s | %s | %s |" % (
+        cin, cout, K, med["bf16"], 100 * spread["bf16"], med["dw"], med["pw"], " | ".join(cells), takes("mx"),
+        takes("end")))
     print(lines[-1], flush=True)
-    del x, w, y, out16, out8, wq
+    del x, w, y, out16, outs, scratch, wq
   text = "\n".join(lines) + "\n"
   print(text)
   if args.out:
